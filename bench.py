@@ -15,7 +15,12 @@ ranks with no data-path collective (weak scaling); RCCL carries the quant-table
 broadcast from rank 0, the barrier, the max-over-ranks time and the per-rank
 frame-0 parity gather (`parity_ranks`).
 
-Prints ONE JSON line (rank 0).  The roofline object describes the dominant
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps`
+steps, writes the last step's outputs when `--dump-outputs DIR` is given, and
+prints the headline fields (`metric`, `value`, `unit`, `ms_per_step`, ...).
+Everything else -- launch profile and roofline, entropy coding, parity against
+the oracle, CPU baseline, north-star point, host path -- runs only with
+`--full`, after the headline region.  The roofline object describes the dominant
 kernel -- the single longest launch of a step -- with ALGORITHMIC bytes: a
 forward front end (k_fwd32i) reads 3 B/px RGB and writes 2*S B/px int16
 coefficients, an inverse (k_inv_fast) the reverse (S = coefficients per pixel,
@@ -83,6 +88,16 @@ def parse():
                     help='1: image-stream pipelining, two buffer sets; the forward of batch k+1 runs beside the '
                          'inverse of batch k on a second stream (measured no faster: the launches share CUs at '
                          'workgroup granularity).  0 (default): one jds_plan_run (forward then inverse) per step')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline region also run every other leg: per-kernel launch profile and '
+                         'roofline, entropy coding, frame-0 parity against the oracle, CPU baseline, north-star '
+                         'point, host path (--sweep: statistics gather, batched SSIM, parity); each leg keeps its '
+                         'own --no-* switch.  Without it a run sets up, warms up, times the steps and prints the '
+                         'headline line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step computed (reconstructed frames, '
+                         'coefficients, per-frame statistics) as DIR/<name>.npy: float32 / float64, a fixed seeded '
+                         'sample of the large arrays')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher check without a GPU: each rank joins the process group (gloo), one all-reduce, '
                          'rank 0 prints the world it saw (tests/test_bench_launch_cpu.py)')
@@ -193,6 +208,40 @@ def max_over_ranks(x, dev, backend):
     t = torch.tensor([x], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_SAMPLE = 4 << 20  # elements kept of a larger array over all ranks: 16 MiB as float32, in all below 64 MB
+DUMP_STATS_SKIP = ('fwd_ms', 'inv_ms', 'reserved')  # host-path timings and padding: not results of a plan run
+
+
+def dump_outputs(dirname, out, coeffs, stats, rank=0, world=1):
+    """--dump-outputs: the arrays a caller of the timed path receives from its
+    last step, as DIR/<name>.npy (rank r > 0: DIR/<name>.rank<r>.npy):
+      * reconstructed, coefficients: float32 (uint8 / int16 values, exact); an
+        array of more than DUMP_SAMPLE // world elements is sampled at that
+        many flat positions drawn once from a seeded CPU generator (sorted,
+        the same in every run and build), so all ranks together stay at the
+        size of one;
+      * stats: float64, one row per frame, the fields of jds_frame_stats in
+        declaration order (arrays flattened) without DUMP_STATS_SKIP."""
+    import numpy as np
+    import torch
+    from jds import _abi
+    os.makedirs(dirname, exist_ok=True)
+    suffix = ('' if rank == 0 else f'.rank{rank}') + '.npy'
+    for name, t in (('reconstructed', out), ('coefficients', coeffs)):
+        flat = t.reshape(-1)
+        keep = max(1, DUMP_SAMPLE // world)
+        if flat.numel() > keep:
+            g = torch.Generator()
+            g.manual_seed(20240229)
+            idx = torch.randint(0, flat.numel(), (keep,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dirname, name + suffix), flat.cpu().numpy().astype(np.float32))
+    st = stats.cpu().numpy().view(_abi.STATS_DTYPE).reshape(-1)
+    cols = [st[f].astype(np.float64).reshape(len(st), -1) for f in _abi.STATS_DTYPE.names
+            if f not in DUMP_STATS_SKIP]
+    np.save(os.path.join(dirname, 'stats' + suffix), np.concatenate(cols, axis=1))
 
 
 def prewarm(run_step, warmup, dev):
@@ -438,6 +487,19 @@ def sweep_main(args):
                          'items_per_step': items, 'items_per_s': round(items * args.steps / elapsed, 1),
                          'front_end': 'replicated per item' if rep else 'shared per frame (jds_plan_create_q)',
                          'parallelism': f'frame-shard x{world}', **dist_info(world, backend)}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, cf, st, rank, world)
+
+    def finish():
+        plan.close()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
     # the per-item statistics of every rank reach every rank (distributed_sweep's
     # all_gather_object, gui/worker.py:55-74's result list), once, outside the
     # timed region: the record shows the gather ran and what it carried
@@ -495,19 +557,16 @@ def sweep_main(args):
         if rank == 0:
             result['parity'] = rec
             result['parity_ranks'] = pr
-    plan.close()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
-def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block=8, qtable=None, seed=1000):
+def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block=8, qtable=None, seed=1000,
+              dump_dir=None):
     """One measured configuration: B device-resident frames per GPU, W untimed
     warmup steps (continued to PREWARM_S of load), then exactly K timed steps
-    bracketed by barrier + synchronize, max over ranks; then a serial
-    calibration pass timing each phase with HIP events on its launch stream.
+    bracketed by barrier + synchronize, max over ranks; `dump_dir`: the last
+    timed step's outputs go there (dump_outputs).  With --full, K more steps
+    then give the per-kernel launch profile and the roofline object.
     Returns (result dict, state) -- state keeps the plans and buffers for the
     legs that follow (entropy, parity); the caller closes the plans."""
     import torch
@@ -574,17 +633,53 @@ def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block
             plans[0].run(*ptrs(0), xflags, s_f.cuda_stream)
 
     nwarm = prewarm(run_step, args.warmup, dev)
+    k0 = nwarm + (-nwarm) % NS  # the timed steps start on buffer set 0, however many warmup steps ran
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for k in range(args.steps):
-        run_step(nwarm + k)
+        run_step(k0 + k)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if world > 1:
+        elapsed = max_over_ranks(elapsed, dev, backend)
+    if dump_dir:
+        last = (k0 + args.steps - 1) % NS  # the buffer set of the last timed step
+        dump_outputs(dump_dir, outs[last], coefs[last], stats_l[last], rank, world)
+
+    px_per_step = B * H * W
+    value = world * px_per_step * args.steps / elapsed / 1e6
+    S = cpf / (H * W)
+    result = {
+        'metric': metric_name(quality, mode),
+        'value': round(value, 2),
+        'unit': 'Mpixels/s',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'warmup_steps_run': nwarm,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'f32+f64',  # forward: fp32 certified + fp64 fix-up; inverse: fp64 (u8 in/out, int16 coefficients)
+        'data': 'synthetic (uniform random RGB generated on device)',
+        'config': {'workload': f'{W}x{H} RGB, Q={quality}, {mode}, prefilter={"on" if pf else "off"}, '
+                               f'{block}x{block} blocks (' + workload_label(H, W, quality, mode, pf, block) + ')',
+                   'frames_per_gpu_per_step': B, 'global_batch_frames': B * world,
+                   'pipeline': ('image stream: forward of batch k+1 beside the inverse of batch k (two streams, '
+                                'two buffer sets)' if NS > 1 else 'serial forward then inverse per step'),
+                   'parallelism': f'frame-shard x{world}', **dist_info(world, backend)},
+        'pipeline_roofline_frac': round(value / world * 1e6 * (6 + 2 * S) / (HBM_PEAK_GBS * 1e9), 4),
+    }
+    state = {'plans': plans, 'rgb': rgbs[0], 'out': outs[0], 'coeffs': coefs[0], 'stats': stats_l[0], 's_f': s_f,
+             'cpf': cpf, 'qt': qt}
+    if not args.full:
+        return result, state
     # Per-kernel launch durations of the same runs (outside the timed region):
     # K more steps exactly as timed, with the plan marking its stream after
     # every launch (jds_plan_profile); the intervals between marks tile the
@@ -626,12 +721,7 @@ def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block
         t_inv = sum(e[2].elapsed_time(e[3]) for e in evs) / args.steps
         kernels = {'forward phase': {'ms_per_step': t_fwd, 'launches_per_step': 1, 'avg_launch_ms': t_fwd},
                    'inverse phase': {'ms_per_step': t_inv, 'launches_per_step': 1, 'avg_launch_ms': t_inv}}
-    if world > 1:
-        elapsed = max_over_ranks(elapsed, dev, backend)
 
-    px_per_step = B * H * W
-    value = world * px_per_step * args.steps / elapsed / 1e6
-    S = cpf / (H * W)
     bytes_fwd = int(px_per_step * 3 + px_per_step * S * 2)  # one launch processes one batch
     bytes_inv = int(px_per_step * S * 2 + px_per_step * 3)
     # the dominant kernel: the single longest launch of the step, with its own
@@ -687,26 +777,7 @@ def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block
                 'source': vsrc}
     bound = 'valu' if valu and valu['frac'] > achieved / HBM_PEAK_GBS else 'hbm'
 
-    result = {
-        'metric': metric_name(quality, mode),
-        'value': round(value, 2),
-        'unit': 'Mpixels/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'warmup_steps_run': nwarm,
-        'ms_per_step': round(elapsed / args.steps * 1e3, 4),
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'f32+f64',  # forward: fp32 certified + fp64 fix-up; inverse: fp64 (u8 in/out, int16 coefficients)
-        'data': 'synthetic (uniform random RGB generated on device)',
-        'config': {'workload': f'{W}x{H} RGB, Q={quality}, {mode}, prefilter={"on" if pf else "off"}, '
-                               f'{block}x{block} blocks (' + workload_label(H, W, quality, mode, pf, block) + ')',
-                   'frames_per_gpu_per_step': B, 'global_batch_frames': B * world,
-                   'pipeline': ('image stream: forward of batch k+1 beside the inverse of batch k (two streams, '
-                                'two buffer sets)' if NS > 1 else 'serial forward then inverse per step'),
-                   'parallelism': f'frame-shard x{world}', **dist_info(world, backend)},
+    result.update({
         'roofline': {'bound': bound, 'kernel': kname, 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS,
                      'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
                      'traffic_source': traffic_src,
@@ -729,10 +800,7 @@ def run_point(args, dev, world, backend, rank, B, H, W, quality, mode, pf, block
                                       'avg_launch_ms': {k: round(v['avg_launch_ms'], 4) for k, v in kernels.items()},
                                       'phases_ms': {'forward': round(t_fwd, 4), 'inverse': round(t_inv, 4)}},
         'fixups_last_step': {'fwd_blocks': int(plans[0].fix_counts()[0]), 'inv_tiles': int(plans[0].fix_counts()[1])},
-        'pipeline_roofline_frac': round(value / world * 1e6 * (6 + 2 * S) / (HBM_PEAK_GBS * 1e9), 4),
-    }
-    state = {'plans': plans, 'rgb': rgbs[0], 'out': outs[0], 'coeffs': coefs[0], 'stats': stats_l[0], 's_f': s_f,
-             'cpf': cpf, 'qt': qt}
+    })
     return result, state
 
 
@@ -795,14 +863,14 @@ def main():
     # at N > 1, the north star's exchange; outside the timed region)
     qt = broadcast_tables([args.quality])[0]
     result, state = run_point(args, dev, world, backend, rank, B, H, W, args.quality, args.mode, args.prefilter,
-                              args.block, qt)
+                              args.block, qt, dump_dir=args.dump_outputs)
     result['config']['quant_table'] = ('rank 0 -> all ranks, one broadcast of 64 float64 '
                                        f'({"RCCL over xGMI" if backend == "nccl" else backend})' if world > 1
                                        else 'local (one rank)')
     plans, rgb, coeffs, stats, s_f, cpf = (state[k] for k in ('plans', 'rgb', 'coeffs', 'stats', 's_f', 'cpf'))
     px_per_step = B * H * W
 
-    if not args.no_entropy and args.block == 8:
+    if args.full and not args.no_entropy and args.block == 8:
         # JPEG entropy coding of the step's coefficients (jds_entropy.hip), timed on
         # its own after the headline region: files per frame, real bits per pixel
         from jds import entropy
@@ -834,7 +902,7 @@ def main():
             int(st0['nonzero']), float(st0['magnitude_bits']), int(st0['total_coeffs']), (H, W), 8)['bpp'], 4)
         del files
 
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         # PSNR / bytes vs the reference restatement on frame 0 (outside the timed
         # region) -- on every rank, its own frames; rank 0 reports all of them
         par = frame0_parity(state, args.quality, args.mode, args.prefilter, args.block)
@@ -842,7 +910,7 @@ def main():
         if rank == 0:
             result['parity'] = par
             result['parity_ranks'] = pr
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         n = max(1, min(B, 64))
         host = rgb[:n].cpu().numpy()
         result['cpu_baseline'] = cpu_baseline(host, args.quality, args.mode, bool(args.prefilter),
@@ -855,7 +923,7 @@ def main():
 
     default_point = (H, W, args.quality, args.mode, bool(args.prefilter), args.block) == (1080, 1920, 50, '4:2:0',
                                                                                           True, 8)
-    if default_point and not args.no_north_star:
+    if args.full and default_point and not args.no_north_star:
         # the north-star point (BASELINE.json north_star: 4K / Q=50 / 4:2:0), same
         # timing method, same ranks: the driver's default run carries it
         ns = NORTH_STAR
@@ -877,7 +945,7 @@ def main():
         for p_ in st_ns['plans']:
             p_.close()
         del st_ns
-    if rank == 0 and not args.no_host_path and args.block == 8:
+    if args.full and rank == 0 and not args.no_host_path and args.block == 8:
         result['host_path'] = host_path(args.quality, args.mode, args.prefilter)
     if rank == 0:
         print(json.dumps(result), flush=True)

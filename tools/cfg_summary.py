@@ -3,7 +3,7 @@
 
     python tools/cfg_summary.py TAG [PROFILE_NAME] [TRAFFIC_KEY]
 
-Reads gpurun_out/cfg/TAG/{bench.json, stats/run_kernel_stats.csv,
+Reads $JDS_OUT/cfg/TAG (default bench_out/cfg/TAG) /{bench.json, stats/run_kernel_stats.csv,
 fetch/run_counter_collection.csv, write/run_counter_collection.csv} and writes
   profiles/PROFILE_NAME_bench.json         the bench line
   profiles/PROFILE_NAME_kernel_stats.csv   rocprofv3 --stats summary
@@ -27,7 +27,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 name = sys.argv[2] if len(sys.argv) > 2 else tag
-src = os.path.join(ROOT, 'gpurun_out', 'cfg', tag)
+src = os.path.join(ROOT, os.environ.get('JDS_OUT', 'bench_out'), 'cfg', tag)
 prof = os.path.join(ROOT, 'profiles')
 
 bench = json.loads(open(os.path.join(src, 'bench.json')).read().strip().splitlines()[-1])

@@ -1,20 +1,22 @@
 #!/bin/bash
 # PMC counter passes over a short bench run (one rocprofv3 --pmc pass per counter group;
-# kernel-trace only, never combined with sys/runtime traces).  Output: gpurun_out/pmc/<pass>/
+# kernel-trace only, never combined with sys/runtime traces).  Output: $JDS_OUT/pmc/<pass>/
+# (default bench_out/ in the repository root)
 set -u
-cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+cd "$(dirname "$0")/.."
 ROOT=$(pwd)
-mkdir -p gpurun_out/pmc
+OUT=$(realpath -m "${JDS_OUT:-bench_out}")/pmc
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="${BENCH_ARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-north-star --no-parity}"
+ARGS="${BENCH_ARGS:---full --steps 3 --warmup 1 --no-cpu-baseline --no-north-star --no-parity}"
 cd /tmp
-timeout -k 10 120 rocprofv3 -L > "$ROOT/gpurun_out/pmc/counters_list.txt" 2>&1 || true
+timeout -k 10 120 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1 || true
 i=0
 while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $group -d "$ROOT/gpurun_out/pmc/p$i" -o run --output-format csv \
-    -- python3 "$ROOT/bench.py" $ARGS > "$ROOT/gpurun_out/pmc/p$i.log" 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $group -d "$OUT/p$i" -o run --output-format csv \
+    -- python3 "$ROOT/bench.py" $ARGS > "$OUT/p$i.log" 2>&1
   rc=$?; echo "pass $i ($group) rc=$rc"
   case $rc in 0|1) ;; *) exit $rc;; esac
 done <<'GROUPS'
