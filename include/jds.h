@@ -278,6 +278,101 @@ int jds_plan_entropy(jds_plan* plan, const int16_t* coeffs, uint8_t* out, int64_
 int jds_encode_jfif(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W, const int16_t* coeffs, uint8_t* out,
                     int64_t out_cap, int64_t* out_len, uint64_t* scan_bits);
 
+/* Baseline JFIF decoding (DESIGN.md "Entropy decode"): the files this library
+ * writes -- and any baseline file of the same profile -- back to
+ * all_quantized_coeffs (reference layout) and on to the RGB image.
+ *
+ * Profile: SOF0, 8-bit, components 1, 2, 3, Y sampled 1x1 / 2x1 / 2x2 with 1x1
+ * chroma, one quantisation table, three non-interleaved scans in any order,
+ * Huffman tables from the file's DHT segments, no DRI; APPn / COM are skipped.
+ * Anything else in a well-formed file is JDS_ENOTSUP (the message names the
+ * feature), malformed bytes are JDS_EINVAL; sizes whose T.81 chroma block grid
+ * differs from the reference's floor-sized planes are JDS_ENOTSUP as for the
+ * encoder.
+ *
+ * The entropy decode is self-synchronising: every scan is cut into
+ * subsequences of a fixed number of bits, one GPU lane decodes each from a
+ * guessed state, and exit states are handed to the next subsequence until none
+ * changes -- inside a workgroup in one launch, across workgroups between
+ * launches (the host reads a counter after each round).  A frame's status
+ * word is 0 or a combination of JDS_DEC_* bits. */
+#define JDS_DEC_HEADER   1u  /* plan path: header differs from the plan's, or lengths[i] == 0 */
+#define JDS_DEC_CODE     2u  /* invalid Huffman code (or a size outside baseline) */
+#define JDS_DEC_K63      4u  /* a run past coefficient 63 */
+#define JDS_DEC_OVERRUN  8u  /* the scan data end inside a symbol */
+#define JDS_DEC_COUNT    16u /* the scan holds fewer or more blocks than the frame needs */
+#define JDS_DEC_DC_RANGE 32u /* a DC value (sum of the differences) outside int16 */
+
+typedef struct {
+  int32_t component;          /* 1 Y, 2 Cb, 3 Cr */
+  int32_t dc_table, ac_table; /* Huffman table ids (0 / 1) */
+  int32_t reserved;
+  int64_t offset, length;     /* the entropy-coded segment: stuffed bytes up to the next marker */
+} jds_jfif_scan;
+
+typedef struct {
+  uint8_t bits[16];  /* BITS: codes per length 1..16 */
+  uint8_t vals[256]; /* HUFFVAL */
+  int32_t n_vals;
+  int32_t defined;
+} jds_jfif_huff;
+
+typedef struct {
+  int64_t H, W;
+  int32_t subsampling;      /* JDS_SS_* */
+  int32_t n_scans;          /* 3 */
+  double qtable[64];        /* row-major (de-zigzagged), as jds_params.qtable */
+  jds_jfif_scan scan[3];    /* in file order */
+  jds_jfif_huff huff[4];    /* [0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1, from the file's DHT segments */
+  int64_t y_blocks, c_blocks; /* blocks of the Y scan / of each chroma scan */
+  int64_t coeffs_needed;    /* int16 entries of the coefficient buffer: 64 * (y_blocks + 2 * c_blocks) */
+  uint32_t status;          /* jds_decode_jfif / jds_decompress_jfif: the frame's JDS_DEC_* bits */
+  uint32_t rounds;          /* the same calls: inter-workgroup propagation rounds */
+} jds_jfif_info;
+
+/* Host only, no device access (like jds_geometry_of); never reads outside [data, data + len). */
+int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out);
+/* One file from host memory to host coefficients (synchronous).  *info is
+ * filled even when coeffs_cap (int16 entries) is too small (then JDS_EINVAL;
+ * info->coeffs_needed holds the need).  A non-zero frame status is JDS_EINVAL
+ * with a message naming the defect. */
+int jds_decode_jfif(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jfif_info* info);
+/* Decode, then the plan's default inverse for the file's geometry and table
+ * (an inverse-only jds_plan_run on zeroed statistics): rgb_out (H*W*3 bytes,
+ * rgb_cap >= that) is this codec's reconstruction of the coefficients, the
+ * bytes jds_compress_reconstruct returned as rgb_out for the frame that made
+ * the file.  coeffs: NULL, or info->coeffs_needed int16 entries (see
+ * jds_jfif_parse). */
+int jds_decompress_jfif(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jfif_info* info);
+/* Device-resident batch decode, the mirror of jds_plan_entropy: frame i's file
+ * at files + i*stride with lengths[i] bytes (u64, device), its coefficients to
+ * coeffs + i*coeffs_per_frame, its status word to status[i] (u32, device).
+ * Each header is compared on the device with the one the plan writes; a
+ * mismatch or lengths[i] == 0 sets JDS_DEC_HEADER and skips the frame (its
+ * coefficients are zero).  Scan offsets come from a marker search on the
+ * device; all frames and scans decode in the same launches.  NOT asynchronous:
+ * the call waits for `stream` after the header pass and after every
+ * propagation round, and returns with the coefficients queued on `stream`.  A
+ * following jds_plan_run(.., JDS_RUN_INV) reconstructs; on a plan that never
+ * ran its forward, give it zeroed stats: afterwards they hold total_coeffs,
+ * block_overhead_bits and pixels, everything else as given. */
+int jds_plan_entropy_decode(jds_plan* plan, const uint8_t* files, int64_t stride, const uint64_t* lengths,
+                            int16_t* coeffs, uint32_t* status, void* stream);
+/* The decoder's compile-time constants: bits per subsequence, subsequences per workgroup. */
+int jds_entropy_decode_info(int32_t* subseq_bits, int32_t* subseq_per_group);
+/* Inter-workgroup propagation rounds (launches of the synchronisation kernel) the plan's last decode took. */
+int jds_plan_entropy_decode_rounds(const jds_plan* plan, uint32_t* rounds);
+
+/* Test-only: the whole decode on the host with the kernels' shared core
+ * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
+ * >= 64), a host loop standing in for the lanes under the same propagation
+ * rule.  coeffs: coeffs_cap int16 entries; rounds_out[3]: decode rounds of the
+ * Y, Cb, Cr scans.  No GPU. */
+int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out);
+
 /* Test-only: evaluate the device DCT expressions (jds_dct8.hpp) on the host so
  * the CPU test suite can pin them against SciPy without a GPU.  Not used by
  * any product path.  in/out: n blocks of 8x8 f64; inverse: 0 = dctn, 1 = idctn. */

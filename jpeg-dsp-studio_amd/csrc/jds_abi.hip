@@ -17,6 +17,7 @@
 
 #include "jds_dct16.hpp"
 #include "jds_dct8.hpp"
+#include "jds_huffdec.hpp"
 #include "jds_internal.hpp"
 
 #ifdef JDS_INV6
@@ -85,6 +86,15 @@ void ent_sizes(const Geo& g, int n, size_t* sz);
 hipError_t launch_entropy(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
                           const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                           unsigned long long* scan_bits, hipStream_t s);
+void dec_constants(int* s, int* g);
+long long dec_layout(DecScan* sc, int nscans, int* max_ngrp);
+size_t dec_scratch_bytes(long long ngroups, int nscans);
+size_t dec_hdr_bytes(int n);
+hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned long long* lengths,
+                          const uint8_t* hdr_dev, int hl, int n, void* work, uint32_t* status, hipStream_t s);
+hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
+                   const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
+                   hipStream_t s, unsigned* rounds, int* too_many);
 hipError_t launch_codec16(int mode, bool pf, const Geo& g, int n, const uint8_t* rgb, uint8_t* rgb_out,
                           int16_t* coeffs, const FrameQ* fq, const double* gk, jds_frame_stats* st, double* part,
                           double* planes, bool want_sse, double* err_y, double* err_rgb, hipStream_t s,
@@ -162,6 +172,7 @@ struct jds_ctx {
   DevBuf chunks;
   DevBuf planes;  // 16x16 path: reconstructed chroma planes
   DevBuf ent[8], ent_hdr, ent_tab, ent_cf, ent_out, ent_meta;  // entropy coder (jds_encode_jfif)
+  DevBuf dec_file, dec_tab, dec_scr, dec_st;  // entropy decoder (jds_decode_jfif): file, tables, scratch, status
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   size_t ss_budget = 0;  // SSIM scratch budget per launch group (0: SSIM_SCRATCH; jds_ctx_set_ssim_scratch)
 };
@@ -304,6 +315,8 @@ struct jds_plan {
   DevBuf planes;  // 16x16 path: reconstructed chroma planes (n x 2 x hc x wc f64)
   double* qt = nullptr;  // host copy of the per-frame 8x8 tables (entropy headers)
   DevBuf ent[8], ent_hdr, ent_tab;  // entropy coder scratch, allocated by the first jds_plan_entropy
+  DevBuf dec_tab, dec_scr, dec_info;  // entropy decoder (jds_plan_entropy_decode): tables, scratch, scan ranges
+  unsigned dec_rounds = 0;            // propagation rounds of the last decode
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   GenBufs gen() const { return {(const AreaTap*)gen_tab.p, (double*)gen_sub.p, (double*)gen_rec.p}; }
   // jds_plan_profile: the launch marks of profiled runs (event pool + names)
@@ -573,6 +586,10 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->ent_cf.release();
   c->ent_out.release();
   c->ent_meta.release();
+  c->dec_file.release();
+  c->dec_tab.release();
+  c->dec_scr.release();
+  c->dec_st.release();
   c->gen_tab.release();
   c->gen_sub.release();
   c->gen_rec.release();
@@ -973,6 +990,9 @@ void jds_plan_destroy(jds_plan* p) {
   for (DevBuf& b : p->ent) b.release();
   p->ent_hdr.release();
   p->ent_tab.release();
+  p->dec_tab.release();
+  p->dec_scr.release();
+  p->dec_info.release();
   free(p->qt);
   marks_release(p->marks);
   delete p;
@@ -1480,6 +1500,213 @@ int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, con
     for (int i = 0; i < 3; ++i) scan_bits[i] = m[1 + i];
   if ((long long)m[0] > out_cap) return fail(JDS_EINVAL, "output buffer too small: %llu bytes needed", m[0]);
   HIP_TRY(hipMemcpy(out, c->ent_out.p, (size_t)m[0], hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+// ------------------------------------------------------ entropy decoding --
+
+int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out) {
+  const int rc = hd_parse(data, len, out, false, g_err, sizeof g_err);
+  if (rc) return rc;
+  if (out->H * out->W > (int64_t)1 << 28)
+    return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
+  return JDS_OK;
+}
+
+int jds_entropy_decode_info(int32_t* subseq_bits, int32_t* subseq_per_group) {
+  if (!subseq_bits || !subseq_per_group) return fail(JDS_EINVAL, "null argument");
+  int s, g;
+  dec_constants(&s, &g);
+  *subseq_bits = s;
+  *subseq_per_group = g;
+  return JDS_OK;
+}
+
+int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  jds_jfif_info info;
+  const int rc = jds_jfif_parse(data, len, &info);
+  if (rc) return rc;
+  if (coeffs_cap < info.coeffs_needed)
+    return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)info.coeffs_needed);
+  rounds_out[0] = rounds_out[1] = rounds_out[2] = 0;
+  const uint32_t st = hd_host_decode(data, &info, subseq_bits, coeffs, rounds_out);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+// Upload one parsed file and decode it into c->ent_cf (device coefficients).
+static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfif_info* info) {
+  hipStream_t s = c->stream;
+  HuffDecTab tabs[4];
+  for (int i = 0; i < 4; ++i) {
+    memset(&tabs[i], 0, sizeof tabs[i]);
+    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0)
+      return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
+  }
+  DecScan sc[3];
+  for (int i = 0; i < 3; ++i) {
+    const jds_jfif_scan& f = info->scan[i];
+    const int comp = f.component - 1;
+    if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
+    sc[i] = DecScan{};
+    sc[i].data_off = f.offset;
+    sc[i].nbytes = f.length;
+    sc[i].coef_off = comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks);
+    sc[i].nblocks = (int)(comp ? info->c_blocks : info->y_blocks);
+    sc[i].frame = 0;
+    sc[i].dc_tab = f.dc_table;
+    sc[i].ac_tab = 2 + f.ac_table;
+  }
+  int max_ngrp = 0;
+  const long long ng = dec_layout(sc, 3, &max_ngrp);
+  if (ng < 0) return fail(JDS_ENOTSUP, "scan too long");
+  HIP_TRY(c->dec_file.ensure((size_t)len));
+  HIP_TRY(c->dec_tab.ensure(sizeof tabs));
+  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, 3)));
+  HIP_TRY(c->dec_st.ensure(16));
+  HIP_TRY(c->ent_cf.ensure((size_t)info->coeffs_needed * sizeof(int16_t)));
+  HIP_TRY(hipMemcpyAsync(c->dec_file.p, data, (size_t)len, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(c->dec_st.p, 0, 16, s));
+  HIP_TRY(hipStreamSynchronize(s));  // tabs is a stack array
+  unsigned rounds = 0;
+  int too_many = 0;
+  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc, 3, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p, c->dec_scr.p,
+                  (int16_t*)c->ent_cf.p, info->coeffs_needed, (uint32_t*)c->dec_st.p, s, &rounds, &too_many));
+  if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  info->status = st;
+  info->rounds = rounds;
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+int jds_decode_jfif(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jfif_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jfif_parse(data, len, info);
+  if (rc) return rc;
+  if (!coeffs || coeffs_cap < info->coeffs_needed)
+    return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)info->coeffs_needed);
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_file_dev(c, data, len, info))) return rc;
+  HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jfif_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jfif_parse(data, len, info);
+  if (rc) return rc;
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  jds_params prm;
+  memset(&prm, 0, sizeof prm);
+  prm.block_size = 8;
+  prm.quality = 0;
+  prm.subsampling = info->subsampling;
+  memcpy(prm.qtable, info->qtable, sizeof prm.qtable);
+  if ((rc = check_tables(&prm))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_file_dev(c, data, len, info))) return rc;
+  // the plan's default inverse route for this geometry and table, on zeroed statistics
+  jds_plan* plan = nullptr;
+  if ((rc = jds_plan_create(c, &prm, 1, info->H, info->W, &plan))) return rc;
+  hipError_t e;
+  if ((e = c->rgb.ensure(nimg)) != hipSuccess || (e = c->out.ensure(nimg)) != hipSuccess ||
+      (e = c->stats.ensure(sizeof(jds_frame_stats))) != hipSuccess ||
+      (e = hipMemsetAsync(c->stats.p, 0, sizeof(jds_frame_stats), c->stream)) != hipSuccess) {
+    jds_plan_destroy(plan);
+    return fail(e == hipErrorOutOfMemory ? JDS_ENOMEM : JDS_EHIP, "decompress: %s", hipGetErrorString(e));
+  }
+  rc = jds_plan_run(plan, (const uint8_t*)c->rgb.p, (uint8_t*)c->out.p, (int16_t*)c->ent_cf.p,
+                    (jds_frame_stats*)c->stats.p, JDS_RUN_INV, c->stream);
+  if (rc == JDS_OK) {
+    e = hipMemcpyAsync(rgb_out, c->out.p, nimg, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && coeffs)
+      e = hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
+                         c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) rc = fail(JDS_EHIP, "decompress: %s", hipGetErrorString(e));
+  }
+  jds_plan_destroy(plan);  // (waits for the context's stream)
+  return rc;
+}
+
+int jds_plan_entropy_decode(jds_plan* p, const uint8_t* files, int64_t stride, const uint64_t* lengths,
+                            int16_t* coeffs, uint32_t* status, void* stream) {
+  if (!p || !files || !lengths || !coeffs || !status) return fail(JDS_EINVAL, "null argument");
+  if (stride < 1) return fail(JDS_EINVAL, "stride %lld", (long long)stride);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!p->ent_hdr.p) {
+    int rc = ent_prepare(p->g, p->mode, p->n, p->qt, p->ent, p->ent_hdr, p->ent_tab, s);
+    if (rc) return rc;
+  }
+  const MarkScope marks_(p, s);
+  size_t sz[8];
+  ent_sizes(p->g, p->n, sz);
+  const int hl = (int)(sz[6] / (size_t)p->n);
+  if (!p->dec_tab.p) {
+    // the decode tables come from the DHT segments of the plan's own header
+    std::vector<uint8_t> h((size_t)hl);
+    jds_jfif_info hi;
+    if (ent_header(p->qt, p->mode, p->g.H, p->g.W, h.data()) != hl ||
+        hd_parse(h.data(), hl, &hi, true, g_err, sizeof g_err) != JDS_OK)
+      return fail(JDS_EINVAL, "entropy decode: the plan's header template does not parse");
+    HuffDecTab tabs[4];
+    for (int i = 0; i < 4; ++i)
+      if (!hi.huff[i].defined || hd_build(hi.huff[i].bits, hi.huff[i].vals, &tabs[i]) < 0)
+        return fail(JDS_EINVAL, "entropy decode: the plan's header template lacks a Huffman table");
+    HIP_TRY(p->dec_tab.ensure(sizeof tabs));
+    HIP_TRY(hipMemcpy(p->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice));
+  }
+  const int n = p->n;
+  if (n > 65535) return fail(JDS_ENOTSUP, "entropy decode: at most 65535 frames per call");
+  HIP_TRY(p->dec_info.ensure(dec_hdr_bytes(n)));
+  HIP_TRY(launch_dec_hdr(files, stride, (const unsigned long long*)lengths, (const uint8_t*)p->ent_hdr.p, hl, n,
+                         p->dec_info.p, status, s));
+  std::vector<long long> si(6 * (size_t)n);
+  std::vector<uint32_t> st((size_t)n);
+  HIP_TRY(hipMemcpyAsync(si.data(), p->dec_info.p, sizeof(long long) * si.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(st.data(), status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const long long nyb = (long long)p->g.nby * p->g.nbx, ncb = (long long)p->g.ncy * p->g.ncx;
+  std::vector<DecScan> sc(3 * (size_t)n);
+  for (int f = 0; f < n; ++f)
+    for (int k = 0; k < 3; ++k) {
+      DecScan& d = sc[3 * (size_t)f + k];
+      d = DecScan{};
+      d.frame = f;
+      d.dc_tab = k ? 1 : 0;
+      d.ac_tab = k ? 3 : 2;
+      d.coef_off = (long long)f * p->g.cpf + (k == 0 ? 0 : (k == 1 ? p->g.off_cb : p->g.off_cr));
+      if (st[f]) continue;  // skipped frame: no workgroups
+      d.data_off = (long long)f * stride + si[6 * (size_t)f + 2 * k];
+      d.nbytes = si[6 * (size_t)f + 2 * k + 1];
+      d.nblocks = (int)(k ? ncb : nyb);
+    }
+  int max_ngrp = 0;
+  const long long ng = dec_layout(sc.data(), 3 * n, &max_ngrp);
+  if (ng < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
+  HIP_TRY(p->dec_scr.ensure(dec_scratch_bytes(ng, 3 * n)));
+  int too_many = 0;
+  p->dec_rounds = 0;
+  HIP_TRY(dec_run(files, sc.data(), 3 * n, ng, max_ngrp, (const HuffDecTab*)p->dec_tab.p, p->dec_scr.p, coeffs,
+                  (long long)n * p->g.cpf, status, s, &p->dec_rounds, &too_many));
+  if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  return JDS_OK;
+}
+
+int jds_plan_entropy_decode_rounds(const jds_plan* p, uint32_t* rounds) {
+  if (!p || !rounds) return fail(JDS_EINVAL, "null argument");
+  *rounds = p->dec_rounds;
   return JDS_OK;
 }
 

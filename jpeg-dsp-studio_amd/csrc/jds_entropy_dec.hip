@@ -1,0 +1,534 @@
+// jds_entropy_dec.hip — baseline JPEG entropy DECODING: the scans of the JFIF
+// files jds_entropy.hip writes (or any baseline file of that profile) back to
+// all_quantized_coeffs.  A Huffman stream without restart markers has no known
+// codeword boundaries, so the decode is self-synchronising (Weissenberger &
+// Schmidt, "Massively Parallel Huffman Decoding on GPUs", and its JPEG
+// follow-up): every scan is cut into subsequences of DEC_S bits, one lane
+// decodes each from the guess (first bit, DC expected), exit states are handed
+// to the next subsequence, and lanes whose entry changed decode again until
+// none changes.  The per-subsequence routine is csrc/jds_huffdec.hpp, shared
+// with the host model.
+//
+//   k_dec_find   plan path: marker search over every frame's file.
+//   k_dec_hdr    plan path, one workgroup per frame: header == the plan's own
+//                header template; the marker list -> the three scans' byte ranges.
+//   k_dec_sync   one workgroup per DEC_G subsequences of one scan, their bytes
+//                staged in LDS: decode, then propagate inside the workgroup
+//                through LDS until its entries settle.  Across workgroups the hand-off happens
+//                BETWEEN launches: a workgroup's last exit state goes to a
+//                double-buffered array the next launch reads; no kernel waits
+//                on another workgroup.  The host reads a "changed" counter
+//                after each launch and stops at zero (at most one launch per
+//                workgroup of the longest scan).
+//   k_dec_prefix per scan: exclusive prefix of the subsequences' block counts.
+//   k_dec_write  every lane decodes again from its settled entry and stores the
+//                coefficients de-zigzagged (per coefficient: a block that spans
+//                subsequences is written by several lanes); judges the scan.
+//   k_dec_dc     per scan: the DC differences -> values (inclusive sum, judged
+//                against int16).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "jds_huffdec.hpp"
+#include "jds_internal.hpp"
+
+namespace jds {
+
+#ifndef JDS_DEC_S
+#define JDS_DEC_S 1024  // A/B builds: tools/build_variant.py
+#endif
+#ifndef JDS_DEC_G
+#define JDS_DEC_G 256
+#endif
+constexpr int DEC_S = JDS_DEC_S;  // bits per subsequence
+constexpr int DEC_G = JDS_DEC_G;  // subsequences (lanes) per workgroup
+static_assert(DEC_S % 8 == 0 && DEC_S >= 64, "a symbol (<= 27 bits + 4 stuffed bytes) ends inside the next subsequence");
+
+void dec_constants(int* s, int* g) {
+  *s = DEC_S;
+  *g = DEC_G;
+}
+
+// Fills nsub / grp0 / ngrp; returns the number of workgroups, *max_ngrp the
+// longest scan's.  nblocks == 0 marks a skipped scan (no workgroups).
+long long dec_layout(DecScan* sc, int nscans, int* max_ngrp) {
+  long long g = 0;
+  int mx = 0;
+  for (int i = 0; i < nscans; ++i) {
+    const long long nbits = sc[i].nbytes * 8;
+    long long nsub = sc[i].nblocks ? (nbits + DEC_S - 1) / DEC_S : 0;
+    if (sc[i].nblocks && nsub == 0) nsub = 1;  // an empty scan still gets judged
+    if (nsub > 0x7fffffffll || g > 0x7fffffffll) return -1;
+    sc[i].nsub = (int)nsub;
+    sc[i].grp0 = (int)g;
+    sc[i].ngrp = (int)((nsub + DEC_G - 1) / DEC_G);
+    g += sc[i].ngrp;
+    mx = sc[i].ngrp > mx ? sc[i].ngrp : mx;
+  }
+  *max_ngrp = mx;
+  return g;
+}
+
+// scratch layout (bytes, 8-aligned parts): entry, exit (u64 per slot), the two
+// hand-off buffers (u64 per workgroup), blocks / first block (u32 per slot),
+// scans, workgroup -> scan, counters
+struct DecScratch {
+  unsigned long long *entry, *exitv, *gx[2];
+  unsigned *nblk, *blk0;
+  DecScan* scans;
+  int* grp_scan;
+  unsigned* changed;
+  size_t bytes;
+};
+
+static size_t up8(size_t v) { return (v + 7) & ~(size_t)7; }
+
+DecScratch dec_scratch(void* base, long long ngroups, int nscans) {
+  DecScratch s{};
+  const size_t slots = (size_t)ngroups * DEC_G;
+  char* p = (char*)base;
+  size_t o = 0;
+  s.entry = (unsigned long long*)(p + o); o += 8 * slots;
+  s.exitv = (unsigned long long*)(p + o); o += 8 * slots;
+  s.gx[0] = (unsigned long long*)(p + o); o += 8 * (size_t)(ngroups + 1);
+  s.gx[1] = (unsigned long long*)(p + o); o += 8 * (size_t)(ngroups + 1);
+  s.nblk = (unsigned*)(p + o); o += up8(4 * slots);
+  s.blk0 = (unsigned*)(p + o); o += up8(4 * slots);
+  s.scans = (DecScan*)(p + o); o += up8(sizeof(DecScan) * (size_t)nscans);
+  s.grp_scan = (int*)(p + o); o += up8(4 * (size_t)(ngroups + 1));
+  s.changed = (unsigned*)(p + o); o += 16;
+  s.bytes = o;
+  return s;
+}
+
+size_t dec_scratch_bytes(long long ngroups, int nscans) { return dec_scratch(nullptr, ngroups, nscans).bytes; }
+
+// ------------------------------------------------------------ kernels --
+
+constexpr int DEC_SOS = 10;
+
+// Marker search of the plan path: 0xFF followed by anything but the stuffed
+// 0x00, from the header's end on (scan data hold no other 0xFF pairs, so a
+// well-formed file has exactly four: three SOS and EOI).  Grid (pieces, frames):
+// a thread scans DEC_FIND_B bytes in 16-byte pieces aligned in memory (whole
+// pieces inside [hl, len) as one load, ragged ends by bytes, nothing outside the
+// file) and appends what it finds to the frame's list (cnt[f], pos[8 f ..]).
+constexpr int DEC_FIND_B = 64;
+
+__global__ void __launch_bounds__(256) k_dec_find(const uint8_t* __restrict__ files, long long stride,
+                                                  const unsigned long long* __restrict__ lengths, int hl,
+                                                  int* __restrict__ cnt, long long* __restrict__ pos) {
+  const int f = blockIdx.y;
+  const unsigned long long len64 = lengths[f];
+  if (len64 < (unsigned long long)(hl + 3 * DEC_SOS + 2) || len64 > (unsigned long long)stride) return;
+  const long long len = (long long)len64;
+  const uint8_t* d = files + (long long)f * stride;
+  const long long a0 = hl - (long long)((uintptr_t)(d + hl) & 15u);  // frame-relative start of the piece holding byte hl
+  const long long base = a0 + ((long long)blockIdx.x * 256 + threadIdx.x) * DEC_FIND_B;
+  for (int c = 0; c < DEC_FIND_B / 16; ++c) {
+    const long long g = base + 16 * c;
+    if (g + 1 >= len) return;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (g >= hl && g + 16 <= len) {
+      const uint4 v = *reinterpret_cast<const uint4*>(d + g);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (g + j >= hl && g + j < len) w[j >> 2] |= (uint32_t)d[g + j] << (8 * (j & 3));
+    }
+    bool ff = false;  // some byte is 0xFF: a zero byte of ~w
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t x = ~w[k];
+      ff = ff || (((x - 0x01010101u) & ~x & 0x80808080u) != 0u);
+    }
+    if (!ff) continue;
+    const uint32_t nx = g + 16 < len ? (uint32_t)d[g + 16] : 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t bj = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+      const uint32_t bn = j < 15 ? (w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu : nx;
+      if (bj == 0xFFu && bn != 0u && g + j >= hl && g + j + 1 < len) {
+        const int k = atomicAdd(&cnt[f], 1);
+        if (k < 8) pos[8 * (long long)f + k] = g + j;
+      }
+    }
+  }
+}
+
+// Header check of one frame (plan path) and its scans' byte ranges from the
+// marker list.  scaninfo[6 f ..]: (offset, length) of the Y, Cb, Cr scans
+// within the frame's file.
+__global__ void __launch_bounds__(256) k_dec_hdr(const uint8_t* __restrict__ files, long long stride,
+                                                 const unsigned long long* __restrict__ lengths,
+                                                 const uint8_t* __restrict__ hdr, int hl,
+                                                 const int* __restrict__ cnt, const long long* __restrict__ mpos,
+                                                 long long* __restrict__ scaninfo, uint32_t* __restrict__ status) {
+  const int f = blockIdx.x, t = threadIdx.x;
+  const unsigned long long len64 = lengths[f];
+  const uint8_t* d = files + (long long)f * stride;
+  if (len64 < (unsigned long long)(hl + 3 * DEC_SOS + 2) || len64 > (unsigned long long)stride) {  // (uniform)
+    if (t == 0) status[f] = HD_BAD_HEADER;
+    return;
+  }
+  const long long len = (long long)len64;
+  int bad = 0;
+  for (int i = t; i < hl; i += 256) bad |= d[i] != hdr[(long long)f * hl + i];
+  bad = __syncthreads_or(bad);
+  if (t != 0) return;
+  long long pos[4] = {0, 0, 0, 0};
+  if (cnt[f] != 4) {
+    bad = 1;
+  } else {
+    for (int i = 0; i < 4; ++i) pos[i] = mpos[8 * (long long)f + i];
+    for (int i = 0; i < 4; ++i)  // (four entries)
+      for (int j = i + 1; j < 4; ++j)
+        if (pos[j] < pos[i]) {
+          const long long x = pos[i];
+          pos[i] = pos[j];
+          pos[j] = x;
+        }
+    bad |= pos[0] != hl || pos[3] != len - 2 || d[len - 1] != 0xD9;
+    for (int s2 = 0; s2 < 3 && !bad; ++s2) {
+      const uint8_t sos[DEC_SOS] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)(s2 + 1), (uint8_t)(s2 == 0 ? 0x00 : 0x11),
+                                    0x00, 0x3F, 0x00};
+      if (pos[s2] + DEC_SOS > pos[s2 + 1]) {
+        bad = 1;
+        break;
+      }
+      for (int i = 0; i < DEC_SOS; ++i) bad |= d[pos[s2] + i] != sos[i];
+    }
+  }
+  for (int s2 = 0; s2 < 3; ++s2) {
+    scaninfo[6 * f + 2 * s2] = bad ? 0 : pos[s2] + DEC_SOS;
+    scaninfo[6 * f + 2 * s2 + 1] = bad ? 0 : pos[s2 + 1] - (pos[s2] + DEC_SOS);
+  }
+  status[f] = bad ? HD_BAD_HEADER : 0u;
+}
+
+// A workgroup's part of its scan in LDS: the bytes of its DEC_G subsequences
+// and DEC_TAIL more (a symbol that starts in the last subsequence reads up to
+// ten bytes from its first one).  Staged with coalesced dword loads -- whole
+// dwords inside the scan, single bytes at its ragged ends, nothing outside it
+// -- from the dword-aligned address at or below the first byte, so LDS dword t
+// is global dword t.  Each lane's 128-byte row is padded by one dword: rows
+// start 33 dwords apart and the lanes of a wave, all reading at about the same
+// offset into their own rows, fall on distinct banks (unpadded, every lane of
+// a wave hits the same bank).
+constexpr int DEC_TAIL = 16;
+constexpr int DEC_ROW = DEC_S / 32;                              // dwords per subsequence
+constexpr int DEC_WIN = DEC_G * DEC_ROW + DEC_TAIL / 4 + 1;      // dwords staged (+1: the alignment shift)
+constexpr int DEC_LDS = DEC_WIN + DEC_WIN / DEC_ROW + 1;         // with the row padding
+static_assert(DEC_S % 32 == 0, "rows of whole dwords");
+
+__device__ __forceinline__ int dec_lds_idx(int q) { return q + q / DEC_ROW; }
+
+struct DecLdsSrc {
+  const uint32_t* lds;
+  const uint8_t* d;  // the scan's bytes (global)
+  int64_t n;
+  int64_t o0;        // scan-relative byte of LDS dword 0 (may be negative: the alignment shift)
+  __device__ __forceinline__ uint32_t byte(int64_t i) const { return d[i]; }
+  __device__ __forceinline__ void bytes10(int64_t b, uint64_t& lo, uint64_t& hi) const {
+    const int64_t o = b - o0;
+    if (o >= 0 && o + 16 <= 4 * (int64_t)DEC_WIN) {
+      const int q = (int)(o >> 2), sh = 8 * (int)(o & 3);
+      const uint64_t w0 = lds[dec_lds_idx(q)], w1 = lds[dec_lds_idx(q + 1)], w2 = lds[dec_lds_idx(q + 2)],
+                     w3 = lds[dec_lds_idx(q + 3)];
+      const uint64_t a = w0 | (w1 << 32), c = w2 | (w3 << 32);
+      lo = sh ? (a >> sh) | (c << (64 - sh)) : a;
+      hi = c >> sh;
+    } else {  // outside the staged window (a hand-off far past this workgroup's bytes): global bytes
+      lo = 0;
+      hi = 0;
+      for (int j = 0; j < 8; ++j)
+        if (b + j < n) lo |= (uint64_t)d[b + j] << (8 * j);
+      for (int j = 0; j < 2; ++j)
+        if (b + 8 + j < n) hi |= (uint64_t)d[b + 8 + j] << (8 * j);
+    }
+  }
+};
+
+// Stage the workgroup's window (every thread of the workgroup; barrier after).
+__device__ __forceinline__ DecLdsSrc dec_stage(uint32_t* s_win, const uint8_t* d, int64_t n, int64_t first_byte) {
+  const int mis = (int)((uintptr_t)(d + first_byte) & 3u);
+  const int64_t o0 = first_byte - mis;
+  for (int t = threadIdx.x; t < DEC_WIN; t += DEC_G) {
+    const int64_t g = o0 + 4 * (int64_t)t;
+    uint32_t v = 0;
+    if (g >= 0 && g + 4 <= n) {
+      v = *reinterpret_cast<const uint32_t*>(d + g);
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (g + j >= 0 && g + j < n) v |= (uint32_t)d[g + j] << (8 * j);
+    }
+    s_win[dec_lds_idx(t)] = v;
+  }
+  return DecLdsSrc{s_win, d, n, o0};
+}
+
+// the scan's two decode tables -> LDS (words; every thread of the workgroup)
+__device__ __forceinline__ void load_tabs(HuffDecTab* s_tab, const HuffDecTab* __restrict__ tabs, int dc, int ac) {
+  static_assert(sizeof(HuffDecTab) % 4 == 0, "word copy");
+  constexpr int NW = (int)(sizeof(HuffDecTab) / 4);
+  const uint32_t* a = reinterpret_cast<const uint32_t*>(tabs + dc);
+  const uint32_t* b = reinterpret_cast<const uint32_t*>(tabs + ac);
+  uint32_t* o = reinterpret_cast<uint32_t*>(s_tab);
+  for (int i = threadIdx.x; i < NW; i += DEC_G) {
+    o[i] = a[i];
+    o[NW + i] = b[i];
+  }
+}
+
+__global__ void __launch_bounds__(DEC_G) k_dec_sync(const uint8_t* __restrict__ files,
+                                                    const DecScan* __restrict__ scans,
+                                                    const int* __restrict__ grp_scan,
+                                                    const HuffDecTab* __restrict__ tabs,
+                                                    unsigned long long* __restrict__ entry,
+                                                    unsigned long long* __restrict__ exitv,
+                                                    unsigned* __restrict__ nblk,
+                                                    const unsigned long long* __restrict__ gx_in,
+                                                    unsigned long long* __restrict__ gx_out,
+                                                    unsigned* __restrict__ changed, const int round) {
+  __shared__ HuffDecTab s_tab[2];
+  __shared__ uint32_t s_win[DEC_LDS];
+  __shared__ unsigned long long s_exit[DEC_G];
+  __shared__ int s_go;
+  const int g = blockIdx.x, t = threadIdx.x;
+  const DecScan sc = scans[grp_scan[g]];
+  const int gl = g - sc.grp0;
+  const long long i = (long long)gl * DEC_G + t;  // subsequence within the scan
+  const size_t slot = (size_t)g * DEC_G + t;
+  const bool live = i < sc.nsub;
+  const uint8_t* d = files + sc.data_off;
+  const long long n = sc.nbytes;
+  unsigned long long ent, ex = HD_NONE;
+  unsigned nb = 0;
+  bool need;
+  if (round == 0) {
+    ent = live ? (i == 0 ? 0ull : hd_guess(HdMemSrc{d, n}, i * DEC_S)) : HD_NONE;
+    need = live;
+  } else {
+    // only a changed hand-off from the previous workgroup of the scan restarts this one
+    ent = entry[slot];
+    ex = exitv[slot];
+    nb = nblk[slot];
+    need = false;
+    if (t == 0) {
+      if (gl > 0) {
+        const unsigned long long c = gx_in[g - 1];
+        if (c != HD_NONE && c != ent) {
+          ent = c;
+          need = true;
+        }
+      }
+      s_go = need;
+    }
+    __syncthreads();
+    if (!s_go) {  // (uniform)
+      if (t == 0) gx_out[g] = gx_in[g];
+      return;
+    }
+  }
+  load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
+  const DecLdsSrc src = dec_stage(s_win, d, n, (long long)gl * DEC_G * (DEC_S / 8));
+  __syncthreads();
+  // entries 0..r of the workgroup are settled after iteration r: at most DEC_G iterations
+  for (int it = 0; it <= DEC_G; ++it) {
+    if (need) ex = hd_sync_lane(src, &s_tab[0], &s_tab[1], ent, (unsigned long long)(i + 1) * DEC_S, nb);
+    s_exit[t] = ex;
+    __syncthreads();
+    need = false;
+    if (live && t > 0) {
+      const unsigned long long c = s_exit[t - 1];
+      if (c != HD_NONE && c != ent) {
+        ent = c;
+        need = true;
+      }
+    }
+    if (!__syncthreads_or(need)) break;
+  }
+  entry[slot] = ent;
+  exitv[slot] = ex;
+  nblk[slot] = live ? nb : 0u;
+  if (t == DEC_G - 1) {
+    if (gl < sc.ngrp - 1 && (round == 0 || ex != gx_in[g])) atomicAdd(changed, 1u);
+    gx_out[g] = ex;
+  }
+}
+
+// Exclusive prefix of a scan's per-subsequence block counts (one 1024-thread
+// workgroup per scan).
+__global__ void __launch_bounds__(1024) k_dec_prefix(const DecScan* __restrict__ scans,
+                                                     const unsigned* __restrict__ nblk,
+                                                     unsigned* __restrict__ blk0) {
+  __shared__ unsigned long long s_w[16];
+  const DecScan sc = scans[blockIdx.x];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const long long n = (long long)sc.ngrp * DEC_G, g0 = (long long)sc.grp0 * DEC_G;
+  const long long C = (n + 1023) / 1024, i0 = t * C, i1 = min(n, i0 + C);
+  unsigned long long loc = 0ull;
+  for (long long i = i0; i < i1; ++i) loc += nblk[g0 + i];
+  unsigned long long inc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  unsigned long long run = inc - loc;
+  for (int w = 0; w < wv; ++w) run += s_w[w];
+  for (long long i = i0; i < i1; ++i) {
+    const unsigned v = nblk[g0 + i];
+    blk0[g0 + i] = (unsigned)(run < 0xffffffffull ? run : 0xffffffffull);  // beyond any scan's block count
+    run += v;
+  }
+}
+
+struct DecSink {
+  int16_t* out;
+  const uint8_t* zz;
+  __device__ __forceinline__ void operator()(int64_t blk, int k, int v) const { out[blk * 64 + zz[k]] = (int16_t)v; }
+};
+
+__constant__ uint8_t c_dec_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                     12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+__global__ void __launch_bounds__(DEC_G) k_dec_write(const uint8_t* __restrict__ files,
+                                                     const DecScan* __restrict__ scans,
+                                                     const int* __restrict__ grp_scan,
+                                                     const HuffDecTab* __restrict__ tabs,
+                                                     const unsigned long long* __restrict__ entry,
+                                                     const unsigned* __restrict__ blk0, int16_t* __restrict__ coeffs,
+                                                     uint32_t* __restrict__ status) {
+  __shared__ HuffDecTab s_tab[2];
+  __shared__ uint32_t s_win[DEC_LDS];
+  __shared__ uint8_t s_zz[64];
+  const int g = blockIdx.x, t = threadIdx.x;
+  const DecScan sc = scans[grp_scan[g]];
+  const long long i = (long long)(g - sc.grp0) * DEC_G + t;
+  const size_t slot = (size_t)g * DEC_G + t;
+  load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
+  if (t < 64) s_zz[t] = c_dec_zz[t];
+  const DecLdsSrc src = dec_stage(s_win, files + sc.data_off, sc.nbytes, (long long)(g - sc.grp0) * DEC_G * (DEC_S / 8));
+  __syncthreads();
+  if (i >= sc.nsub) return;
+  // stores are clamped to the scan's blocks: hd_run stops at blk == nblocks
+  const uint32_t fl = hd_write_lane(src, &s_tab[0], &s_tab[1], entry[slot],
+                                    (unsigned long long)(i + 1) * DEC_S, (int64_t)blk0[slot], (int64_t)sc.nblocks,
+                                    i == sc.nsub - 1, DecSink{coeffs + sc.coef_off, s_zz});
+  if (fl) atomicOr(&status[sc.frame], fl);
+}
+
+// DC differences -> values: inclusive sum over the scan's blocks in 64-bit,
+// judged against int16 (one 1024-thread workgroup per scan).
+__global__ void __launch_bounds__(1024) k_dec_dc(const DecScan* __restrict__ scans, int16_t* __restrict__ coeffs,
+                                                 uint32_t* __restrict__ status) {
+  __shared__ long long s_w[16];
+  const DecScan sc = scans[blockIdx.x];
+  if (sc.nblocks == 0) return;
+  int16_t* cf = coeffs + sc.coef_off;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const long long n = sc.nblocks;
+  const long long C = (n + 1023) / 1024, i0 = t * C, i1 = min(n, i0 + C);
+  long long loc = 0;
+  for (long long i = i0; i < i1; ++i) loc += cf[64 * i];
+  long long inc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  long long run = inc - loc;
+  for (int w = 0; w < wv; ++w) run += s_w[w];
+  bool bad = false;
+  for (long long i = i0; i < i1; ++i) {
+    run += cf[64 * i];
+    bad = bad || run < -32768 || run > 32767;
+    cf[64 * i] = (int16_t)run;
+  }
+  if (bad) atomicOr(&status[sc.frame], HD_DC_RANGE);
+}
+
+// ------------------------------------------------------------ driver --
+
+// work: dec_hdr_bytes(n) bytes of device scratch; the scans' (offset, length)
+// pairs come first in it (6 n long long).
+size_t dec_hdr_bytes(int n) { return sizeof(long long) * 14 * (size_t)n + 4 * (size_t)n; }
+
+hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned long long* lengths,
+                          const uint8_t* hdr_dev, int hl, int n, void* work, uint32_t* status, hipStream_t s) {
+  long long* scaninfo = (long long*)work;
+  long long* pos = scaninfo + 6 * (size_t)n;
+  int* cnt = (int*)(pos + 8 * (size_t)n);
+  hipError_t e = hipMemsetAsync(cnt, 0, 4 * (size_t)n, s);
+  if (e != hipSuccess) return e;
+  const long long per = 256ll * DEC_FIND_B;
+  const long long gx = (stride + 16 + per - 1) / per;
+  if (gx > 0x7fffffffll || n > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_dec_find, dim3((unsigned)gx, n), dim3(256), 0, s, files, stride, lengths, hl, cnt, pos);
+  kmark(s, "k_dec_find");
+  hipLaunchKernelGGL(k_dec_hdr, dim3(n), dim3(256), 0, s, files, stride, lengths, hdr_dev, hl, cnt, pos, scaninfo,
+                     status);
+  kmark(s, "k_dec_hdr");
+  return hipGetLastError();
+}
+
+// The decode of host-described scans (sc: nscans entries laid out by
+// dec_layout, ngroups workgroups, the longest scan max_ngrp): uploads the
+// descriptors, zero-fills n_coeffs coefficients, synchronises between
+// propagation rounds.  *too_many: the round bound was exceeded (a bug, not a
+// property of any input).  status must hold the frames' initial words.
+hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
+                   const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
+                   hipStream_t s, unsigned* rounds, int* too_many) {
+  *rounds = 0;
+  *too_many = 0;
+  hipError_t e = hipMemsetAsync(coeffs, 0, sizeof(int16_t) * (size_t)n_coeffs, s);
+  if (e != hipSuccess || ngroups == 0) return e;
+  const DecScratch d = dec_scratch(scratch, ngroups, nscans);
+  int* gs = (int*)malloc(4 * (size_t)ngroups);
+  if (!gs) return hipErrorOutOfMemory;
+  for (int i = 0; i < nscans; ++i)
+    for (int g = 0; g < sc[i].ngrp; ++g) gs[sc[i].grp0 + g] = i;
+  e = hipMemcpyAsync(d.scans, sc, sizeof(DecScan) * (size_t)nscans, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.grp_scan, gs, 4 * (size_t)ngroups, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // gs is freed below
+  free(gs);
+  if (e != hipSuccess) return e;
+  const unsigned grid = (unsigned)ngroups;
+  for (int r = 0;; ++r) {
+    if (r >= max_ngrp) {  // entries of workgroups 0..r are settled after launch r
+      *too_many = 1;
+      return hipSuccess;
+    }
+    if ((e = hipMemsetAsync(d.changed, 0, 4, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dec_sync, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
+                       d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r);
+    kmark(s, "k_dec_sync");
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    unsigned ch = 0;
+    if ((e = hipMemcpyAsync(&ch, d.changed, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+    *rounds = (unsigned)(r + 1);
+    if (!ch) break;
+  }
+  hipLaunchKernelGGL(k_dec_prefix, dim3(nscans), dim3(1024), 0, s, d.scans, d.nblk, d.blk0);
+  kmark(s, "k_dec_prefix");
+  hipLaunchKernelGGL(k_dec_write, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry, d.blk0,
+                     coeffs, status);
+  kmark(s, "k_dec_write");
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dec_dc, dim3(nscans), dim3(1024), 0, s, d.scans, coeffs, status);
+  kmark(s, "k_dec_dc");
+  return hipGetLastError();
+}
+
+}  // namespace jds

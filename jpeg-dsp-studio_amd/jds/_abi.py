@@ -67,6 +67,27 @@ class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('total_ms', C.c_double), ('launches', C.c_int64)]
 
 
+class JfifScan(C.Structure):
+    _fields_ = [('component', C.c_int32), ('dc_table', C.c_int32), ('ac_table', C.c_int32),
+                ('reserved', C.c_int32), ('offset', C.c_int64), ('length', C.c_int64)]
+
+
+class JfifHuff(C.Structure):
+    _fields_ = [('bits', C.c_uint8 * 16), ('vals', C.c_uint8 * 256), ('n_vals', C.c_int32),
+                ('defined', C.c_int32)]
+
+
+class JfifInfo(C.Structure):
+    _fields_ = [('H', C.c_int64), ('W', C.c_int64), ('subsampling', C.c_int32), ('n_scans', C.c_int32),
+                ('qtable', C.c_double * 64), ('scan', JfifScan * 3), ('huff', JfifHuff * 4),
+                ('y_blocks', C.c_int64), ('c_blocks', C.c_int64), ('coeffs_needed', C.c_int64),
+                ('status', C.c_uint32), ('rounds', C.c_uint32)]
+
+
+# frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
+DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE = 1, 2, 4, 8, 16, 32
+
+
 class JDSError(RuntimeError):
     pass
 
@@ -114,6 +135,13 @@ _SIGS = {
     'jds_plan_entropy': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     'jds_encode_jfif': (C.c_int, [_P, C.POINTER(Params), C.c_int64, C.c_int64, _P, _P, C.c_int64,
                                   C.POINTER(C.c_int64), _P]),
+    'jds_jfif_parse': (C.c_int, [_P, C.c_int64, C.POINTER(JfifInfo)]),
+    'jds_decode_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(JfifInfo)]),
+    'jds_decompress_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(JfifInfo)]),
+    'jds_plan_entropy_decode': (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P]),
+    'jds_entropy_decode_info': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'jds_plan_entropy_decode_rounds': (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    'jds_selftest_huffdec': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_area_tab': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P]),

@@ -71,6 +71,26 @@ def compress_reconstruct_raw(image: np.ndarray, quality: int, qtable: np.ndarray
     return res
 
 
+def decompress_jfif(data, device: int = 0, with_info: bool = False):
+    """jds_decompress_jfif: a baseline JFIF of the profile this library writes -> the HxWx3
+    uint8 image this codec reconstructs from its coefficients (the bytes
+    compress_reconstruct_raw returned for the frame that made the file);
+    with_info: (image, {'coeffs', 'H', 'W', 'mode', 'qtable', 'rounds'})."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.JfifInfo()
+    check(lib().jds_jfif_parse(p, n, C.byref(info)))
+    H, W = int(info.H), int(info.W)
+    img = np.empty((H, W, 3), np.uint8)
+    cf = np.empty(int(info.coeffs_needed), np.int16)
+    with lease(device) as ctx:
+        check(lib().jds_decompress_jfif(ctx.handle, p, n, img.ctypes.data, img.size, cf.ctypes.data, C.byref(info)))
+    if not with_info:
+        return img
+    d = entropy._info_dict(info)
+    return img, {'coeffs': cf, 'H': H, 'W': W, 'mode': d['mode'], 'qtable': d['qtable'], 'rounds': int(info.rounds)}
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

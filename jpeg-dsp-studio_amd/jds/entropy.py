@@ -1,7 +1,10 @@
 """Baseline JPEG entropy coding on the GPU (include/jds.h: jds_encode_jfif,
 jds_plan_entropy): the reference's quantised coefficients -> a standard JFIF
 file (the reference itself only estimates the size,
-utils/metrics.py:51-92).  Byte-for-byte definition: oracle/jpeg_entropy.py."""
+utils/metrics.py:51-92).  Byte-for-byte definition: oracle/jpeg_entropy.py.
+And back (jds_jfif_parse, jds_decode_jfif, jds_plan_entropy_decode): a
+baseline file of that profile -> the coefficients, by a self-synchronising
+parallel Huffman decode (DESIGN.md "Entropy decode")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,6 +41,73 @@ def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarra
         return out[:n.value].tobytes(), [int(b) for b in bits]
 
 
+_MODE_NAMES = {v: k for k, v in _abi.MODE_CODES.items()}
+
+
+def _bytes_arg(data):
+    """(keep-alive array, pointer, length) of a bytes-like file."""
+    a = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    if a.size == 0:
+        raise ValueError('empty file')
+    return a, a.ctypes.data, int(a.size)
+
+
+def _info_dict(info: _abi.JfifInfo) -> dict:
+    names = ('dc0', 'dc1', 'ac0', 'ac1')
+    huff = {}
+    for i, nm in enumerate(names):
+        h = info.huff[i]
+        if h.defined:
+            huff[nm] = (list(h.bits), list(h.vals)[:h.n_vals])
+    return {'H': int(info.H), 'W': int(info.W), 'mode': _MODE_NAMES[info.subsampling],
+            'qtable': np.ctypeslib.as_array(info.qtable).astype(np.float64).reshape(8, 8),
+            'scans': [{'component': int(s.component), 'dc_table': int(s.dc_table), 'ac_table': int(s.ac_table),
+                       'offset': int(s.offset), 'length': int(s.length)} for s in info.scan[:info.n_scans]],
+            'huffman': huff, 'y_blocks': int(info.y_blocks), 'c_blocks': int(info.c_blocks),
+            'coeffs_needed': int(info.coeffs_needed)}
+
+
+def parse_jfif(data) -> dict:
+    """jds_jfif_parse (host only, no GPU): geometry, table, scans and Huffman tables of a
+    baseline JFIF of the profile this library writes.  ValueError for anything else."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JfifInfo()
+    check(lib().jds_jfif_parse(p, n, C.byref(info)))
+    return _info_dict(info)
+
+
+def decode_info() -> Tuple[int, int]:
+    """(bits per subsequence, subsequences per workgroup) of the GPU decoder."""
+    s, g = C.c_int32(0), C.c_int32(0)
+    check(lib().jds_entropy_decode_info(C.byref(s), C.byref(g)))
+    return int(s.value), int(g.value)
+
+
+def decode_jfif(data, device: int = 0) -> dict:
+    """One file -> {'coeffs' (int16, reference layout), 'H', 'W', 'mode', 'qtable', 'rounds'}."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JfifInfo()
+    check(lib().jds_jfif_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.coeffs_needed), np.int16)
+    with _abi.lease(device) as ctx:
+        check(lib().jds_decode_jfif(ctx.handle, p, n, cf.ctypes.data, cf.size, C.byref(info)))
+    d = _info_dict(info)
+    return {'coeffs': cf, 'H': d['H'], 'W': d['W'], 'mode': d['mode'], 'qtable': d['qtable'],
+            'rounds': int(info.rounds)}
+
+
+def host_decode_jfif(data, subseq_bits: int = 1024):
+    """Test aid (jds_selftest_huffdec): the decoder's algorithm on the host with the
+    kernels' shared core -> (coeffs, [rounds of the Y, Cb, Cr scans]).  No GPU."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JfifInfo()
+    check(lib().jds_jfif_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.coeffs_needed), np.int16)
+    rounds = (C.c_int32 * 3)()
+    check(lib().jds_selftest_huffdec(p, n, int(subseq_bits), cf.ctypes.data, cf.size, rounds))
+    return cf, [int(r) for r in rounds]
+
+
 def bitrate_from_jfif(nbytes: int, shape) -> dict:
     """bpp / compression ratio of a real file, in estimate_bitrate_no_entropy's
     terms (utils/metrics.py:62-92: 24-bit originals)."""
@@ -62,3 +132,19 @@ class PlanEntropy:
             stream = lib().jds_ctx_stream(self.plan.ctx.handle)
         check(lib().jds_plan_entropy(self.plan.handle, coeffs_dev, out_dev, out_stride, lengths_dev,
                                      scan_bits_dev or None, stream))
+
+    def decode(self, files_dev: int, stride: int, lengths_dev: int, coeffs_dev: int, status_dev: int,
+               stream: int | None = None):
+        """jds_plan_entropy_decode: the files run() wrote (or any with the plan's header) back to
+        coefficients; status_dev: one uint32 per frame (0 = decoded).  Waits for the stream
+        between propagation rounds."""
+        if stream is None:
+            stream = lib().jds_ctx_stream(self.plan.ctx.handle)
+        check(lib().jds_plan_entropy_decode(self.plan.handle, files_dev, stride, lengths_dev, coeffs_dev,
+                                            status_dev, stream))
+
+    def decode_rounds(self) -> int:
+        """Inter-workgroup propagation rounds of the last decode()."""
+        r = C.c_uint32(0)
+        check(lib().jds_plan_entropy_decode_rounds(self.plan.handle, C.byref(r)))
+        return int(r.value)

@@ -1,0 +1,76 @@
+// jfif_host_san.cpp — stand-alone host program over the JFIF parser and the
+// entropy decoder's shared core (csrc/jds_huffdec.hpp), for sanitizer runs:
+//
+//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -Iinclude -Ijpeg-dsp-studio_amd/csrc tools/jfif_host_san.cpp -o jfif_host_san
+//   ./jfif_host_san DIR [subseq_bits ...]
+//
+// Parses every file of DIR from an exactly-sized heap copy (so a read past the
+// end is a sanitizer report) and host-decodes the ones that parse, with each
+// subsequence size (default 64, 128, 1024).  Rejected and defective files are
+// expected; the program exits 0 unless it cannot read DIR.  No HIP, no GPU.
+#include <dirent.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <string>
+#include <vector>
+
+#include "jds_huffdec.hpp"
+
+int main(int argc, char** argv) {
+  if (argc < 2) {
+    fprintf(stderr, "usage: %s DIR [subseq_bits ...]\n", argv[0]);
+    return 2;
+  }
+  std::vector<int> sizes;
+  for (int i = 2; i < argc; ++i) sizes.push_back(atoi(argv[i]));
+  if (sizes.empty()) sizes = {64, 128, 1024};
+  for (int s : sizes)
+    if (s < 64 || s % 8) {
+      fprintf(stderr, "subseq_bits must be a multiple of 8, at least 64\n");
+      return 2;
+    }
+  DIR* dir = opendir(argv[1]);
+  if (!dir) {
+    perror(argv[1]);
+    return 2;
+  }
+  long files = 0, parsed = 0, decoded = 0, defective = 0;
+  while (dirent* e = readdir(dir)) {
+    if (e->d_name[0] == '.') continue;
+    const std::string path = std::string(argv[1]) + "/" + e->d_name;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) continue;
+    fseek(f, 0, SEEK_END);
+    const long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    // exactly n bytes on the heap: the sanitizer's red zone starts at data + n
+    uint8_t* data = (uint8_t*)malloc(n > 0 ? (size_t)n : 1);
+    if (!data || (n > 0 && fread(data, 1, (size_t)n, f) != (size_t)n)) {
+      fclose(f);
+      free(data);
+      continue;
+    }
+    fclose(f);
+    ++files;
+    jds_jfif_info info;
+    char msg[256];
+    if (jds::hd_parse(data, n, &info, false, msg, sizeof msg) == JDS_OK && info.coeffs_needed <= (int64_t)1 << 28) {
+      ++parsed;
+      int16_t* cf = (int16_t*)malloc(sizeof(int16_t) * (size_t)info.coeffs_needed);
+      if (cf) {
+        for (int s : sizes) {
+          int32_t rounds[3] = {0, 0, 0};
+          const uint32_t st = jds::hd_host_decode(data, &info, s, cf, rounds);
+          st ? ++defective : ++decoded;
+        }
+        free(cf);
+      }
+    }
+    free(data);
+  }
+  closedir(dir);
+  printf("%ld files, %ld parsed, %ld decodes clean, %ld defective\n", files, parsed, decoded, defective);
+  return 0;
+}
