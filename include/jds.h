@@ -284,7 +284,14 @@ int jds_encode_jfif(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W, con
  *
  * Profile: SOF0, 8-bit, components 1, 2, 3, Y sampled 1x1 / 2x1 / 2x2 with 1x1
  * chroma, one quantisation table, three non-interleaved scans in any order,
- * Huffman tables from the file's DHT segments, no DRI; APPn / COM are skipped.
+ * Huffman tables from the file's DHT segments; APPn / COM are skipped.
+ * Restart intervals (T.81 B.2.4.4, E.1.4): a DRI segment (length 4, else
+ * JDS_EINVAL) sets the interval Ri for the scans that follow, Ri = 0 switches
+ * restarts off, DRI may appear more than once.  A non-interleaved scan's MCU is
+ * one block, so a scan of nb blocks then holds ceil(nb / Ri) - 1 markers, the
+ * i-th being RST(i & 7); a wrong count or order is JDS_EINVAL (the message names
+ * the scan and DRI), as is an RSTm with Ri = 0 or outside scan data.  Fill
+ * bytes (FF FF) before a marker inside such a scan are JDS_ENOTSUP.
  * Anything else in a well-formed file is JDS_ENOTSUP (the message names the
  * feature), malformed bytes are JDS_EINVAL; sizes whose T.81 chroma block grid
  * differs from the reference's floor-sized planes are JDS_ENOTSUP as for the
@@ -294,20 +301,23 @@ int jds_encode_jfif(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W, con
  * subsequences of a fixed number of bits, one GPU lane decodes each from a
  * guessed state, and exit states are handed to the next subsequence until none
  * changes -- inside a workgroup in one launch, across workgroups between
- * launches (the host reads a counter after each round).  A frame's status
- * word is 0 or a combination of JDS_DEC_* bits. */
+ * launches (the host reads a counter after each round).  A scan with restart
+ * intervals needs none of that: every interval is a stream of its own whose
+ * first block is known, one lane decodes it in one pass (0 rounds).  A frame's
+ * status word is 0 or a combination of JDS_DEC_* bits. */
 #define JDS_DEC_HEADER   1u  /* plan path: header differs from the plan's, or lengths[i] == 0 */
 #define JDS_DEC_CODE     2u  /* invalid Huffman code (or a size outside baseline) */
 #define JDS_DEC_K63      4u  /* a run past coefficient 63 */
 #define JDS_DEC_OVERRUN  8u  /* the scan data end inside a symbol */
 #define JDS_DEC_COUNT    16u /* the scan holds fewer or more blocks than the frame needs */
 #define JDS_DEC_DC_RANGE 32u /* a DC value (sum of the differences) outside int16 */
+#define JDS_DEC_RESTART  64u /* the restart markers are not the ones the geometry and the interval require */
 
 typedef struct {
   int32_t component;          /* 1 Y, 2 Cb, 3 Cr */
   int32_t dc_table, ac_table; /* Huffman table ids (0 / 1) */
-  int32_t reserved;
-  int64_t offset, length;     /* the entropy-coded segment: stuffed bytes up to the next marker */
+  int32_t restart_interval;   /* the DRI interval in effect at this scan's SOS (MCUs = blocks), 0: none */
+  int64_t offset, length;     /* the entropy-coded segment: stuffed bytes up to the next marker, RSTm markers included */
 } jds_jfif_scan;
 
 typedef struct {
@@ -365,11 +375,37 @@ int jds_entropy_decode_info(int32_t* subseq_bits, int32_t* subseq_per_group);
 /* Inter-workgroup propagation rounds (launches of the synchronisation kernel) the plan's last decode took. */
 int jds_plan_entropy_decode_rounds(const jds_plan* plan, uint32_t* rounds);
 
+/* Restart intervals (DESIGN.md "Restart intervals").  The writer codes in
+ * independent 64-block segments, one wave each; with interval 64 every segment
+ * is a restart interval: DRI after the last DHT, every interval padded to its
+ * byte, RST(i - 1 & 7) in front of interval i >= 1 of a scan.  Byte-for-byte
+ * definition: tests/restart_ref.py over oracle/jpeg_entropy.py.
+ *   jds_entropy_restart_info: the one interval the writer supports besides 0
+ *     (64), and the largest interval the decoder gives to one lane (files with a
+ *     larger one decode through the self-synchronising kernels, one descriptor
+ *     per interval).
+ *   The _rst calls mirror their plain namesakes; interval 0 is JDS_EINVAL (the
+ *     plain calls write plain files), any value but the writer's is JDS_ENOTSUP.
+ *   jds_plan_entropy_decode_rst: as jds_plan_entropy_decode for the files
+ *     jds_plan_entropy_rst writes, but ASYNCHRONOUS: the plan knows every
+ *     frame's marker count, so nothing is read back.  A frame whose markers
+ *     (SOS, RST0, RST1, .., SOS, .., EOI) are not the ones its geometry and the
+ *     interval require gets JDS_DEC_RESTART and, like a JDS_DEC_HEADER frame,
+ *     zero coefficients.  The interval must not exceed lane_max_blocks. */
+int jds_entropy_restart_info(int32_t* writer_interval, int32_t* lane_max_blocks);
+int jds_plan_entropy_capacity_rst(const jds_plan* plan, int32_t interval, int64_t* bytes_per_frame);
+int jds_plan_entropy_rst(jds_plan* plan, int32_t interval, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
+                         uint64_t* lengths, uint64_t* scan_bits, void* stream);
+int jds_encode_jfif_rst(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W, int32_t interval,
+                        const int16_t* coeffs, uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits);
+int jds_plan_entropy_decode_rst(jds_plan* plan, int32_t interval, const uint8_t* files, int64_t stride,
+                                const uint64_t* lengths, int16_t* coeffs, uint32_t* status, void* stream);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation
  * rule.  coeffs: coeffs_cap int16 entries; rounds_out[3]: decode rounds of the
- * Y, Cb, Cr scans.  No GPU. */
+ * Y, Cb, Cr scans (0 for a scan with restart intervals).  No GPU. */
 int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
                          int32_t* rounds_out);
 

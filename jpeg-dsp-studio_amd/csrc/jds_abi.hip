@@ -86,6 +86,19 @@ void ent_sizes(const Geo& g, int n, size_t* sz);
 hipError_t launch_entropy(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
                           const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                           unsigned long long* scan_bits, hipStream_t s);
+int ent_restart_interval();
+int ent_header_rst(const double* q, int mode, int H, int W, int interval, uint8_t* o);
+long long ent_capacity_rst(const Geo& g);
+hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
+                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
+                              unsigned long long* scan_bits, hipStream_t s);
+void rst_constants(int* lane_max);
+size_t rst_work_bytes(int n, const RstGeo& rg);
+hipError_t launch_dec_rst(const uint8_t* files, const RstIv* ivs_dev, long long niv, const HuffDecTab* tabs_dev,
+                          int16_t* coeffs, uint32_t* status, hipStream_t s);
+hipError_t launch_dec_rst_plan(const uint8_t* files, long long stride, const unsigned long long* lengths,
+                               const uint8_t* hdr_dev, int hl, int n, const RstGeo& rg, void* work,
+                               const HuffDecTab* tabs_dev, int16_t* coeffs, uint32_t* status, hipStream_t s);
 void dec_constants(int* s, int* g);
 long long dec_layout(DecScan* sc, int nscans, int* max_ngrp);
 size_t dec_scratch_bytes(long long ngroups, int nscans);
@@ -173,6 +186,7 @@ struct jds_ctx {
   DevBuf planes;  // 16x16 path: reconstructed chroma planes
   DevBuf ent[8], ent_hdr, ent_tab, ent_cf, ent_out, ent_meta;  // entropy coder (jds_encode_jfif)
   DevBuf dec_file, dec_tab, dec_scr, dec_st;  // entropy decoder (jds_decode_jfif): file, tables, scratch, status
+  DevBuf dec_iv;                              // its restart interval table
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   size_t ss_budget = 0;  // SSIM scratch budget per launch group (0: SSIM_SCRATCH; jds_ctx_set_ssim_scratch)
 };
@@ -317,6 +331,8 @@ struct jds_plan {
   DevBuf ent[8], ent_hdr, ent_tab;  // entropy coder scratch, allocated by the first jds_plan_entropy
   DevBuf dec_tab, dec_scr, dec_info;  // entropy decoder (jds_plan_entropy_decode): tables, scratch, scan ranges
   unsigned dec_rounds = 0;            // propagation rounds of the last decode
+  DevBuf rst_hdr, rst_work;           // jds_plan_entropy_decode_rst: restart header templates, interval table and marker list
+  int rst_hdr_interval = 0;           // the interval rst_hdr was built for
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   GenBufs gen() const { return {(const AreaTap*)gen_tab.p, (double*)gen_sub.p, (double*)gen_rec.p}; }
   // jds_plan_profile: the launch marks of profiled runs (event pool + names)
@@ -590,6 +606,7 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->dec_tab.release();
   c->dec_scr.release();
   c->dec_st.release();
+  c->dec_iv.release();
   c->gen_tab.release();
   c->gen_sub.release();
   c->gen_rec.release();
@@ -993,6 +1010,8 @@ void jds_plan_destroy(jds_plan* p) {
   p->dec_tab.release();
   p->dec_scr.release();
   p->dec_info.release();
+  p->rst_hdr.release();
+  p->rst_work.release();
   free(p->qt);
   marks_release(p->marks);
   delete p;
@@ -1450,12 +1469,23 @@ int jds_plan_entropy_capacity(const jds_plan* p, int64_t* bytes_per_frame) {
   return JDS_OK;
 }
 
-int jds_plan_entropy(jds_plan* p, const int16_t* coeffs, uint8_t* out, int64_t out_stride, uint64_t* lengths,
-                     uint64_t* scan_bits, void* stream) {
+// The writer's restart interval: 0 is the plain calls' business, anything but the coder's segment size unsupported.
+static int check_writer_interval(int32_t interval) {
+  if (interval == 0)
+    return fail(JDS_EINVAL, "restart interval 0: the plain entropy calls write files without restart markers");
+  if (interval != ent_restart_interval())
+    return fail(JDS_ENOTSUP, "restart interval %d: the writer supports %d (its segment size) and 0", interval,
+                ent_restart_interval());
+  return JDS_OK;
+}
+
+static int plan_entropy(jds_plan* p, bool rst, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
+                        uint64_t* lengths, uint64_t* scan_bits, void* stream) {
   if (!p || !coeffs || !out || !lengths) return fail(JDS_EINVAL, "null argument");
-  if (out_stride < ent_capacity(p->g))
-    return fail(JDS_EINVAL, "out_stride %lld < worst-case file size %lld", (long long)out_stride,
-                (long long)ent_capacity(p->g));
+  if (p->g.bs != 8) return fail(JDS_ENOTSUP, "JPEG entropy coding needs 8x8 blocks (block_size %d)", p->g.bs);
+  const long long cap = rst ? ent_capacity_rst(p->g) : ent_capacity(p->g);
+  if (out_stride < cap)
+    return fail(JDS_EINVAL, "out_stride %lld < worst-case file size %lld", (long long)out_stride, cap);
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t s = (hipStream_t)stream;
   if (!p->ent_hdr.p) {
@@ -1464,13 +1494,45 @@ int jds_plan_entropy(jds_plan* p, const int16_t* coeffs, uint8_t* out, int64_t o
   }
   void* bufs[8];
   for (int i = 0; i < 8; ++i) bufs[i] = p->ent[i].p;
-  HIP_TRY(launch_entropy(p->g, p->n, coeffs, bufs, (const uint8_t*)p->ent_hdr.p, p->ent_tab.p, out, out_stride,
-                         (unsigned long long*)lengths, (unsigned long long*)scan_bits, s));
+  const MarkScope marks_(p, s);
+  HIP_TRY((rst ? launch_entropy_rst : launch_entropy)(p->g, p->n, coeffs, bufs, (const uint8_t*)p->ent_hdr.p,
+                                                      p->ent_tab.p, out, out_stride, (unsigned long long*)lengths,
+                                                      (unsigned long long*)scan_bits, s));
   return JDS_OK;
 }
 
-int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, const int16_t* coeffs, uint8_t* out,
-                    int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
+int jds_plan_entropy(jds_plan* p, const int16_t* coeffs, uint8_t* out, int64_t out_stride, uint64_t* lengths,
+                     uint64_t* scan_bits, void* stream) {
+  return plan_entropy(p, false, coeffs, out, out_stride, lengths, scan_bits, stream);
+}
+
+int jds_entropy_restart_info(int32_t* writer_interval, int32_t* lane_max_blocks) {
+  if (!writer_interval || !lane_max_blocks) return fail(JDS_EINVAL, "null argument");
+  int lm;
+  rst_constants(&lm);
+  *writer_interval = ent_restart_interval();
+  *lane_max_blocks = lm;
+  return JDS_OK;
+}
+
+int jds_plan_entropy_capacity_rst(const jds_plan* p, int32_t interval, int64_t* bytes_per_frame) {
+  if (!p || !bytes_per_frame) return fail(JDS_EINVAL, "null argument");
+  if (p->g.bs != 8) return fail(JDS_ENOTSUP, "JPEG entropy coding needs 8x8 blocks (block_size %d)", p->g.bs);
+  const int rc = check_writer_interval(interval);
+  if (rc) return rc;
+  *bytes_per_frame = ent_capacity_rst(p->g);
+  return JDS_OK;
+}
+
+int jds_plan_entropy_rst(jds_plan* p, int32_t interval, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
+                         uint64_t* lengths, uint64_t* scan_bits, void* stream) {
+  const int rc = check_writer_interval(interval);
+  if (rc) return rc;
+  return plan_entropy(p, true, coeffs, out, out_stride, lengths, scan_bits, stream);
+}
+
+static int encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, bool rst, const int16_t* coeffs,
+                       uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
   if (!c || !prm || !coeffs || !out || !out_len) return fail(JDS_EINVAL, "null argument");
   Geo g;
   int mode;
@@ -1479,7 +1541,7 @@ int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, con
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   if ((rc = ent_prepare(g, mode, 1, prm->qtable, c->ent, c->ent_hdr, c->ent_tab, s))) return rc;
-  const long long cap = ent_capacity(g);
+  const long long cap = rst ? ent_capacity_rst(g) : ent_capacity(g);
   HIP_TRY(c->ent_cf.ensure((size_t)g.cpf * sizeof(int16_t)));
   HIP_TRY(c->ent_out.ensure((size_t)cap));
   HIP_TRY(c->ent_meta.ensure(4 * sizeof(unsigned long long)));
@@ -1487,8 +1549,9 @@ int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, con
   void* bufs[8];
   for (int i = 0; i < 8; ++i) bufs[i] = c->ent[i].p;
   unsigned long long* meta = (unsigned long long*)c->ent_meta.p;
-  HIP_TRY(launch_entropy(g, 1, (const int16_t*)c->ent_cf.p, bufs, (const uint8_t*)c->ent_hdr.p, c->ent_tab.p,
-                         (uint8_t*)c->ent_out.p, cap, meta, meta + 1, s));
+  HIP_TRY((rst ? launch_entropy_rst : launch_entropy)(g, 1, (const int16_t*)c->ent_cf.p, bufs,
+                                                      (const uint8_t*)c->ent_hdr.p, c->ent_tab.p,
+                                                      (uint8_t*)c->ent_out.p, cap, meta, meta + 1, s));
   unsigned long long m[4];
   HIP_TRY(hipMemcpyAsync(m, meta, sizeof m, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1501,6 +1564,18 @@ int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, con
   if ((long long)m[0] > out_cap) return fail(JDS_EINVAL, "output buffer too small: %llu bytes needed", m[0]);
   HIP_TRY(hipMemcpy(out, c->ent_out.p, (size_t)m[0], hipMemcpyDeviceToHost));
   return JDS_OK;
+}
+
+int jds_encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, const int16_t* coeffs, uint8_t* out,
+                    int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
+  return encode_jfif(c, prm, H, W, false, coeffs, out, out_cap, out_len, scan_bits);
+}
+
+int jds_encode_jfif_rst(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, int32_t interval,
+                        const int16_t* coeffs, uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
+  const int rc = check_writer_interval(interval);
+  if (rc) return rc;
+  return encode_jfif(c, prm, H, W, true, coeffs, out, out_cap, out_len, scan_bits);
 }
 
 // ------------------------------------------------------ entropy decoding --
@@ -1546,27 +1621,73 @@ static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfi
     if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0)
       return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
   }
-  DecScan sc[3];
+  // A scan without restart intervals is one descriptor of the self-synchronising
+  // kernels.  With an interval of at most lane_max blocks every interval goes to
+  // a lane of k_dec_rst; with a larger one every interval is a descriptor of its
+  // own (byte range, block count, destination), whose DC sum is the interval's.
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<DecScan> sc;
+  std::vector<RstIv> ivs;
   for (int i = 0; i < 3; ++i) {
     const jds_jfif_scan& f = info->scan[i];
     const int comp = f.component - 1;
     if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
-    sc[i] = DecScan{};
-    sc[i].data_off = f.offset;
-    sc[i].nbytes = f.length;
-    sc[i].coef_off = comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks);
-    sc[i].nblocks = (int)(comp ? info->c_blocks : info->y_blocks);
-    sc[i].frame = 0;
-    sc[i].dc_tab = f.dc_table;
-    sc[i].ac_tab = 2 + f.ac_table;
+    const long long coef_off = comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks);
+    const long long nblocks = comp ? info->c_blocks : info->y_blocks;
+    const long long ri = f.restart_interval;
+    auto descriptor = [&](long long off, long long nbytes, long long blk0, long long nb) {
+      DecScan d{};
+      d.data_off = off;
+      d.nbytes = nbytes;
+      d.coef_off = coef_off + 64 * blk0;
+      d.nblocks = (int)nb;
+      d.frame = 0;
+      d.dc_tab = f.dc_table;
+      d.ac_tab = 2 + f.ac_table;
+      sc.push_back(d);
+    };
+    if (ri == 0) {
+      descriptor(f.offset, f.length, 0, nblocks);
+      continue;
+    }
+    // the parser checked the markers' number and order: interval k ends at marker k
+    const uint8_t* d = data + f.offset;
+    long long a = 0, blk0 = 0;
+    while (blk0 < nblocks) {
+      long long e = a;
+      while (e < f.length && !(d[e] == 0xFF && e + 1 < f.length && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
+      const long long nb = nblocks - blk0 < ri ? nblocks - blk0 : ri;
+      if (ri <= lane_max) {
+        if (e - a > 0x7fffffffll) return fail(JDS_ENOTSUP, "restart interval of %lld bytes", e - a);
+        RstIv v{};
+        v.data_off = f.offset + a;
+        v.coef_off = coef_off + 64 * blk0;
+        v.nbytes = (int)(e - a);
+        v.nblk = (int)nb;
+        v.frame = 0;
+        v.tabs = f.dc_table | ((2 + f.ac_table) << 8);
+        ivs.push_back(v);
+      } else {
+        descriptor(f.offset + a, e - a, blk0, nb);
+      }
+      blk0 += nb;
+      a = e + 2;
+      if (e >= f.length && blk0 < nblocks) return fail(JDS_EINVAL, "restart markers missing from the scan data (DRI %lld)", ri);
+    }
   }
+  if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
+  const int nsc = (int)sc.size();
   int max_ngrp = 0;
-  const long long ng = dec_layout(sc, 3, &max_ngrp);
+  const long long ng = dec_layout(sc.data(), nsc, &max_ngrp);
   if (ng < 0) return fail(JDS_ENOTSUP, "scan too long");
   HIP_TRY(c->dec_file.ensure((size_t)len));
   HIP_TRY(c->dec_tab.ensure(sizeof tabs));
-  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, 3)));
+  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, nsc)));
   HIP_TRY(c->dec_st.ensure(16));
+  HIP_TRY(c->dec_iv.ensure(sizeof(RstIv) * ivs.size()));
+  if (!ivs.empty())
+    HIP_TRY(hipMemcpyAsync(c->dec_iv.p, ivs.data(), sizeof(RstIv) * ivs.size(), hipMemcpyHostToDevice, s));
   HIP_TRY(c->ent_cf.ensure((size_t)info->coeffs_needed * sizeof(int16_t)));
   HIP_TRY(hipMemcpyAsync(c->dec_file.p, data, (size_t)len, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice, s));
@@ -1574,9 +1695,13 @@ static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfi
   HIP_TRY(hipStreamSynchronize(s));  // tabs is a stack array
   unsigned rounds = 0;
   int too_many = 0;
-  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc, 3, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p, c->dec_scr.p,
-                  (int16_t*)c->ent_cf.p, info->coeffs_needed, (uint32_t*)c->dec_st.p, s, &rounds, &too_many));
+  // (zero-fills the coefficients; with no descriptors that is all it does, and rounds stays 0)
+  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc.data(), nsc, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p,
+                  c->dec_scr.p, (int16_t*)c->ent_cf.p, info->coeffs_needed, (uint32_t*)c->dec_st.p, s, &rounds,
+                  &too_many));
   if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  HIP_TRY(launch_dec_rst((const uint8_t*)c->dec_file.p, (const RstIv*)c->dec_iv.p, (long long)ivs.size(),
+                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s));
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1701,6 +1826,68 @@ int jds_plan_entropy_decode(jds_plan* p, const uint8_t* files, int64_t stride, c
   HIP_TRY(dec_run(files, sc.data(), 3 * n, ng, max_ngrp, (const HuffDecTab*)p->dec_tab.p, p->dec_scr.p, coeffs,
                   (long long)n * p->g.cpf, status, s, &p->dec_rounds, &too_many));
   if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  return JDS_OK;
+}
+
+int jds_plan_entropy_decode_rst(jds_plan* p, int32_t interval, const uint8_t* files, int64_t stride,
+                                const uint64_t* lengths, int16_t* coeffs, uint32_t* status, void* stream) {
+  if (!p || !files || !lengths || !coeffs || !status) return fail(JDS_EINVAL, "null argument");
+  if (stride < 1) return fail(JDS_EINVAL, "stride %lld", (long long)stride);
+  int lane_max;
+  rst_constants(&lane_max);
+  if (interval == 0)
+    return fail(JDS_EINVAL, "restart interval 0: jds_plan_entropy_decode reads files without restart markers");
+  if (interval < 0 || interval > lane_max)
+    return fail(JDS_ENOTSUP, "restart interval %d: the batch decode takes 1 .. %d", interval, lane_max);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  // everything below that waits happens once per plan (and interval); a repeated call only enqueues
+  if (!p->ent_hdr.p) {
+    int rc = ent_prepare(p->g, p->mode, p->n, p->qt, p->ent, p->ent_hdr, p->ent_tab, s);
+    if (rc) return rc;
+  }
+  const int n = p->n;
+  size_t sz[8];
+  ent_sizes(p->g, n, sz);
+  const int hl0 = (int)(sz[6] / (size_t)n), hl = hl0 + 6;
+  if (!p->dec_tab.p) {
+    std::vector<uint8_t> h((size_t)hl0);
+    jds_jfif_info hi;
+    if (ent_header(p->qt, p->mode, p->g.H, p->g.W, h.data()) != hl0 ||
+        hd_parse(h.data(), hl0, &hi, true, g_err, sizeof g_err) != JDS_OK)
+      return fail(JDS_EINVAL, "entropy decode: the plan's header template does not parse");
+    HuffDecTab tabs[4];
+    for (int i = 0; i < 4; ++i)
+      if (!hi.huff[i].defined || hd_build(hi.huff[i].bits, hi.huff[i].vals, &tabs[i]) < 0)
+        return fail(JDS_EINVAL, "entropy decode: the plan's header template lacks a Huffman table");
+    HIP_TRY(p->dec_tab.ensure(sizeof tabs));
+    HIP_TRY(hipMemcpy(p->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice));
+  }
+  if (p->rst_hdr_interval != interval) {
+    std::vector<uint8_t> h((size_t)hl * (size_t)n);
+    for (int i = 0; i < n; ++i)
+      if (ent_header_rst(p->qt + 64 * i, p->mode, p->g.H, p->g.W, interval, h.data() + (size_t)hl * i) != hl)
+        return fail(JDS_EINVAL, "frame %d: baseline JPEG needs integer quantisation steps in [1, 255]", i);
+    HIP_TRY(p->rst_hdr.ensure(h.size()));
+    HIP_TRY(hipMemcpy(p->rst_hdr.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    p->rst_hdr_interval = interval;
+  }
+  RstGeo rg{};
+  rg.ri = interval;
+  rg.nblk[0] = p->g.nby * p->g.nbx;
+  rg.nblk[1] = rg.nblk[2] = p->g.ncy * p->g.ncx;
+  rg.first[0] = 0;
+  for (int k = 0; k < 3; ++k) rg.first[k + 1] = rg.first[k] + (rg.nblk[k] + interval - 1) / interval;
+  rg.off[0] = 0;
+  rg.off[1] = p->g.off_cb;
+  rg.off[2] = p->g.off_cr;
+  rg.cpf = p->g.cpf;
+  if ((long long)rg.first[3] * n > 0x7fffffffll) return fail(JDS_ENOTSUP, "batch too long for one decode");
+  HIP_TRY(p->rst_work.ensure(rst_work_bytes(n, rg)));
+  const MarkScope marks_(p, s);
+  p->dec_rounds = 0;
+  HIP_TRY(launch_dec_rst_plan(files, stride, (const unsigned long long*)lengths, (const uint8_t*)p->rst_hdr.p, hl, n, rg,
+                              p->rst_work.p, (const HuffDecTab*)p->dec_tab.p, coeffs, status, s));
   return JDS_OK;
 }
 

@@ -24,6 +24,8 @@
 //                headers (host-built template: SOI, APP0, DQT, SOF0, DHT),
 //                the three SOS markers, EOI, file length.
 //   k_ent_emit3  stuffed copy to the file (0x00 after every 0xFF).
+// With restart interval 64 a segment is a restart interval and one wave codes
+// it from start to end: k_rst_code, k_rst_fscan, k_rst_emit (further down).
 // (The rounds 1-3 multi-pass coder -- a counting walk, a block scan, a packing
 // walk with LDS atomics, per-chunk stuffing -- measured 0.54 ms per 64 x 1080p
 // against this one's 0.30, and a one-launch form with a decoupled look-back
@@ -468,14 +470,16 @@ __device__ __forceinline__ int es_ff(uint32_t v, int nbytes) {  // 0xFF bytes am
 // ES_SW), ov: its global words (slots >= ES_SW, or all slots when st is null).
 // fuse (not the scan's last segment): tailx holds the next segment's bits that
 // share this segment's final word, so that word is written whole here; Wn: the
-// scan's end bit when the next segment ends in that word.
+// scan's end bit when the next segment ends in that word.  rs: the packed words
+// the offsets count from (the scan's; a restart interval's own slot); report:
+// the scan's last segment stores the scan's length (info, scan_bits).
 __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g, int lane, bool valid, int nvalid,
                                          bool last_seg, uint32_t nb, uint32_t excl, unsigned long long pre,
                                          unsigned long long A, const uint32_t* st, const uint32_t* ov, int k,
                                          uint32_t* __restrict__ raw, unsigned long long* __restrict__ ffs,
                                          unsigned long long* __restrict__ info,
                                          unsigned long long* __restrict__ scan_bits, bool fuse, uint32_t tailx,
-                                         unsigned long long Wn) {
+                                         unsigned long long Wn, uint32_t* __restrict__ rs, bool report) {
   const unsigned long long W1 = pre + A;
   auto stw = [&](int j) -> uint32_t { return j >= k ? 0u : ((st == nullptr || j >= ES_SW) ? ov[j * 64] : st[j * 64]); };
   const unsigned long long o = pre + excl;  // the lane's first bit in the scan
@@ -506,7 +510,6 @@ __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g,
   }
   const uint32_t X1 = wave_shl1(X);
   const uint32_t in_tail = c ? ((fuse && lane == 63) ? tailx : X1) : 0u;
-  uint32_t* rs = raw + raw_base(e, q.f, q.s);
   // word indices within the scan fit 32 bits (< 2^28 words)
   const uint32_t wlast = (uint32_t)((W1 - 1ull) >> 5);
   const bool open_end = !fuse && !last_seg && (W1 & 31ull);
@@ -546,7 +549,7 @@ __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g,
   ffc = (int)wave_sum((uint32_t)ffc);
   if (lane == 0) {
     ffs[g] = (unsigned long long)ffc;
-    if (last_seg) {
+    if (last_seg && report) {
       info[2 * (q.f * 3 + q.s)] = 0ull;
       info[2 * (q.f * 3 + q.s) + 1] = W1;
       if (scan_bits) scan_bits[q.f * 3 + q.s] = W1;
@@ -679,7 +682,8 @@ __global__ void __launch_bounds__(256) k_ent_place(const EntGeo e, const int nse
     if (q.seg + 2 == q.nseg_s && sh && ((W1 + An - 1ull) >> 5) == ((W1 - 1ull) >> 5)) Wn = W1 + An;
   }
   es_place(e, q, g, lane, valid, nvalid, last_seg, nb, inc - nb, pre, A, nullptr,
-           gst + (size_t)g * ES_MAXW * 64 + lane, (int)((nb + 31u) >> 5), raw, ffs, info, scan_bits, fuse, tailx, Wn);
+           gst + (size_t)g * ES_MAXW * 64 + lane, (int)((nb + 31u) >> 5), raw, ffs, info, scan_bits, fuse, tailx, Wn,
+           raw + raw_base(e, q.f, q.s), true);
 }
 
 // One wave per segment: the bytes of the words it finalised, stuffed (0x00
@@ -772,25 +776,11 @@ __global__ void __launch_bounds__(1024) k_ent_fscan(const EntGeo e, const unsign
   }
 }
 
-__global__ void __launch_bounds__(256) k_ent_emit3(const EntGeo e, const int nseg,
-                                                   const unsigned long long* __restrict__ desc,
-                                                   const unsigned long long* __restrict__ info,
-                                                   const uint32_t* __restrict__ raw,
-                                                   const unsigned long long* __restrict__ outoff,
-                                                   uint8_t* __restrict__ out, long long stride) {
-  __shared__ uint32_t sbuf[4][(2 * EM_CHUNK + 8) / 4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int g = blockIdx.x * 4 + wv;
-  if (g >= nseg) return;
-  const EsSeg q = es_seg(e, g);
-  const unsigned long long W0 = q.seg ? desc[g - 1] : 0ull, W1 = desc[g];
-  const unsigned long long nbytes = (info[2 * (q.f * 3 + q.s) + 1] + 7) >> 3;
-  const unsigned long long fw = (W0 + 31) >> 5, lw = (W1 - 1) >> 5;
-  if (fw > lw) return;
-  const unsigned long long b0 = 4 * fw, b1 = (4 * lw + 4 < nbytes) ? 4 * lw + 4 : nbytes;
-  uint8_t* dst = out + (long long)q.f * stride + (long long)outoff[g];
-  const uint32_t* w = raw + raw_base(e, q.f, q.s);
-  uint8_t* lb = reinterpret_cast<uint8_t*>(sbuf[wv]);
+// Stuffed copy of bytes [b0, b1) of the packed words w to dst by one wave (sb:
+// the wave's LDS buffer); returns the end of what it wrote.
+__device__ __forceinline__ uint8_t* em_copy(const uint32_t* __restrict__ w, unsigned long long b0,
+                                            unsigned long long b1, uint8_t* dst, uint32_t* sb, int lane) {
+  uint8_t* lb = reinterpret_cast<uint8_t*>(sb);
   for (unsigned long long i0 = b0; i0 < b1; i0 += EM_CHUNK) {
     // lane l takes the chunk's dwords l, l + 64, l + 128, l + 192: coalesced
     // loads, and a wave's byte stores land on consecutive LDS words (16 B per
@@ -834,7 +824,7 @@ __global__ void __launch_bounds__(256) k_ent_emit3(const EntGeo e, const int nse
     for (int d = lane; d < nd; d += 64) {
       const int lo = 4 * d, hi = 4 * d + 4;
       if (lo >= sh0 && hi <= sh0 + tot) {
-        *reinterpret_cast<uint32_t*>(a0 + lo) = sbuf[wv][d];
+        *reinterpret_cast<uint32_t*>(a0 + lo) = sb[d];
       } else {
         for (int c = lo; c < hi; ++c)
           if (c >= sh0 && c < sh0 + tot) a0[c] = lb[c];
@@ -844,6 +834,195 @@ __global__ void __launch_bounds__(256) k_ent_emit3(const EntGeo e, const int nse
     asm volatile("" ::: "memory");
     dst += tot;
   }
+  return dst;
+}
+
+__global__ void __launch_bounds__(256) k_ent_emit3(const EntGeo e, const int nseg,
+                                                   const unsigned long long* __restrict__ desc,
+                                                   const unsigned long long* __restrict__ info,
+                                                   const uint32_t* __restrict__ raw,
+                                                   const unsigned long long* __restrict__ outoff,
+                                                   uint8_t* __restrict__ out, long long stride) {
+  __shared__ uint32_t sbuf[4][(2 * EM_CHUNK + 8) / 4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = blockIdx.x * 4 + wv;
+  if (g >= nseg) return;
+  const EsSeg q = es_seg(e, g);
+  const unsigned long long W0 = q.seg ? desc[g - 1] : 0ull, W1 = desc[g];
+  const unsigned long long nbytes = (info[2 * (q.f * 3 + q.s) + 1] + 7) >> 3;
+  const unsigned long long fw = (W0 + 31) >> 5, lw = (W1 - 1) >> 5;
+  if (fw > lw) return;
+  const unsigned long long b0 = 4 * fw, b1 = (4 * lw + 4 < nbytes) ? 4 * lw + 4 : nbytes;
+  uint8_t* dst = out + (long long)q.f * stride + (long long)outoff[g];
+  const uint32_t* w = raw + raw_base(e, q.f, q.s);
+  em_copy(w, b0, b1, dst, sbuf[wv], lane);
+}
+
+// ------------------------------------- restart intervals (Ri = 64) --
+//
+// With a restart interval of 64 blocks a segment IS a restart interval (T.81
+// E.1.4; DESIGN.md "Restart intervals"): its first block predicts from 0, it is
+// padded to its own byte and nothing of it shares a word with a neighbour.  So
+// one wave codes an interval from start to end in one kernel:
+//   k_rst_code   walk (es_block) and placement (es_place at bit offset 0 of the
+//                segment's own slot, as the last segment of a one-segment scan:
+//                pad bits, 0xFF count); the segment's bits.
+//   k_rst_fscan  per frame: prefix over the segments' output bytes (data bytes
+//                + 0xFF bytes + 2 for the RSTm in front of segments 1.. of a
+//                scan) -> every segment's first output byte; the header template
+//                (with DRI), the SOS markers, EOI, length, the scans' bits.
+//   k_rst_emit   RSTm, then the segment's stuffed bytes.
+// A segment's slot is RS_SLOT words of the scan's packed area: 64 blocks of at
+// most 1660 bits are exactly 3320 words, so slot seg starts where the plain
+// coder's worst case would put block 64 seg, and ent_sizes' areas carry over.
+constexpr int RS_INTERVAL = 64;
+constexpr int RS_SLOT = 64 * 1660 / 32;
+static_assert(RS_SLOT * 32 == 64 * 1660, "whole words");
+constexpr int RS_DRI = 6;  // FF DD 00 04 Ri(2)
+
+int ent_restart_interval() { return RS_INTERVAL; }
+
+__global__ void __launch_bounds__(64 * ES_WAVES) __attribute__((amdgpu_waves_per_eu(ES_WPE))) k_rst_code(
+    const EntGeo e, const int nseg, const int16_t* __restrict__ coeffs, const EsTab* __restrict__ gt,
+    uint32_t* gst, uint32_t* __restrict__ raw, unsigned long long* __restrict__ agg, uint32_t* __restrict__ badseg,
+    unsigned long long* __restrict__ ffs) {
+  __shared__ EsTab es;
+  __shared__ uint32_t stage[ES_WAVES][ES_SW > 0 ? ES_SW : 1][64];
+  __shared__ int16_t czs[ES_WAVES][ES_HI > 0 ? ES_HI : 1][64];
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(gt);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&es);
+    for (int i = threadIdx.x; i < (int)(sizeof(EsTab) / 4); i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int16_t* cz = &czs[wv][0][lane];
+  const int g = blockIdx.x * ES_WAVES + wv;
+  if (g >= nseg) return;  // (whole wave; no barrier follows)
+  const EsSeg q = es_seg(e, g);
+  const int bi = q.seg * 64 + lane;
+  const bool valid = bi < q.nbs;
+  const int nvalid = q.nbs - q.seg * 64 < 64 ? q.nbs - q.seg * 64 : 64;
+  const long long gb = (long long)q.f * e.nb + e.first[q.s] + (valid ? bi : q.nbs - 1);
+  const BlockRegs rg = load_block(coeffs + gb * 64);
+  const int dc = coef_at<0>(rg);
+  int pred = wave_shr1(dc);
+  if (lane == 0) pred = 0;  // the interval's first block: the prediction restarts
+  uint32_t* st = &stage[wv][0][lane];
+  uint32_t* ov = gst + (size_t)g * ES_MAXW * 64 + lane;
+  uint32_t nb = 0u;
+  int k = 0;
+  bool bd = false;
+  if (valid) {
+    EsStage o{st, ov};
+    nb = es_block(rg, dc - pred, es, q.s ? 1 : 0, o, bd, cz);
+    k = (int)((nb + 31u) >> 5);
+  }
+  const bool any_bad = __ballot(bd) != 0ull;
+  const uint32_t inc = wave_incl_sum(nb, lane);
+  const unsigned long long A = lane63(inc);  // (<= 64 * 1660 bits)
+  // the lane reads back its own staged words: LDS slots and, past ES_SW, its own global stores
+  es_place(e, q, g, lane, valid, nvalid, true, nb, inc - nb, 0ull, A, st, ov, k, raw, ffs, nullptr, nullptr, false, 0u,
+           0ull, raw + raw_base(e, q.f, q.s) + (long long)q.seg * RS_SLOT, false);
+  if (lane == 0) {
+    agg[g] = A;
+    badseg[g] = any_bad ? 1u : 0u;
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_rst_fscan(const EntGeo e, const unsigned long long* __restrict__ agg,
+                                                    const unsigned long long* __restrict__ ffs,
+                                                    unsigned long long* __restrict__ outoff,
+                                                    const uint8_t* __restrict__ hdr, uint8_t* __restrict__ file,
+                                                    long long stride, unsigned long long* __restrict__ lengths,
+                                                    unsigned long long* __restrict__ scan_bits,
+                                                    const uint32_t* __restrict__ badseg) {
+  __shared__ unsigned long long s_w[16], s_bits[3], s_first[3];
+  __shared__ int s_bad;
+  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int n = e.sfirst[3];
+  const long long g0 = (long long)f * n;
+  const long long hl = e.hdr + RS_DRI;
+  if (t < 3) s_bits[t] = 0ull;
+  if (t == 0) s_bad = 0;
+  __syncthreads();
+  auto scan_of = [&](int i) { return i < e.sfirst[1] ? 0 : (i < e.sfirst[2] ? 1 : 2); };
+  auto bytes_of = [&](int i) {  // the segment's output bytes, its RSTm included
+    return ((agg[g0 + i] + 7) >> 3) + ffs[g0 + i] + (i != e.sfirst[scan_of(i)] ? 2ull : 0ull);
+  };
+  const int C = (n + 1023) / 1024, i0 = t * C, i1 = min(n, i0 + C);
+  unsigned long long loc = 0ull, bits[3] = {0ull, 0ull, 0ull};
+  int b = 0;
+  for (int i = i0; i < i1; ++i) {
+    loc += bytes_of(i);
+    bits[scan_of(i)] += agg[g0 + i];
+    b |= (int)badseg[g0 + i];
+  }
+  for (int s2 = 0; s2 < 3; ++s2)
+    if (bits[s2]) atomicAdd(&s_bits[s2], bits[s2]);
+  if (b) s_bad = 1;
+  unsigned long long inc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  unsigned long long base = 0ull, all = 0ull;
+  for (int w = 0; w < 16; ++w) {
+    base += w < wv ? s_w[w] : 0ull;
+    all += s_w[w];
+  }
+  unsigned long long run = base + inc - loc;
+  for (int i = i0; i < i1; ++i) {
+    const int s2 = scan_of(i);
+    // the frame's bytes before this segment: header, the SOS of scans 0..s2, the earlier segments
+    outoff[g0 + i] = (unsigned long long)(hl + ENT_SOS * (s2 + 1)) + run;
+    if (i == e.sfirst[s2]) s_first[s2] = run;
+    run += bytes_of(i);
+  }
+  uint8_t* dst = file + (long long)f * stride;
+  for (int i = t; i < e.hdr; i += 1024) dst[i] = hdr[(long long)f * e.hdr + i];
+  if (t == 0) {
+    const uint8_t dri[RS_DRI] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(RS_INTERVAL >> 8), (uint8_t)(RS_INTERVAL & 255)};
+    for (int i = 0; i < RS_DRI; ++i) dst[e.hdr + i] = dri[i];
+  }
+  __syncthreads();
+  if (t < 3) {
+    uint8_t* m = dst + hl + ENT_SOS * t + (long long)s_first[t];
+    const uint8_t sos[ENT_SOS] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)(t + 1), (uint8_t)(t == 0 ? 0x00 : 0x11),
+                                  0x00, 0x3F, 0x00};
+    for (int i = 0; i < ENT_SOS; ++i) m[i] = sos[i];
+    if (scan_bits) scan_bits[f * 3 + t] = s_bits[t];
+  }
+  if (t == 0) {
+    const long long end = hl + 3 * ENT_SOS + (long long)all;
+    dst[end] = 0xFF;
+    dst[end + 1] = 0xD9;
+    if (lengths) lengths[f] = s_bad ? 0ull : (unsigned long long)(end + 2);  // 0: not baseline-codable
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rst_emit(const EntGeo e, const int nseg,
+                                                  const unsigned long long* __restrict__ agg,
+                                                  const uint32_t* __restrict__ raw,
+                                                  const unsigned long long* __restrict__ outoff,
+                                                  uint8_t* __restrict__ out, long long stride) {
+  __shared__ uint32_t sbuf[4][(2 * EM_CHUNK + 8) / 4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = blockIdx.x * 4 + wv;
+  if (g >= nseg) return;
+  const EsSeg q = es_seg(e, g);
+  uint8_t* dst = out + (long long)q.f * stride + (long long)outoff[g];
+  if (q.seg) {
+    if (lane == 0) {
+      dst[0] = 0xFF;
+      dst[1] = (uint8_t)(0xD0 + ((q.seg - 1) & 7));
+    }
+    dst += 2;
+  }
+  em_copy(raw + raw_base(e, q.f, q.s) + (long long)q.seg * RS_SLOT, 0ull, (agg[g] + 7) >> 3, dst, sbuf[wv], lane);
 }
 
 // ------------------------------------------------------------ driver --
@@ -945,6 +1124,56 @@ hipError_t launch_entropy(const Geo& g, int n, const int16_t* coeffs, void* cons
                           const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                           unsigned long long* scan_bits, hipStream_t s) {
   return launch_entropy_fused(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
+}
+
+// The restart header template: the plain one, then DRI.  Returns its length or -1.
+int ent_header_rst(const double* q, int mode, int H, int W, int interval, uint8_t* o) {
+  const int p = ent_header(q, mode, H, W, o);
+  if (p < 0) return -1;
+  const uint8_t dri[RS_DRI] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(interval >> 8), (uint8_t)(interval & 255)};
+  memcpy(o + p, dri, RS_DRI);
+  return p + RS_DRI;
+}
+
+// Worst-case restart file: the plain bound (header, 3 SOS, every scan at 1660
+// bits per block with all bytes stuffed, EOI) + the DRI segment + per interval
+// its 2 marker bytes and the pad byte its own byte boundary can add beyond the
+// scan's single one -- which, all pad bits being 1, can itself be an 0xFF with
+// its stuffed 0x00: 4 bytes per interval.
+long long ent_capacity_rst(const Geo& g) {
+  const EntGeo e = ent_geo(g);
+  return ent_capacity(g) + RS_DRI + 4ll * e.sfirst[3];
+}
+
+// code + place, per-frame offsets and markers, stuffing: 3 launches per batch of
+// frames, scratch as launch_entropy's (ent_sizes)
+hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
+                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
+                              unsigned long long* scan_bits, hipStream_t s) {
+  const EntGeo e = ent_geo(g);
+  const long long nseg_l = (long long)n * e.sfirst[3];
+  if (nseg_l >= (1ll << 31)) return hipErrorInvalidValue;
+  const int nseg = (int)nseg_l;
+  auto* desc = (unsigned long long*)buf[0] + 1;
+  auto* agg = desc + nseg + 1;
+  auto* outoff = agg + nseg + 1;  // (the plain path's segoff)
+  auto* badseg = (uint32_t*)(outoff + nseg + 1) + 64 * (size_t)nseg;
+  auto* ovf = (uint32_t*)buf[1];
+  auto* raw = (uint32_t*)buf[3];
+  auto* ffs = (unsigned long long*)buf[4];
+  const unsigned wg = (unsigned)((nseg + ES_WAVES - 1) / ES_WAVES);
+  const unsigned wg4 = (unsigned)((nseg + 3) / 4);
+  const EsTab* est = reinterpret_cast<const EsTab*>((const char*)tab_dev + sizeof(EntTab));
+  hipLaunchKernelGGL(k_rst_code, dim3(wg), dim3(64 * ES_WAVES), 0, s, e, nseg, coeffs, est, ovf, raw, agg, badseg, ffs);
+  kmark(s, "k_rst_code");
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(k_rst_fscan, dim3(n), dim3(1024), 0, s, e, agg, ffs, outoff, hdr_dev, out, stride, lengths,
+                     scan_bits, badseg);
+  kmark(s, "k_rst_fscan");
+  hipLaunchKernelGGL(k_rst_emit, dim3(wg4), dim3(256), 0, s, e, nseg, agg, raw, outoff, out, stride);
+  kmark(s, "k_rst_emit");
+  return hipGetLastError();
 }
 
 }  // namespace jds

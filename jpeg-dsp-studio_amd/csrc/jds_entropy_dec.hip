@@ -26,6 +26,8 @@
 //                subsequences is written by several lanes); judges the scan.
 //   k_dec_dc     per scan: the DC differences -> values (inclusive sum, judged
 //                against int16).
+// Scans with restart intervals need none of this: k_rst_scan / k_dec_rst at
+// the end of the file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -529,6 +531,274 @@ hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long lon
   hipLaunchKernelGGL(k_dec_dc, dim3(nscans), dim3(1024), 0, s, d.scans, coeffs, status);
   kmark(s, "k_dec_dc");
   return hipGetLastError();
+}
+
+// ------------------------------------------------- restart intervals --
+//
+// A scan with restart intervals (DESIGN.md "Restart intervals") is a row of
+// independent streams whose first block is known: one lane per interval
+// decodes it once with hd_rst_lane, from state (0, 0) and DC prediction 0.  No
+// synchronisation rounds, no block prefix, no scan-wide DC sum, no host read.
+//
+//   k_rst_scan  plan path, one workgroup per frame: header == the plan's
+//               restart header template; marker search (0xFF followed by
+//               neither 0x00 nor 0xFF) in file order -- every thread counts
+//               the markers of its piece of the file, a prefix over the
+//               workgroup turns the counts into ordinals; the list must read
+//               SOS, RST0, RST1, .., SOS, .., EOI with the counts the geometry
+//               requires; the frame's interval table.
+//   k_dec_rst   one lane per interval, 64 intervals per workgroup (one wave).
+//
+// Byte source of k_dec_rst: bounded global reads through a lane-private LDS
+// row (RstRowSrc).  A workgroup's intervals are contiguous in the file but of
+// unequal length -- 48 bytes for 64 zero blocks, about 1.2 KB at Q50 noise, about
+// 13 KB for 64 blocks of +-1023 -- so a staged window of the whole range fits
+// only sometimes; staging it when it fits 32 KiB measured the same as the rows
+// alone on all three probe batches and was dropped (DESIGN.md "Restart
+// intervals").  Ten global byte loads per symbol, the plain fallback, measured
+// 4.8 against 3.4 ms on the Q50 batch.  Reads never leave the interval:
+// hd_window masks what lies past its end.
+#ifndef JDS_RST_LANE_MAX
+#define JDS_RST_LANE_MAX 128  // A/B builds: tools/build_variant.py
+#endif
+constexpr int RST_LANE_MAX = JDS_RST_LANE_MAX;  // blocks of the longest interval a lane decodes (jds_entropy_restart_info)
+constexpr int RST_G = 64;                       // intervals per workgroup: one wave
+static_assert(RST_G == 64, "one wave: s_zz is filled by its 64 lanes");
+
+void rst_constants(int* lane_max) { *lane_max = RST_LANE_MAX; }
+
+// The row holds RST_ROW dwords of the interval from a dword-aligned address on;
+// a read outside it refills it (whole dwords inside the interval, single bytes
+// at its ragged ends, nothing outside), so a symbol costs LDS reads and a lane
+// waits for global memory once per row, not once per symbol.  Rows are
+// RST_ROW + 1 dwords apart: lanes reading at the same offset of their rows
+// fall on distinct banks.
+constexpr int RST_ROW = 32;
+struct RstRowSrc {
+  uint32_t* row;     // this lane's row
+  const uint8_t* d;  // the interval's bytes (global)
+  int64_t n;
+  int mis;                           // d's misalignment in memory: row dwords are aligned there
+  mutable int64_t base = 1ll << 40;  // interval byte of row dword 0 (none yet)
+  __device__ __forceinline__ uint32_t byte(int64_t i) const { return d[i]; }
+  __device__ __forceinline__ void bytes10(int64_t b, uint64_t& lo, uint64_t& hi) const {
+    if (b < base || b + 16 > base + 4 * RST_ROW) {
+      base = b - ((b + mis) & 3);
+#pragma unroll 8
+      for (int q = 0; q < RST_ROW; ++q) {
+        const int64_t g = base + 4 * q;
+        uint32_t v = 0;
+        if (g >= 0 && g + 4 <= n) {
+          v = *reinterpret_cast<const uint32_t*>(d + g);
+        } else {
+          for (int j = 0; j < 4; ++j)
+            if (g + j >= 0 && g + j < n) v |= (uint32_t)d[g + j] << (8 * j);
+        }
+        row[q] = v;
+      }
+    }
+    const int x = (int)(b - base), q = x >> 2, sh = 8 * (x & 3);  // q + 3 < RST_ROW
+    const uint64_t a = row[q] | ((uint64_t)row[q + 1] << 32), c = row[q + 2] | ((uint64_t)row[q + 3] << 32);
+    lo = sh ? (a >> sh) | (c << (64 - sh)) : a;
+    hi = c >> sh;
+  }
+};
+
+struct DecRstSink {
+  int16_t* out;
+  const uint8_t* zz;
+  int acc;
+  bool bad;
+  __device__ __forceinline__ void operator()(int64_t blk, int k, int v) {
+    if (k == 0) {
+      acc += v;
+      bad = bad || acc < -32768 || acc > 32767;
+      v = acc;
+    }
+    out[blk * 64 + zz[k]] = (int16_t)v;
+  }
+};
+
+__global__ void __launch_bounds__(RST_G) k_dec_rst(const uint8_t* __restrict__ files, const RstIv* __restrict__ ivs,
+                                                   const int niv, const HuffDecTab* __restrict__ tabs,
+                                                   int16_t* __restrict__ coeffs, uint32_t* __restrict__ status) {
+  __shared__ HuffDecTab s_tab[4];
+  __shared__ uint32_t s_row[RST_G * (RST_ROW + 1)];
+  __shared__ uint8_t s_zz[64];
+  const int t = threadIdx.x;
+  const long long i = (long long)blockIdx.x * RST_G + t;
+  {
+    constexpr int NW = (int)(4 * sizeof(HuffDecTab) / 4);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(tabs);
+    uint32_t* o = reinterpret_cast<uint32_t*>(s_tab);
+    for (int j = t; j < NW; j += RST_G) o[j] = a[j];
+  }
+  s_zz[t] = c_dec_zz[t];
+  RstIv iv{};
+  if (i < niv) iv = ivs[i];
+  __syncthreads();
+  if (iv.nblk <= 0) return;
+  DecRstSink sink{coeffs + iv.coef_off, s_zz, 0, false};
+  const uint8_t* d = files + iv.data_off;
+  uint32_t fl = hd_rst_lane(RstRowSrc{s_row + t * (RST_ROW + 1), d, iv.nbytes, (int)((uintptr_t)d & 3u)},
+                            &s_tab[iv.tabs & 255], &s_tab[(iv.tabs >> 8) & 255], 0, iv.nblk, sink);
+  if (sink.bad) fl |= HD_DC_RANGE;
+  if (fl) atomicOr(&status[iv.frame], fl);
+}
+
+// the 16 bytes of the file at [g, g + 16) (g aligned to 16 in memory) that lie in [lo, len): bit j
+// of the result is set where byte g + j is a marker's 0xFF
+__device__ __forceinline__ uint32_t rst_piece(const uint8_t* __restrict__ d, long long g, long long lo, long long len) {
+  if (g + 16 <= lo || g + 1 >= len) return 0u;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (g >= lo && g + 16 <= len) {
+    const uint4 v = *reinterpret_cast<const uint4*>(d + g);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (g + j >= lo && g + j < len) w[j >> 2] |= (uint32_t)d[g + j] << (8 * (j & 3));
+  }
+  bool ff = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t x = ~w[k];
+    ff = ff || (((x - 0x01010101u) & ~x & 0x80808080u) != 0u);
+  }
+  if (!ff) return 0u;
+  const uint32_t nx = g + 16 < len ? (uint32_t)d[g + 16] : 0u;
+  uint32_t m = 0u;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const uint32_t bj = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+    const uint32_t bn = j < 15 ? (w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu : nx;
+    if (bj == 0xFFu && bn != 0u && bn != 0xFFu && g + j >= lo && g + j + 1 < len) m |= 1u << j;
+  }
+  return m;
+}
+
+// mpos: (first[3] + 1) positions per frame; ivs: first[3] intervals per frame.
+__global__ void __launch_bounds__(1024) k_rst_scan(const uint8_t* __restrict__ files, long long stride,
+                                                   const unsigned long long* __restrict__ lengths,
+                                                   const uint8_t* __restrict__ hdr, int hl, const RstGeo rg,
+                                                   long long* __restrict__ mpos, RstIv* __restrict__ ivs,
+                                                   uint32_t* __restrict__ status) {
+  __shared__ unsigned s_w[16];
+  const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int ni = rg.first[3], nm = ni + 1;  // intervals and markers (3 SOS, the RSTm, EOI) of a frame
+  RstIv* iv = ivs + (long long)f * ni;
+  long long* mp = mpos + (long long)f * nm;
+  const unsigned long long len64 = lengths[f];
+  const uint8_t* d = files + (long long)f * stride;
+  uint32_t st = 0u;
+  if (len64 < (unsigned long long)(hl + 3 * DEC_SOS + 2) || len64 > (unsigned long long)stride) st = HD_BAD_HEADER;  // (uniform)
+  const long long len = st ? 0 : (long long)len64;
+  if (!st) {
+    int bad = 0;
+    for (int i = t; i < hl; i += 1024) bad |= d[i] != hdr[(long long)f * hl + i];
+    if (__syncthreads_or(bad)) st = HD_BAD_HEADER;
+  }
+  if (!st) {  // (uniform)
+    const long long a0 = hl - (long long)((uintptr_t)(d + hl) & 15u);
+    const long long np = (len - a0 + 15) >> 4, C = (np + 1023) / 1024;
+    const long long p0 = t * C, p1 = p0 + C < np ? p0 + C : np;
+    unsigned loc = 0u;
+    for (long long p = p0; p < p1; ++p) loc += (unsigned)__popc(rst_piece(d, a0 + 16 * p, hl, len));
+    unsigned inc = loc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned y = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    unsigned base = 0u, all = 0u;
+    for (int w = 0; w < 16; ++w) {
+      base += w < wv ? s_w[w] : 0u;
+      all += s_w[w];
+    }
+    if (all != (unsigned)nm) {
+      st = HD_RESTART;
+    } else {
+      unsigned ord = base + inc - loc;
+      for (long long p = p0; p < p1 && loc; ++p) {
+        uint32_t m = rst_piece(d, a0 + 16 * p, hl, len);
+        while (m) {
+          const int j = __builtin_ctz(m);
+          m &= m - 1u;
+          if (ord < (unsigned)nm) mp[ord] = a0 + 16 * p + j;
+          ++ord;
+        }
+      }
+      __syncthreads();  // the list (global, this workgroup's writes) is visible
+      int bad = 0;
+      for (int j = t; j < nm; j += 1024) {
+        const long long pos = mp[j];
+        if (j == ni) {
+          bad |= pos != len - 2 || d[len - 1] != 0xD9;
+          continue;
+        }
+        const int s2 = j < rg.first[1] ? 0 : (j < rg.first[2] ? 1 : 2), k = j - rg.first[s2];
+        if (k == 0) {
+          const uint8_t sos[DEC_SOS] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)(s2 + 1), (uint8_t)(s2 == 0 ? 0x00 : 0x11),
+                                        0x00, 0x3F, 0x00};
+          if (pos + DEC_SOS > mp[j + 1] || (j == 0 && pos != hl)) {
+            bad = 1;
+          } else {
+            for (int i = 0; i < DEC_SOS; ++i) bad |= d[pos + i] != sos[i];
+          }
+        } else {
+          bad |= d[pos + 1] != 0xD0 + ((k - 1) & 7);
+        }
+      }
+      if (__syncthreads_or(bad)) st = HD_RESTART;
+    }
+  }
+  for (int j = t; j < ni; j += 1024) {
+    const int s2 = j < rg.first[1] ? 0 : (j < rg.first[2] ? 1 : 2), k = j - rg.first[s2];
+    RstIv v{};
+    v.frame = f;
+    v.tabs = s2 ? (1 | (3 << 8)) : (0 | (2 << 8));
+    v.coef_off = (long long)f * rg.cpf + rg.off[s2] + 64ll * k * rg.ri;
+    if (!st) {
+      const long long a = mp[j] + (k == 0 ? DEC_SOS : 2);
+      const int rem = rg.nblk[s2] - k * rg.ri;
+      v.data_off = (long long)f * stride + a;
+      v.nbytes = (int)(mp[j + 1] - a);
+      v.nblk = rem < rg.ri ? rem : rg.ri;
+    }
+    iv[j] = v;
+  }
+  if (t == 0) status[f] = st;
+}
+
+// work of the plan path: the interval table, then the marker list
+size_t rst_work_bytes(int n, const RstGeo& rg) {
+  return (sizeof(RstIv) * (size_t)rg.first[3] + sizeof(long long) * (size_t)(rg.first[3] + 1)) * (size_t)n;
+}
+
+hipError_t launch_dec_rst(const uint8_t* files, const RstIv* ivs_dev, long long niv, const HuffDecTab* tabs_dev,
+                          int16_t* coeffs, uint32_t* status, hipStream_t s) {
+  if (niv <= 0) return hipSuccess;
+  if (niv > 0x7fffffffll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_dec_rst, dim3((unsigned)((niv + RST_G - 1) / RST_G)), dim3(RST_G), 0, s, files, ivs_dev,
+                     (int)niv, tabs_dev, coeffs, status);
+  kmark(s, "k_dec_rst");
+  return hipGetLastError();
+}
+
+// Plan path: zero-fill, scan every frame's markers, decode every interval.  Enqueues only.
+hipError_t launch_dec_rst_plan(const uint8_t* files, long long stride, const unsigned long long* lengths,
+                               const uint8_t* hdr_dev, int hl, int n, const RstGeo& rg, void* work,
+                               const HuffDecTab* tabs_dev, int16_t* coeffs, uint32_t* status, hipStream_t s) {
+  RstIv* ivs = (RstIv*)work;
+  long long* mpos = (long long*)(ivs + (size_t)rg.first[3] * (size_t)n);
+  hipError_t e = hipMemsetAsync(coeffs, 0, sizeof(int16_t) * (size_t)rg.cpf * (size_t)n, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_rst_scan, dim3(n), dim3(1024), 0, s, files, stride, lengths, hdr_dev, hl, rg, mpos, ivs, status);
+  kmark(s, "k_rst_scan");
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return launch_dec_rst(files, ivs, (long long)rg.first[3] * n, tabs_dev, coeffs, status, s);
 }
 
 }  // namespace jds

@@ -2,7 +2,8 @@
 // self-synchronising entropy decoder (jds_entropy_dec.hip; DESIGN.md "Entropy
 // decode").  Compiles for host and device: the GPU lanes, the host model behind
 // jds_selftest_huffdec and the stand-alone sanitizer program
-// (tools/jfif_host_san.cpp) run this same code.  No HIP types here.
+// (tools/jfif_host_san.cpp) run this same code.  No HIP types here.  Scans
+// with restart intervals (DRI) decode one interval per lane (hd_rst_lane).
 //
 // Stream positions are bit positions in the STUFFED scan bytes: the reader
 // skips the 0x00 after every 0xFF itself, so a position never points into a
@@ -36,7 +37,8 @@ enum : uint32_t {
   HD_K63 = JDS_DEC_K63,
   HD_OVERRUN = JDS_DEC_OVERRUN,
   HD_COUNT = JDS_DEC_COUNT,
-  HD_DC_RANGE = JDS_DEC_DC_RANGE
+  HD_DC_RANGE = JDS_DEC_DC_RANGE,
+  HD_RESTART = JDS_DEC_RESTART
 };
 
 // Decode table of one Huffman table: codes of up to 8 bits resolve through
@@ -246,13 +248,39 @@ JDS_HDI uint64_t hd_sync_lane(const Src& src, const HuffDecTab* dc, const HuffDe
   return (fl & (HD_BAD_CODE | HD_K63)) ? HD_NONE : hd_pack(p, k);
 }
 
+// The blocks are complete at position p: what follows must be the final data
+// byte's pad bits (p lies inside the source's last data byte or at its end).
+template <class Src>
+JDS_HDI bool hd_tail_ok(const Src& src, uint64_t p) {
+  const int64_t n = src.n;
+  int64_t L = n - 1;
+  if (n >= 2 && src.byte(n - 1) == 0x00 && src.byte(n - 2) == 0xFF) L = n - 2;
+  return (int64_t)p > 8 * L && (int64_t)p <= 8 * n;
+}
+
+// One restart interval, a stream of its own (T.81 E.1.4): decode from state
+// (0, 0) over the interval's stuffed bytes, nblk blocks to the sink from block
+// blk0 on (the sink sums the DC differences from 0 itself).  Judged alone: the
+// interval must hold exactly its blocks and end in its pad bits.  The GPU lane
+// (k_dec_rst) and the host model run this.
+template <class Src, class Sink>
+JDS_HDI uint32_t hd_rst_lane(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, int64_t blk0, int64_t nblk,
+                             Sink&& sink) {
+  uint64_t p = 0;
+  int k = 0;
+  int64_t blk = blk0;
+  const uint32_t fl = hd_run(src, dc, ac, p, k, (uint64_t)src.n * 8u, blk, blk0 + nblk, sink);
+  if (fl) return fl;
+  if (blk != blk0 + nblk) return HD_COUNT;
+  return hd_tail_ok(src, p) ? 0u : (uint32_t)HD_COUNT;
+}
+
 // Write pass of one subsequence, from its settled entry state and first block
 // index; judges the scan: defects of the decode, data after the last block,
 // or too few blocks (reported by the scan's last subsequence).
 template <class Src, class Sink>
 JDS_HDI uint32_t hd_write_lane(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, uint64_t entry,
                                uint64_t pend, int64_t blk0, int64_t nblocks, bool last, Sink&& sink) {
-  const int64_t n = src.n;
   if (entry == HD_NONE) return last ? HD_COUNT : 0;
   if (blk0 >= nblocks) return 0;
   uint64_t p = entry >> 8;
@@ -262,9 +290,7 @@ JDS_HDI uint32_t hd_write_lane(const Src& src, const HuffDecTab* dc, const HuffD
   if (fl) return fl;
   if (blk == nblocks) {
     // the scan is complete: what follows must be the final data byte's pad bits
-    int64_t L = n - 1;
-    if (n >= 2 && src.byte(n - 1) == 0x00 && src.byte(n - 2) == 0xFF) L = n - 2;
-    if (!((int64_t)p > 8 * L && (int64_t)p <= 8 * n)) fl |= HD_COUNT;
+    if (!hd_tail_ok(src, p)) fl |= HD_COUNT;
   } else if (last) {
     fl |= HD_COUNT;
   }
@@ -282,6 +308,27 @@ struct DecScan {
   int grp0, ngrp;      // its workgroups
   int nsub;            // its subsequences
   int pad_;
+};
+
+// One restart interval of one frame (k_dec_rst): built on the host for a
+// parsed file, on the device (k_rst_scan) for a plan's batch.  nblk == 0: not
+// decoded (its frame is skipped).
+struct RstIv {
+  long long data_off;  // the interval's stuffed bytes, from the files base
+  long long coef_off;  // its first block's first coefficient, from the coeffs base
+  int nbytes;
+  int nblk;
+  int frame;
+  int tabs;  // dc table index | ac table index << 8 (into the table array)
+};
+
+// What a plan knows about its restart files before it sees them.
+struct RstGeo {
+  int ri;           // the interval, in blocks
+  int nblk[3];      // blocks of the Y, Cb, Cr scans
+  int first[4];     // first interval of each scan within the frame; first[3]: intervals per frame
+  long long off[3];  // the scans' first coefficient within the frame
+  long long cpf;     // coefficients per frame
 };
 
 // ------------------------------------------------------------- host side --
@@ -320,7 +367,7 @@ inline int hd_block_counts(int64_t H, int64_t W, int mode, int64_t* ny, int64_t*
 }
 
 // Parse a baseline JFIF of the profile this library writes (include/jds.h:
-// jds_jfif_parse).  headers_only: stop without error where the data ends once
+// jds_jfif_parse), with or without restart intervals.  headers_only: stop without error where the data ends once
 // SOF0 and the four Huffman tables are known (the plan's header template).
 // Never reads outside [data, data + len).
 inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool headers_only, char* msg, size_t cap) {
@@ -331,6 +378,7 @@ inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool h
   bool qdef[4] = {false, false, false, false};
   int tq = -1;
   bool sof = false, seen[4] = {false, false, false, false};
+  int ri = 0;  // the restart interval in effect (DRI), 0: none
   int64_t p = 2;
   for (;;) {
     if (p + 2 > len) {
@@ -344,7 +392,8 @@ inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool h
       continue;
     }
     if (m == 0xD9) break;  // EOI
-    if (m >= 0xD0 && m <= 0xD7) return hd_fail(msg, cap, JDS_ENOTSUP, "restart markers (RST%d) are not supported", m - 0xD0);
+    if (m >= 0xD0 && m <= 0xD7)
+      return hd_fail(msg, cap, JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
     if (m == 0xD8 || m == 0x01 || m == 0x00)
       return hd_fail(msg, cap, JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
     if (p + 4 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
@@ -381,7 +430,8 @@ inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool h
       if (m == 0xCC || m >= 0xC9) return hd_fail(msg, cap, JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", m);
       return hd_fail(msg, cap, JDS_ENOTSUP, "%s (SOF%d) is not supported: baseline SOF0 only", m == 0xC2 ? "progressive JPEG" : "this frame type", m - 0xC0);
     } else if (m == 0xDD) {
-      return hd_fail(msg, cap, JDS_ENOTSUP, "restart intervals (DRI) are not supported");
+      if (ln != 4) return hd_fail(msg, cap, JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
+      ri = (s[0] << 8) | s[1];
     } else if (m == 0xDB) {
       int64_t q = 0;
       while (q < sl) {
@@ -435,20 +485,43 @@ inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool h
       if (out->n_scans >= 3) return hd_fail(msg, cap, JDS_EINVAL, "more than three scans");
       seen[comp] = true;
       int64_t e = p + 2 + ln;
-      // entropy-coded segment: up to the next marker (0xFF, then neither 0x00 nor a fill 0xFF)
+      // entropy-coded segment: up to the next marker (0xFF, then neither 0x00 nor a fill 0xFF);
+      // with a restart interval in effect its RSTm markers belong to it, m = i & 7 for the i-th
+      int64_t nm = 0;
       for (;;) {
         if (e + 1 >= len) return hd_fail(msg, cap, JDS_EINVAL, "truncated scan data: EOI missing");
         if (data[e] == 0xFF && data[e + 1] != 0x00) {
-          if (data[e + 1] >= 0xD0 && data[e + 1] <= 0xD7)
-            return hd_fail(msg, cap, JDS_ENOTSUP, "restart markers (RST%d) are not supported", data[e + 1] - 0xD0);
-          break;
+          const int r = data[e + 1] - 0xD0;
+          if (r < 0 || r > 7) break;
+          if (!ri)
+            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)",
+                           out->n_scans, r);
+          if (r != (int)(nm & 7))
+            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)",
+                           out->n_scans, r, (int)(nm & 7), ri);
+          ++nm;
+          e += 2;
+          continue;
         }
         ++e;
+      }
+      if (ri) {
+        int64_t ny = 0, nc = 0;
+        const int brc = hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, msg, cap);
+        if (brc) return brc;
+        const int64_t nb = comp == 1 ? ny : nc, need = (nb + ri - 1) / ri - 1;
+        if (nm != need)
+          return hd_fail(msg, cap, JDS_EINVAL, "scan %d: %lld restart markers where DRI %d needs %lld", out->n_scans,
+                         (long long)nm, ri, (long long)need);
+        if (data[e + 1] == 0xFF)
+          return hd_fail(msg, cap, JDS_ENOTSUP, "scan %d: fill bytes (FF FF) in scan data with a restart interval (DRI %d)",
+                         out->n_scans, ri);
       }
       jds_jfif_scan* sc = &out->scan[out->n_scans++];
       sc->component = comp;
       sc->dc_table = td;
       sc->ac_table = ta;
+      sc->restart_interval = ri;
       sc->offset = p + 2 + ln;
       sc->length = e - sc->offset;
       p = e;
@@ -474,6 +547,7 @@ inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool h
 
 inline const char* hd_status_text(uint32_t st) {
   if (st & HD_BAD_HEADER) return "header mismatch or empty file";
+  if (st & HD_RESTART) return "restart markers differ from what the geometry and the restart interval require";
   if (st & HD_BAD_CODE) return "invalid Huffman code in the scan data";
   if (st & HD_K63) return "coefficient index beyond 63 in the scan data";
   if (st & HD_OVERRUN) return "scan data overrun: the scan ends inside a symbol";
@@ -536,6 +610,45 @@ inline uint32_t hd_host_scan(const uint8_t* d, int64_t n, const HuffDecTab* dc, 
   return st;
 }
 
+// DC differences -> values inside the lane of one restart interval, judged
+// against int16 (the prediction starts from 0 at every interval).
+struct HdRstHostSink {
+  int16_t* out;
+  int32_t acc = 0;
+  bool bad = false;
+  void operator()(int64_t blk, int k, int v) {
+    if (k == 0) {
+      acc += v;
+      bad = bad || acc < -32768 || acc > 32767;
+      v = acc;
+    }
+    out[blk * 64 + HD_ZZ[k]] = (int16_t)v;
+  }
+};
+
+// One scan with restart interval ri on the host, a loop standing in for the
+// lanes of k_dec_rst: the parser checked the markers' number and order, so
+// interval i lies between markers i - 1 and i.  out: nblocks x 64, zeroed here.
+inline uint32_t hd_host_scan_rst(const uint8_t* d, int64_t n, const HuffDecTab* dc, const HuffDecTab* ac, int64_t ri,
+                                 int64_t nblocks, int16_t* out) {
+  memset(out, 0, sizeof(int16_t) * 64 * (size_t)nblocks);
+  uint32_t st = 0;
+  int64_t a = 0, blk0 = 0;
+  while (blk0 < nblocks) {
+    int64_t e = a;
+    while (e < n && !(d[e] == 0xFF && e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
+    const int64_t nb = nblocks - blk0 < ri ? nblocks - blk0 : ri;
+    HdRstHostSink sink{out};
+    st |= hd_rst_lane(HdMemSrc{d + a, e - a}, dc, ac, blk0, nb, sink);
+    if (sink.bad) st |= HD_DC_RANGE;
+    blk0 += nb;
+    if (e >= n) break;
+    a = e + 2;
+  }
+  if (blk0 < nblocks) st |= HD_RESTART;  // (the parser's marker count rules this out)
+  return st;
+}
+
 // A whole parsed file on the host (jds_selftest_huffdec, tools/jfif_host_san.cpp).
 // coeffs: info->coeffs_needed int16 in the reference layout.  rounds[3]: per
 // component (Y, Cb, Cr).
@@ -551,7 +664,12 @@ inline uint32_t hd_host_decode(const uint8_t* data, const jds_jfif_info* info, i
     const int c = sc.component - 1;
     const int64_t nb = c ? info->c_blocks : info->y_blocks;
     const int64_t off = c == 0 ? 0 : 64 * (info->y_blocks + (c - 1) * info->c_blocks);
-    st |= hd_host_scan(data + sc.offset, sc.length, &dc, &ac, S, nb, coeffs + off, rounds + c);
+    if (sc.restart_interval > 0) {  // every interval a stream of its own: no propagation rounds
+      st |= hd_host_scan_rst(data + sc.offset, sc.length, &dc, &ac, sc.restart_interval, nb, coeffs + off);
+      rounds[c] = 0;
+    } else {
+      st |= hd_host_scan(data + sc.offset, sc.length, &dc, &ac, S, nb, coeffs + off, rounds + c);
+    }
   }
   return st;
 }

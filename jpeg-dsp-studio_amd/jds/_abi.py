@@ -69,7 +69,7 @@ class KernelTime(C.Structure):
 
 class JfifScan(C.Structure):
     _fields_ = [('component', C.c_int32), ('dc_table', C.c_int32), ('ac_table', C.c_int32),
-                ('reserved', C.c_int32), ('offset', C.c_int64), ('length', C.c_int64)]
+                ('restart_interval', C.c_int32), ('offset', C.c_int64), ('length', C.c_int64)]
 
 
 class JfifHuff(C.Structure):
@@ -85,7 +85,7 @@ class JfifInfo(C.Structure):
 
 
 # frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
-DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE = 1, 2, 4, 8, 16, 32
+DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE, DEC_RESTART = 1, 2, 4, 8, 16, 32, 64
 
 
 class JDSError(RuntimeError):
@@ -135,6 +135,12 @@ _SIGS = {
     'jds_plan_entropy': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     'jds_encode_jfif': (C.c_int, [_P, C.POINTER(Params), C.c_int64, C.c_int64, _P, _P, C.c_int64,
                                   C.POINTER(C.c_int64), _P]),
+    'jds_entropy_restart_info': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'jds_plan_entropy_capacity_rst': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    'jds_plan_entropy_rst': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    'jds_encode_jfif_rst': (C.c_int, [_P, C.POINTER(Params), C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64,
+                                      C.POINTER(C.c_int64), _P]),
+    'jds_plan_entropy_decode_rst': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     'jds_jfif_parse': (C.c_int, [_P, C.c_int64, C.POINTER(JfifInfo)]),
     'jds_decode_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(JfifInfo)]),
     'jds_decompress_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(JfifInfo)]),

@@ -4,7 +4,9 @@ file (the reference itself only estimates the size,
 utils/metrics.py:51-92).  Byte-for-byte definition: oracle/jpeg_entropy.py.
 And back (jds_jfif_parse, jds_decode_jfif, jds_plan_entropy_decode): a
 baseline file of that profile -> the coefficients, by a self-synchronising
-parallel Huffman decode (DESIGN.md "Entropy decode")."""
+parallel Huffman decode (DESIGN.md "Entropy decode").  Both directions take
+restart intervals (DESIGN.md "Restart intervals"): the writer at the interval
+restart_info() reports, the decoder at any, one lane per interval in one pass."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,10 +18,19 @@ from . import _abi
 from ._abi import check, lib, make_params
 
 
+def restart_info() -> Tuple[int, int]:
+    """(the restart interval the writer supports besides 0, the largest interval the decoder
+    gives to one lane), in blocks."""
+    w, m = C.c_int32(0), C.c_int32(0)
+    check(lib().jds_entropy_restart_info(C.byref(w), C.byref(m)))
+    return int(w.value), int(m.value)
+
+
 def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarray,
-                device: int = 0) -> Tuple[bytes, List[int]]:
+                device: int = 0, restart_interval: int = 0) -> Tuple[bytes, List[int]]:
     """One frame: all_quantized_coeffs (int16, Y/Cb/Cr blocks) -> (file bytes,
-    entropy-coded bits of the Y, Cb, Cr scans)."""
+    entropy-coded bits of the Y, Cb, Cr scans).  restart_interval: 0, or restart_info()[0]
+    for a file with DRI and RSTm markers (every interval an independent stream)."""
     p = make_params(50, qtable, mode, False, np.zeros(3))
     geo = _abi.geometry(p, H, W)
     cf = np.ascontiguousarray(coeffs, dtype=np.int16).reshape(-1)
@@ -32,8 +43,12 @@ def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarra
     while True:
         out = np.empty(cap, np.uint8)
         with _abi.lease(device) as ctx:
-            rc = lib().jds_encode_jfif(ctx.handle, C.byref(p), H, W, cf.ctypes.data, out.ctypes.data,
-                                       cap, C.byref(n), bits)
+            if restart_interval:
+                rc = lib().jds_encode_jfif_rst(ctx.handle, C.byref(p), H, W, int(restart_interval), cf.ctypes.data,
+                                               out.ctypes.data, cap, C.byref(n), bits)
+            else:
+                rc = lib().jds_encode_jfif(ctx.handle, C.byref(p), H, W, cf.ctypes.data, out.ctypes.data,
+                                           cap, C.byref(n), bits)
         if rc == _abi.JDS_EINVAL and n.value > cap:
             cap = n.value
             continue
@@ -62,7 +77,8 @@ def _info_dict(info: _abi.JfifInfo) -> dict:
     return {'H': int(info.H), 'W': int(info.W), 'mode': _MODE_NAMES[info.subsampling],
             'qtable': np.ctypeslib.as_array(info.qtable).astype(np.float64).reshape(8, 8),
             'scans': [{'component': int(s.component), 'dc_table': int(s.dc_table), 'ac_table': int(s.ac_table),
-                       'offset': int(s.offset), 'length': int(s.length)} for s in info.scan[:info.n_scans]],
+                       'restart_interval': int(s.restart_interval), 'offset': int(s.offset),
+                       'length': int(s.length)} for s in info.scan[:info.n_scans]],
             'huffman': huff, 'y_blocks': int(info.y_blocks), 'c_blocks': int(info.c_blocks),
             'coeffs_needed': int(info.coeffs_needed)}
 
@@ -118,28 +134,42 @@ def bitrate_from_jfif(nbytes: int, shape) -> dict:
 
 
 class PlanEntropy:
-    """Device-resident entropy coding for a jds_plan: out[i] holds frame i's file."""
+    """Device-resident entropy coding for a jds_plan: out[i] holds frame i's file.
+    restart_interval (0, or restart_info()[0]): capacity, run and decode follow it."""
 
-    def __init__(self, plan: _abi.Plan):
+    def __init__(self, plan: _abi.Plan, restart_interval: int = 0):
         self.plan = plan
+        self.restart_interval = int(restart_interval)
         cap = C.c_int64(0)
-        check(lib().jds_plan_entropy_capacity(plan.handle, C.byref(cap)))
+        if self.restart_interval:
+            check(lib().jds_plan_entropy_capacity_rst(plan.handle, self.restart_interval, C.byref(cap)))
+        else:
+            check(lib().jds_plan_entropy_capacity(plan.handle, C.byref(cap)))
         self.capacity = int(cap.value)
 
     def run(self, coeffs_dev: int, out_dev: int, out_stride: int, lengths_dev: int, scan_bits_dev: int = 0,
             stream: int | None = None):
         if stream is None:
             stream = lib().jds_ctx_stream(self.plan.ctx.handle)
-        check(lib().jds_plan_entropy(self.plan.handle, coeffs_dev, out_dev, out_stride, lengths_dev,
-                                     scan_bits_dev or None, stream))
+        if self.restart_interval:
+            check(lib().jds_plan_entropy_rst(self.plan.handle, self.restart_interval, coeffs_dev, out_dev, out_stride,
+                                             lengths_dev, scan_bits_dev or None, stream))
+        else:
+            check(lib().jds_plan_entropy(self.plan.handle, coeffs_dev, out_dev, out_stride, lengths_dev,
+                                         scan_bits_dev or None, stream))
 
     def decode(self, files_dev: int, stride: int, lengths_dev: int, coeffs_dev: int, status_dev: int,
                stream: int | None = None):
         """jds_plan_entropy_decode: the files run() wrote (or any with the plan's header) back to
         coefficients; status_dev: one uint32 per frame (0 = decoded).  Waits for the stream
-        between propagation rounds."""
+        between propagation rounds; with a restart interval (jds_plan_entropy_decode_rst) it
+        only enqueues."""
         if stream is None:
             stream = lib().jds_ctx_stream(self.plan.ctx.handle)
+        if self.restart_interval:
+            check(lib().jds_plan_entropy_decode_rst(self.plan.handle, self.restart_interval, files_dev, stride,
+                                                    lengths_dev, coeffs_dev, status_dev, stream))
+            return
         check(lib().jds_plan_entropy_decode(self.plan.handle, files_dev, stride, lengths_dev, coeffs_dev,
                                             status_dev, stream))
 

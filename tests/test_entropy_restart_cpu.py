@@ -1,0 +1,227 @@
+"""CPU-side checks of restart intervals (no GPU): tests/restart_ref.py's files
+against libjpeg (through Pillow), the host parser's DRI / RSTm handling, the
+host model of the one-lane-per-interval decode (hd_rst_lane, the code the GPU
+lanes run) and its verdicts on defective intervals, and the parser and that
+model under AddressSanitizer / UBSan as a stand-alone program
+(tools/jfif_host_san.cpp) over truncated and mutated restart files."""
+import functools
+import io
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import restart_ref as rr
+from conftest import ROOT
+from oracle import cpu_ref
+from oracle import jpeg_entropy as je
+from test_entropy_decode_cpu import extreme_coeffs
+
+MODES = ('4:4:4', '4:2:2', '4:2:0')
+GRID_RI = (1, 7, 8, 64, 100, 65535)
+
+
+@pytest.fixture(scope='module', autouse=True)
+def built():
+    from jds import build
+    build.build()
+
+
+@functools.lru_cache(maxsize=None)
+def codec_coeffs(h, w, mode, q):
+    """(coefficients, qtable) of a random frame through the oracle codec (test_entropy_decode_cpu's codec_file)."""
+    img = cpu_ref.random_image(h, w, 3)
+    ref = cpu_ref.compress_reconstruct(img, q, 8, mode, mode != '4:4:4', metrics=False)
+    return np.asarray(ref['coeffs'], np.int16).reshape(-1), np.asarray(ref['qtable'], np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def rst_file(h, w, mode, q, ri):
+    cf, qt = codec_coeffs(h, w, mode, q)
+    return rr.encode_jfif_rst(cf, h, w, mode, qt, ri)[0]
+
+
+def plain_file(h, w, mode, q):
+    cf, qt = codec_coeffs(h, w, mode, q)
+    ny, nc = rr.counts(h, w, mode)
+    return je.encode_jfif(cf, h, w, mode, qt, ny, nc)[0]
+
+
+# -------------------------------------------------------- reference validity --
+
+@pytest.mark.parametrize('h,w,mode,q,ri', [(64, 96, '4:2:0', 50, 64), (264, 200, '4:2:2', 95, 64),
+                                           (33, 47, '4:4:4', 10, 7), (48, 40, '4:2:2', 90, 1)])
+def test_reference_files_decode_under_libjpeg_to_the_plain_files_pixels(h, w, mode, q, ri):
+    Image = pytest.importorskip('PIL.Image')
+    a = np.asarray(Image.open(io.BytesIO(rst_file(h, w, mode, q, ri))).convert('RGB'))
+    b = np.asarray(Image.open(io.BytesIO(plain_file(h, w, mode, q))).convert('RGB'))
+    assert a.shape == (h, w, 3) and np.array_equal(a, b)
+
+
+# ------------------------------------------------------------------ parser --
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('ri', GRID_RI)
+def test_parse_reports_the_interval_and_spans_the_markers(mode, ri):
+    from jds import entropy
+    h, w = 64, 96
+    cf, qt = codec_coeffs(h, w, mode, 50)
+    data = rst_file(h, w, mode, 50, ri)
+    info = entropy.parse_jfif(data)
+    ny, nc = rr.counts(h, w, mode)
+    blocks = cf.reshape(-1, 64)
+    for s, (lo, hi) in zip(info['scans'], ((0, ny), (ny, ny + nc), (ny + nc, ny + 2 * nc))):
+        assert s['restart_interval'] == ri
+        seg, _, nm = rr.encode_scan_rst(blocks[lo:hi], s['component'] > 1, ri)
+        assert nm == -(-(hi - lo) // ri) - 1
+        assert data[s['offset']:s['offset'] + s['length']] == seg
+
+
+def test_dri_between_scans_changes_the_later_scans_and_dri_0_switches_restarts_off():
+    from jds import entropy
+    h, w, mode = 64, 96, '4:2:0'
+    cf, qt = codec_coeffs(h, w, mode, 50)
+    ny, nc = rr.counts(h, w, mode)
+    b = cf.reshape(-1, 64)
+    head = je.jfif_headers(h, w, mode, qt)
+    data = (head + rr.dri(64) + je.sos(1) + rr.encode_scan_rst(b[:ny], False, 64)[0]
+            + rr.dri(5) + je.sos(2) + rr.encode_scan_rst(b[ny:ny + nc], True, 5)[0]
+            + rr.dri(0) + je.sos(3) + je.encode_scan(b[ny + nc:], True)[0] + b'\xff\xd9')
+    assert [s['restart_interval'] for s in entropy.parse_jfif(data)['scans']] == [64, 5, 0]
+    got, rounds = entropy.host_decode_jfif(data)
+    assert np.array_equal(got, cf) and rounds[:2] == [0, 0] and rounds[2] >= 1
+    plain = plain_file(h, w, mode, 50)
+    sos = plain.index(b'\xff\xda')
+    off = plain[:sos] + rr.dri(0) + plain[sos:]
+    assert [s['restart_interval'] for s in entropy.parse_jfif(off)['scans']] == [0, 0, 0]
+    assert np.array_equal(entropy.host_decode_jfif(off)[0], cf)
+
+
+# -------------------------------------------------------------- host model --
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('ri', GRID_RI)
+def test_host_model_decodes_every_interval_on_its_own(mode, ri):
+    from jds import entropy
+    cf, _ = codec_coeffs(64, 96, mode, 50)
+    got, rounds = entropy.host_decode_jfif(rst_file(64, 96, mode, 50, ri))
+    assert np.array_equal(got, cf) and rounds == [0, 0, 0]
+
+
+def test_host_model_extreme_coefficients_and_all_zero_frame():
+    from jds import entropy
+    cf = extreme_coeffs(96, 128, seed=1)
+    data = rr.encode_jfif_rst(cf, 96, 128, '4:4:4', np.ones((8, 8)), 64)[0]
+    got, rounds = entropy.host_decode_jfif(data)
+    assert np.array_equal(got, cf) and rounds == [0, 0, 0]
+    ny, nc = rr.counts(128, 256, '4:4:4')
+    z = np.zeros(64 * (ny + 2 * nc), np.int16)
+    got, rounds = entropy.host_decode_jfif(rr.encode_jfif_rst(z, 128, 256, '4:4:4', np.ones((8, 8)), 64)[0])
+    assert not got.any() and got.size == z.size and rounds == [0, 0, 0]
+
+
+# -------------------------------------------------------------- rejections --
+
+def _markers(data):
+    """Positions of the RSTm markers of the file (scan data hold no other FF Dn pairs)."""
+    return [i for i in range(len(data) - 1) if data[i] == 0xFF and 0xD0 <= data[i + 1] <= 0xD7]
+
+
+@pytest.mark.parametrize('kind', ['removed', 'duplicated', 'rst3_for_rst2', 'dri_length_6', 'rst_without_dri'])
+def test_parse_rejects_wrong_markers(kind):
+    from jds import entropy
+    data = bytearray(rst_file(64, 96, '4:4:4', 50, 8))  # 96 blocks per scan: 11 markers each
+    entropy.parse_jfif(bytes(data))
+    m = _markers(data)
+    assert len(m) == 33
+    word = 'DRI|restart'
+    if kind == 'removed':
+        del data[m[4]:m[4] + 2]
+    elif kind == 'duplicated':
+        data[m[4]:m[4]] = data[m[4]:m[4] + 2]
+    elif kind == 'rst3_for_rst2':
+        assert data[m[2] + 1] == 0xD2
+        data[m[2] + 1] = 0xD3
+    elif kind == 'dri_length_6':
+        d = data.index(b'\xff\xdd')
+        data[d:d + 6] = b'\xff\xdd\x00\x06\x00\x08\x00\x00'
+        word = 'DRI'
+    elif kind == 'rst_without_dri':
+        d = data.index(b'\xff\xdd')
+        del data[d:d + 6]
+    with pytest.raises(ValueError, match=word):
+        entropy.parse_jfif(bytes(data))
+
+
+def test_host_model_reports_defective_intervals():
+    from jds import entropy
+    h, w, mode, ri = 64, 96, '4:4:4', 8
+    cf, qt = codec_coeffs(h, w, mode, 50)
+    data = rst_file(h, w, mode, 50, ri)
+    m = _markers(data)
+    # an interval truncated by one byte: its last byte (a stuffed 0xFF's 0x00 would go with it) removed
+    cut = m[5] - 1
+    assert data[cut - 1] != 0xFF
+    with pytest.raises(ValueError, match='defective scan data'):
+        entropy.host_decode_jfif(data[:cut] + data[cut + 1:])
+    # one extra EOB-only block inside an interval of the Y scan: 9 blocks where 8 belong.  Zero
+    # blocks add 6 bits each, so some number of them must lengthen the interval by a byte; with
+    # one more byte the eighth block no longer ends in the interval's last byte.
+    blocks = cf.reshape(-1, 64)
+    ivs = rr.scan_intervals(blocks[:96], False, ri)
+    # (6 more bits fit an interval's pad bits only when it has 6 or 7 of them: the first interval
+    # that grows by a byte is taken)
+    for j in range(len(ivs)):
+        extra = np.zeros((1, 64), np.int16)
+        extra[0, 0] = blocks[j * ri + ri - 1, 0]  # DC difference 0
+        grown = je.encode_scan(np.concatenate([blocks[j * ri:(j + 1) * ri], extra]), False)[0]
+        if len(grown) > len(ivs[j][0]):
+            break
+    assert len(grown) > len(ivs[j][0])
+    y0 = data.index(je.sos(1)) + 10
+    start = y0 + sum(len(s) for s, _ in ivs[:j]) + 2 * j
+    assert data[start:start + len(ivs[j][0])] == ivs[j][0]
+    bad = data[:start] + grown + data[start + len(ivs[j][0]):]
+    entropy.parse_jfif(bad)  # the markers are still right
+    with pytest.raises(ValueError, match='defective scan data'):
+        entropy.host_decode_jfif(bad)
+
+
+# ---------------------------------------------------------- sanitizer run --
+
+def test_restart_parser_and_model_clean_under_host_sanitizers(tmp_path):
+    """tools/jfif_host_san.cpp (its own main, no HIP, nothing loaded into Python) built with
+    -fsanitize=address,undefined over valid restart files, one truncated at every length, every
+    byte of the DRI segment mutated and every marker's second byte mutated."""
+    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('clang++'), shutil.which('g++'))
+                if c and os.path.exists(c)), None)
+    assert cxx, 'no host C++ compiler'
+    exe = tmp_path / 'jfif_host_san'
+    subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    '-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'jpeg-dsp-studio_amd', 'csrc'),
+                    os.path.join(ROOT, 'tools', 'jfif_host_san.cpp'), '-o', str(exe)], check=True)
+    corpus = tmp_path / 'corpus'
+    corpus.mkdir()
+    valid = [rst_file(64, 96, '4:2:0', 50, 64), rst_file(264, 200, '4:2:2', 95, 64), rst_file(33, 47, '4:4:4', 10, 7),
+             rst_file(48, 40, '4:2:2', 90, 1), rst_file(64, 96, '4:4:4', 50, 8),
+             rr.encode_jfif_rst(extreme_coeffs(96, 128, seed=1), 96, 128, '4:4:4', np.ones((8, 8)), 64)[0]]
+    for i, d in enumerate(valid):
+        (corpus / f'valid_{i}.jpg').write_bytes(d)
+    small = rst_file(16, 24, '4:4:4', 50, 2)
+    for n in range(len(small)):
+        (corpus / f'trunc_{n}.jpg').write_bytes(small[:n])
+    base = valid[4]
+    d = base.index(b'\xff\xdd')
+    muts = [(i, v) for i in range(d, d + 6) for v in range(256)]
+    muts += [(i + 1, v) for i in _markers(base) for v in (0x00, 0xFF, 0xD9, 0xDA, base[i + 1] ^ 1, (base[i + 1] + 1) & 0xFF)]
+    for i, v in muts:
+        if v != base[i]:
+            (corpus / f'mut_{i}_{v}.jpg').write_bytes(base[:i] + bytes([v]) + base[i + 1:])
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+    r = subprocess.run([str(exe), str(corpus)], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert r.stderr == '', r.stderr[-4000:]
+    files, parsed, clean = (int(r.stdout.split()[i]) for i in (0, 2, 4))
+    assert files == len(os.listdir(corpus)) and parsed >= len(valid) and clean >= 3 * len(valid)

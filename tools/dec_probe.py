@@ -8,7 +8,14 @@ propagation rounds, so a batch is timed by a host clock around calls that end
 in a device synchronise as well as by events; per-kernel times come from the
 plan's launch marks in a run of their own.  Repetitions: at least REPS (10), and
 enough to fill WINDOW seconds (1.0) after three warm-up calls (clock ramp).
-Prints one JSON line per batch; --out FILE also writes them as a JSON list."""
+Prints one JSON line per batch; --out FILE also writes them as a JSON list.
+
+--restart: the same three batches, plain files against files with restart
+interval 64 (jds_plan_entropy_rst / jds_plan_entropy_decode_rst) in one session:
+file bytes, encode and decode ms (host clock around a synchronise, and events)
+of both, the variants alternating ROUNDS (3) times so the spread of repeated
+runs shows, and the restart kernels' times from the launch marks in a run of
+their own."""
 import json
 import os
 import sys
@@ -95,13 +102,77 @@ def probe(name, quality, zero, B, H, W, dev):
     return res
 
 
+def probe_restart(name, quality, zero, B, H, W, dev):
+    prm = _abi.make_params(quality, scale_quant_matrix(JPEG_LUMA_Q50, quality), '4:2:0', True,
+                           codec.gaussian_kernel3())
+    plan = _abi.Plan(_abi.context(0), [prm] * B, H, W)
+    s = torch.cuda.Stream(dev)
+    cf = torch.zeros((B, plan.geometry.coeffs_per_frame), dtype=torch.int16, device=dev)
+    if not zero:
+        g = torch.Generator(device=dev).manual_seed(7)
+        rgb = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device=dev, generator=g)
+        out = torch.empty_like(rgb)
+        st = torch.zeros((B, _abi.STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        plan.run(rgb.data_ptr(), out.data_ptr(), cf.data_ptr(), st.data_ptr(), 0, s.cuda_stream)
+        torch.cuda.synchronize()
+        del rgb, out
+    interval = entropy.restart_info()[0]
+    ents = {'plain': entropy.PlanEntropy(plan), 'restart': entropy.PlanEntropy(plan, interval)}
+    files = {k: torch.empty((B, e.capacity), dtype=torch.uint8, device=dev) for k, e in ents.items()}
+    lengths = {k: torch.zeros(B, dtype=torch.int64, device=dev) for k in ents}
+    cf2 = torch.empty_like(cf)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def enc(k):
+        return lambda: ents[k].run(cf.data_ptr(), files[k].data_ptr(), ents[k].capacity, lengths[k].data_ptr(), 0,
+                                   s.cuda_stream)
+
+    def dec(k):
+        return lambda: ents[k].decode(files[k].data_ptr(), ents[k].capacity, lengths[k].data_ptr(), cf2.data_ptr(),
+                                      status.data_ptr(), s.cuda_stream)
+
+    res = {'batch': name, 'frames': B, 'H': H, 'W': W, 'quality': quality, 'restart_interval': interval,
+           'restart_info': entropy.restart_info(), 'bit_exact': True}
+    runs = {f'{op}_{k}': [] for op in ('encode', 'decode') for k in ents}
+    for _ in range(int(os.environ.get('ROUNDS', '3'))):
+        for k in ents:
+            fn = enc(k)
+            host, ev = timed(fn, s, reps_for(fn, s))
+            runs[f'encode_{k}'].append({'host_clock_ms': host, 'events_ms': ev})
+        for k in ents:
+            fn = dec(k)
+            cf2.fill_(77)
+            host, ev = timed(fn, s, reps_for(fn, s))
+            runs[f'decode_{k}'].append({'host_clock_ms': host, 'events_ms': ev})
+            res['bit_exact'] = res['bit_exact'] and bool(torch.equal(cf2, cf)) and not bool(status.any())
+            res[f'rounds_{k}'] = ents[k].decode_rounds()
+    for k in ents:
+        res[f'file_bytes_{k}'] = int(lengths[k].sum())
+    res['file_bytes_overhead'] = res['file_bytes_restart'] / res['file_bytes_plain'] - 1.0
+    res['ms_per_batch'] = runs
+    res['ms_per_batch_median_events'] = {k: sorted(r['events_ms'] for r in v)[len(v) // 2] for k, v in runs.items()}
+    # the restart kernels from the plan's launch marks, in a run of their own
+    plan.profile(True)
+    kreps = 50
+    for _ in range(kreps):
+        enc('restart')()
+        dec('restart')()
+    torch.cuda.synchronize()
+    kern, span = plan.profile_read()
+    plan.profile(False)
+    res['restart_kernels_ms_per_batch'] = {k: v[0] / kreps for k, v in kern.items()}
+    plan.close()
+    return res
+
+
 def main():
     B = int(os.environ.get('FRAMES', '64'))
     H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
     dev = torch.device('cuda', 0)
     rows = []
     for name, q, zero in (('noise_q50', 50, False), ('all_zero', 50, True), ('noise_q95', 95, False)):
-        rows.append(probe(name, q, zero, B, H, W, dev))
+        rows.append((probe_restart if '--restart' in sys.argv else probe)(name, q, zero, B, H, W, dev))
         print(json.dumps(rows[-1]), flush=True)
     if '--out' in sys.argv:
         with open(sys.argv[sys.argv.index('--out') + 1], 'w') as f:

@@ -7,7 +7,8 @@
 //
 // Parses every file of DIR from an exactly-sized heap copy (so a read past the
 // end is a sanitizer report) and host-decodes the ones that parse, with each
-// subsequence size (default 64, 128, 1024).  Rejected and defective files are
+// subsequence size (default 64, 128, 1024; scans with restart intervals decode
+// one interval at a time whatever the size).  Rejected and defective files are
 // expected; the program exits 0 unless it cannot read DIR.  No HIP, no GPU.
 #include <dirent.h>
 #include <stdio.h>
