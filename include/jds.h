@@ -401,6 +401,83 @@ int jds_encode_jfif_rst(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W,
 int jds_plan_entropy_decode_rst(jds_plan* plan, int32_t interval, const uint8_t* files, int64_t stride,
                                 const uint64_t* lengths, int16_t* coeffs, uint32_t* status, void* stream);
 
+/* Baseline JPEGs from elsewhere (DESIGN.md "Interleaved scans").  The calls
+ * above read the profile this library writes; libjpeg, Pillow, cameras and
+ * browsers write another: ONE interleaved scan (Ns = 3, MCUs of Y.. Cb Cr
+ * blocks) and a quantisation table per component.  jds_jpeg_parse accepts
+ * everything jds_jfif_parse accepts and in addition
+ *   - one scan with Ns = 3 (components 1, 2, 3 in that order) instead of three
+ *     with Ns = 1; Ns = 2 and a mix of the two forms are JDS_ENOTSUP;
+ *   - up to three 8-bit quantisation tables, Tq per component;
+ *   - T.81's block grids at every size: component c has
+ *     ceil(ceil(W * Hc / Hmax) / 8) columns (rows alike); reference_grid says
+ *     whether they equal the floor-sized grids of the calls above;
+ *   - with an interleaved scan DRI counts MCUs: ceil(nMCU / Ri) - 1 markers,
+ *     RST0, RST1, .. in order.
+ * Still rejected by name: progressive, arithmetic, 12-bit, grayscale, 16-bit
+ * DQT, Huffman ids above 1, DHT redefined between scans, component ids other
+ * than 1, 2, 3, luma sampling other than 1x1, 2x1, 2x2, subsampled chroma.
+ *
+ * Coefficient layout of every decode: Y, Cb, Cr planar, each component's
+ * blocks in raster order of its T.81 grid, each block row-major;
+ * coeffs_needed = 64 * sum of the grid sizes (with reference_grid set: exactly
+ * the layout of jds_decode_jfif).  The blocks an interleaved scan carries
+ * beyond the grids (padding to whole MCUs) are decoded, count in their
+ * component's DC prediction and are dropped. */
+typedef struct {
+  int32_t n_components;       /* Ns: 3 (interleaved) or 1 */
+  int32_t component[3];       /* 1 Y, 2 Cb, 3 Cr, in scan order */
+  int32_t dc_table[3], ac_table[3]; /* Huffman table ids (0 / 1) per scan component */
+  int32_t restart_interval;   /* DRI in effect at SOS, in MCUs of this scan (Ns = 1: blocks); 0: none */
+  int64_t offset, length;     /* the entropy-coded segment, RSTm markers included */
+} jds_jpeg_scan;
+
+typedef struct {
+  int64_t H, W;
+  int32_t subsampling;        /* JDS_SS_* */
+  int32_t n_scans;            /* 1 (interleaved) or 3 */
+  int32_t interleaved;        /* 1: one scan with Ns = 3 */
+  int32_t reference_grid;     /* 1: the T.81 grids are the ones jds_jfif_parse accepts */
+  int32_t single_table;       /* 1: one quantisation table serves all three components */
+  int32_t blocks_per_mcu;     /* of the interleaved MCU: 6 (4:2:0), 4 (4:2:2), 3 (4:4:4) */
+  int32_t hs[3], vs[3];       /* sampling factors per component */
+  int32_t tq[3];              /* quantisation table id per component */
+  int64_t mcu_cols, mcu_rows; /* ceil(W / (8 Hmax)), ceil(H / (8 Vmax)) */
+  int64_t grid_cols[3], grid_rows[3]; /* T.81 block grid per component */
+  double qtable[3][64];       /* per component, row-major (de-zigzagged) */
+  jds_jpeg_scan scan[3];      /* in file order */
+  jds_jfif_huff huff[4];      /* [0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1 */
+  int64_t coeffs_needed;      /* 64 * sum of grid_cols[c] * grid_rows[c] */
+  uint32_t status;            /* jds_decode_jpeg: the frame's JDS_DEC_* bits */
+  uint32_t rounds;            /* jds_decode_jpeg: inter-workgroup propagation rounds */
+} jds_jpeg_info;
+
+/* Host only, no device access; never reads outside [data, data + len). */
+int jds_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out);
+/* One file from host memory to host coefficients (synchronous); the error
+ * contract of jds_decode_jfif.  An interleaved scan decodes through the
+ * interleaved instantiations of the same kernels: the decoder state carries
+ * the block's slot in the MCU, the tables are chosen per slot, DC differences
+ * go to a scan-order staging array and a per-component segmented sum places the
+ * values.  Restart intervals of at most lane_max_blocks blocks
+ * (Ri * blocks_per_mcu) decode one per lane, longer ones one descriptor each. */
+int jds_decode_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jpeg_info* info);
+/* jds_decompress_jfif for a file of either scan form that the plan's inverse can
+ * take: one quantisation table for all components (single_table) and the
+ * reference's block grids (reference_grid); anything else is JDS_ENOTSUP.  Such
+ * files -- a table per component, other grids -- are reconstructed stage by
+ * stage with the file's own tables (jds.codec.decompress_jpeg: jds_stage_quantize_n,
+ * jds_stage_block_dct_n, jds_stage_upsample, jds_stage_ycbcr_to_rgb), not a
+ * throughput path.  coeffs: NULL, or info->coeffs_needed entries. */
+int jds_decompress_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jpeg_info* info);
+/* Test-only: jds_decode_jpeg's algorithm on the host (see jds_selftest_huffdec).
+ * rounds_out[3]: decode rounds per scan in file order (an interleaved file has
+ * one scan; 0 for a scan with restart intervals).  No GPU. */
+int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

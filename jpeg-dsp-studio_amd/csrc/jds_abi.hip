@@ -95,7 +95,7 @@ hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* 
 void rst_constants(int* lane_max);
 size_t rst_work_bytes(int n, const RstGeo& rg);
 hipError_t launch_dec_rst(const uint8_t* files, const RstIv* ivs_dev, long long niv, const HuffDecTab* tabs_dev,
-                          int16_t* coeffs, uint32_t* status, hipStream_t s);
+                          int16_t* coeffs, uint32_t* status, hipStream_t s, const HdMcu* mcu_dev);
 hipError_t launch_dec_rst_plan(const uint8_t* files, long long stride, const unsigned long long* lengths,
                                const uint8_t* hdr_dev, int hl, int n, const RstGeo& rg, void* work,
                                const HuffDecTab* tabs_dev, int16_t* coeffs, uint32_t* status, hipStream_t s);
@@ -107,7 +107,7 @@ hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned
                           const uint8_t* hdr_dev, int hl, int n, void* work, uint32_t* status, hipStream_t s);
 hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
                    const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
-                   hipStream_t s, unsigned* rounds, int* too_many);
+                   hipStream_t s, unsigned* rounds, int* too_many, const HdMcu* mcu_dev, int16_t* dcs);
 hipError_t launch_codec16(int mode, bool pf, const Geo& g, int n, const uint8_t* rgb, uint8_t* rgb_out,
                           int16_t* coeffs, const FrameQ* fq, const double* gk, jds_frame_stats* st, double* part,
                           double* planes, bool want_sse, double* err_y, double* err_rgb, hipStream_t s,
@@ -187,6 +187,7 @@ struct jds_ctx {
   DevBuf ent[8], ent_hdr, ent_tab, ent_cf, ent_out, ent_meta;  // entropy coder (jds_encode_jfif)
   DevBuf dec_file, dec_tab, dec_scr, dec_st;  // entropy decoder (jds_decode_jfif): file, tables, scratch, status
   DevBuf dec_iv;                              // its restart interval table
+  DevBuf dec_mcu;                             // interleaved scans (jds_decode_jpeg): MCU descriptor, DC staging array
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   size_t ss_budget = 0;  // SSIM scratch budget per launch group (0: SSIM_SCRATCH; jds_ctx_set_ssim_scratch)
 };
@@ -607,6 +608,7 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->dec_scr.release();
   c->dec_st.release();
   c->dec_iv.release();
+  c->dec_mcu.release();
   c->gen_tab.release();
   c->gen_sub.release();
   c->gen_rec.release();
@@ -1698,10 +1700,10 @@ static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfi
   // (zero-fills the coefficients; with no descriptors that is all it does, and rounds stays 0)
   HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc.data(), nsc, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p,
                   c->dec_scr.p, (int16_t*)c->ent_cf.p, info->coeffs_needed, (uint32_t*)c->dec_st.p, s, &rounds,
-                  &too_many));
+                  &too_many, nullptr, nullptr));
   if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
   HIP_TRY(launch_dec_rst((const uint8_t*)c->dec_file.p, (const RstIv*)c->dec_iv.p, (long long)ivs.size(),
-                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s));
+                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s, nullptr));
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1724,6 +1726,204 @@ int jds_decode_jfif(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeff
   return JDS_OK;
 }
 
+// ------------------------------------------ files of either scan form --
+
+int jds_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out) {
+  const int rc = hd_jpeg_parse(data, len, out, g_err, sizeof g_err);
+  if (rc) return rc;
+  if (out->H * out->W > (int64_t)1 << 28)
+    return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
+  return JDS_OK;
+}
+
+int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  jds_jpeg_info info;
+  const int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  if (coeffs_cap < info.coeffs_needed)
+    return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)info.coeffs_needed);
+  int lane_max;
+  rst_constants(&lane_max);
+  const uint32_t st = hd_jpeg_host_decode(data, &info, subseq_bits, lane_max, coeffs, rounds_out);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+// Upload a parsed file with one interleaved scan and decode it into c->ent_cf.
+// Routing as decode_file_dev's: no restart interval -> one descriptor; intervals
+// of at most lane_max blocks (Ri * blocks per MCU) -> one lane of k_dec_rst
+// each; longer ones -> one descriptor each.
+static int decode_il_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
+  hipStream_t s = c->stream;
+  HuffDecTab tabs[4];
+  for (int i = 0; i < 4; ++i) {
+    memset(&tabs[i], 0, sizeof tabs[i]);
+    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0)
+      return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
+  }
+  const HdMcu m = hd_jpeg_mcu(info);
+  const jds_jpeg_scan& f = info->scan[0];
+  if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
+  const long long nblocks = (long long)m.bpm * m.mcu_cols * m.mcu_rows;
+  if (nblocks > 0x7fffffffll) return fail(JDS_ENOTSUP, "scan of %lld blocks", nblocks);
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<DecScan> sc;
+  std::vector<RstIv> ivs;
+  const long long rib = (long long)f.restart_interval * m.bpm;
+  auto descriptor = [&](long long off, long long nbytes, long long blk0, long long nb) {
+    DecScan d{};
+    d.data_off = off;
+    d.nbytes = nbytes;
+    d.coef_off = 0;
+    d.nblocks = (int)nb;
+    d.frame = 0;
+    d.blk_base = (int)blk0;
+    sc.push_back(d);
+  };
+  if (rib == 0) {
+    descriptor(f.offset, f.length, 0, nblocks);
+  } else {
+    const uint8_t* d = data + f.offset;
+    long long a = 0, blk0 = 0;
+    while (blk0 < nblocks) {
+      long long e = a;
+      while (e < f.length && !(d[e] == 0xFF && e + 1 < f.length && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
+      const long long nb = nblocks - blk0 < rib ? nblocks - blk0 : rib;
+      if (rib <= lane_max) {
+        if (e - a > 0x7fffffffll) return fail(JDS_ENOTSUP, "restart interval of %lld bytes", e - a);
+        RstIv v{};
+        v.data_off = f.offset + a;
+        v.coef_off = blk0;
+        v.nbytes = (int)(e - a);
+        v.nblk = (int)nb;
+        v.frame = 0;
+        ivs.push_back(v);
+      } else {
+        descriptor(f.offset + a, e - a, blk0, nb);
+      }
+      blk0 += nb;
+      a = e + 2;
+      if (e >= f.length && blk0 < nblocks)
+        return fail(JDS_EINVAL, "restart markers missing from the scan data (DRI %d)", f.restart_interval);
+    }
+  }
+  if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
+  const int nsc = (int)sc.size();
+  int max_ngrp = 0;
+  const long long ng = dec_layout(sc.data(), nsc, &max_ngrp);
+  if (ng < 0) return fail(JDS_ENOTSUP, "scan too long");
+  const size_t dcs_off = (sizeof(HdMcu) + 15) & ~(size_t)15;
+  HIP_TRY(c->dec_file.ensure((size_t)len));
+  HIP_TRY(c->dec_tab.ensure(sizeof tabs));
+  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, nsc)));
+  HIP_TRY(c->dec_st.ensure(16));
+  HIP_TRY(c->dec_iv.ensure(sizeof(RstIv) * ivs.size()));
+  HIP_TRY(c->dec_mcu.ensure(dcs_off + sizeof(int16_t) * (size_t)nblocks));
+  if (!ivs.empty())
+    HIP_TRY(hipMemcpyAsync(c->dec_iv.p, ivs.data(), sizeof(RstIv) * ivs.size(), hipMemcpyHostToDevice, s));
+  HIP_TRY(c->ent_cf.ensure((size_t)info->coeffs_needed * sizeof(int16_t)));
+  HIP_TRY(hipMemcpyAsync(c->dec_file.p, data, (size_t)len, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->dec_mcu.p, &m, sizeof m, hipMemcpyHostToDevice, s));
+  int16_t* dcs = (int16_t*)((char*)c->dec_mcu.p + dcs_off);
+  HIP_TRY(hipMemsetAsync(dcs, 0, sizeof(int16_t) * (size_t)nblocks, s));
+  HIP_TRY(hipMemsetAsync(c->dec_st.p, 0, 16, s));
+  HIP_TRY(hipStreamSynchronize(s));  // tabs and m are stack objects
+  unsigned rounds = 0;
+  int too_many = 0;
+  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc.data(), nsc, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p,
+                  c->dec_scr.p, (int16_t*)c->ent_cf.p, info->coeffs_needed, (uint32_t*)c->dec_st.p, s, &rounds,
+                  &too_many, (const HdMcu*)c->dec_mcu.p, dcs));
+  if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  HIP_TRY(launch_dec_rst((const uint8_t*)c->dec_file.p, (const RstIv*)c->dec_iv.p, (long long)ivs.size(),
+                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s,
+                         (const HdMcu*)c->dec_mcu.p));
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  info->status = st;
+  info->rounds = rounds;
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+// A parsed file of either scan form into c->ent_cf.
+static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
+  int rc;
+  if (info->interleaved) {
+    rc = decode_il_dev(c, data, len, info);
+  } else {
+    // three non-interleaved scans: the existing route, over the T.81 grids (a
+    // non-interleaved scan holds exactly its component's grid, T.81 A.2.2)
+    jds_jfif_info fi;
+    memset(&fi, 0, sizeof fi);
+    fi.H = info->H;
+    fi.W = info->W;
+    fi.subsampling = info->subsampling;
+    fi.n_scans = 3;
+    for (int i = 0; i < 3; ++i) {
+      const jds_jpeg_scan& f = info->scan[i];
+      fi.scan[i].component = f.component[0];
+      fi.scan[i].dc_table = f.dc_table[0];
+      fi.scan[i].ac_table = f.ac_table[0];
+      fi.scan[i].restart_interval = f.restart_interval;
+      fi.scan[i].offset = f.offset;
+      fi.scan[i].length = f.length;
+    }
+    memcpy(fi.huff, info->huff, sizeof fi.huff);
+    fi.y_blocks = info->grid_cols[0] * info->grid_rows[0];
+    fi.c_blocks = info->grid_cols[1] * info->grid_rows[1];
+    fi.coeffs_needed = info->coeffs_needed;
+    rc = decode_file_dev(c, data, len, &fi);
+    info->status = fi.status;
+    info->rounds = fi.rounds;
+  }
+  return rc;
+}
+
+int jds_decode_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jpeg_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  if (!coeffs || coeffs_cap < info->coeffs_needed)
+    return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)info->coeffs_needed);
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+static int inverse_of_decoded(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, int64_t n_coeffs,
+                              uint8_t* rgb_out, int16_t* coeffs);
+
+int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jpeg_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  if (!info->single_table || !info->reference_grid)
+    return fail(JDS_ENOTSUP, "the plan's inverse takes one quantisation table and the reference's block grids: "
+                             "%s (the per-stage calls reconstruct such a file)",
+                info->single_table ? "this size has other grids" : "the file has a table per component");
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  jds_params prm;
+  memset(&prm, 0, sizeof prm);
+  prm.block_size = 8;
+  prm.quality = 0;
+  prm.subsampling = info->subsampling;
+  memcpy(prm.qtable, info->qtable[0], sizeof prm.qtable);
+  if ((rc = check_tables(&prm))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
 int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
                         int16_t* coeffs, jds_jfif_info* info) {
   if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
@@ -1740,9 +1940,17 @@ int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* r
   if ((rc = check_tables(&prm))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = decode_file_dev(c, data, len, info))) return rc;
-  // the plan's default inverse route for this geometry and table, on zeroed statistics
+  return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
+// c->ent_cf (a decoded frame) -> rgb_out by the plan's default inverse route for
+// this geometry and table, on zeroed statistics; coeffs: NULL or n_coeffs entries.
+static int inverse_of_decoded(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, int64_t n_coeffs,
+                              uint8_t* rgb_out, int16_t* coeffs) {
+  const size_t nimg = (size_t)H * (size_t)W * 3;
+  int rc;
   jds_plan* plan = nullptr;
-  if ((rc = jds_plan_create(c, &prm, 1, info->H, info->W, &plan))) return rc;
+  if ((rc = jds_plan_create(c, prm, 1, H, W, &plan))) return rc;
   hipError_t e;
   if ((e = c->rgb.ensure(nimg)) != hipSuccess || (e = c->out.ensure(nimg)) != hipSuccess ||
       (e = c->stats.ensure(sizeof(jds_frame_stats))) != hipSuccess ||
@@ -1755,8 +1963,7 @@ int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* r
   if (rc == JDS_OK) {
     e = hipMemcpyAsync(rgb_out, c->out.p, nimg, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && coeffs)
-      e = hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
-                         c->stream);
+      e = hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)n_coeffs * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail(JDS_EHIP, "decompress: %s", hipGetErrorString(e));
   }
@@ -1824,7 +2031,7 @@ int jds_plan_entropy_decode(jds_plan* p, const uint8_t* files, int64_t stride, c
   int too_many = 0;
   p->dec_rounds = 0;
   HIP_TRY(dec_run(files, sc.data(), 3 * n, ng, max_ngrp, (const HuffDecTab*)p->dec_tab.p, p->dec_scr.p, coeffs,
-                  (long long)n * p->g.cpf, status, s, &p->dec_rounds, &too_many));
+                  (long long)n * p->g.cpf, status, s, &p->dec_rounds, &too_many, nullptr, nullptr));
   if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
   return JDS_OK;
 }

@@ -28,6 +28,15 @@
 //                against int16).
 // Scans with restart intervals need none of this: k_rst_scan / k_dec_rst at
 // the end of the file.
+//
+// Interleaved scans (jds_decode_jpeg; DESIGN.md "Interleaved scans"): k_dec_sync,
+// k_dec_write and k_dec_rst have a second instantiation, <true>, whose decoder
+// state carries the block's slot in the MCU and whose tables are chosen per slot
+// from the MCU descriptor (HdMcu, in LDS beside all four decode tables).  Its
+// write pass places blocks through hd_il_place, drops the ones that pad the
+// image to whole MCUs, and sends every DC difference to a scan-order staging
+// array; k_dec_dc_mcu sums a component's differences there and places the
+// values.  The <false> instantiations are the code described above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -284,6 +293,23 @@ __device__ __forceinline__ void load_tabs(HuffDecTab* s_tab, const HuffDecTab* _
   }
 }
 
+// all four decode tables and the MCU descriptor of an interleaved scan -> LDS
+__device__ __forceinline__ void load_il(HuffDecTab* s_tab, uint32_t* s_mcu, const HuffDecTab* __restrict__ tabs,
+                                        const HdMcu* __restrict__ mcu, int nthr) {
+  static_assert(sizeof(HdMcu) % 4 == 0, "word copy");
+  constexpr int NW = (int)(4 * sizeof(HuffDecTab) / 4), NM = (int)(sizeof(HdMcu) / 4);
+  const uint32_t* a = reinterpret_cast<const uint32_t*>(tabs);
+  const uint32_t* b = reinterpret_cast<const uint32_t*>(mcu);
+  uint32_t* o = reinterpret_cast<uint32_t*>(s_tab);
+  for (int i = threadIdx.x; i < NW; i += nthr) o[i] = a[i];
+  for (int i = threadIdx.x; i < NM; i += nthr) s_mcu[i] = b[i];
+}
+
+constexpr int MCU_W = (int)(sizeof(HdMcu) / 4);
+
+// IL: the scan is interleaved (state with slot, tables per slot from the MCU
+// descriptor `mcu`); the non-interleaved instantiation ignores `mcu`.
+template <bool IL>
 __global__ void __launch_bounds__(DEC_G) k_dec_sync(const uint8_t* __restrict__ files,
                                                     const DecScan* __restrict__ scans,
                                                     const int* __restrict__ grp_scan,
@@ -293,8 +319,10 @@ __global__ void __launch_bounds__(DEC_G) k_dec_sync(const uint8_t* __restrict__ 
                                                     unsigned* __restrict__ nblk,
                                                     const unsigned long long* __restrict__ gx_in,
                                                     unsigned long long* __restrict__ gx_out,
-                                                    unsigned* __restrict__ changed, const int round) {
-  __shared__ HuffDecTab s_tab[2];
+                                                    unsigned* __restrict__ changed, const int round,
+                                                    const HdMcu* __restrict__ mcu) {
+  __shared__ HuffDecTab s_tab[IL ? 4 : 2];
+  __shared__ __attribute__((aligned(8))) uint32_t s_mcu[IL ? MCU_W : 2];
   __shared__ uint32_t s_win[DEC_LDS];
   __shared__ unsigned long long s_exit[DEC_G];
   __shared__ int s_go;
@@ -334,12 +362,21 @@ __global__ void __launch_bounds__(DEC_G) k_dec_sync(const uint8_t* __restrict__ 
       return;
     }
   }
-  load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
+  if constexpr (IL)
+    load_il(s_tab, s_mcu, tabs, mcu, DEC_G);
+  else
+    load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
   const DecLdsSrc src = dec_stage(s_win, d, n, (long long)gl * DEC_G * (DEC_S / 8));
   __syncthreads();
   // entries 0..r of the workgroup are settled after iteration r: at most DEC_G iterations
   for (int it = 0; it <= DEC_G; ++it) {
-    if (need) ex = hd_sync_lane(src, &s_tab[0], &s_tab[1], ent, (unsigned long long)(i + 1) * DEC_S, nb);
+    if (need) {
+      if constexpr (IL)
+        ex = hd_sync_lane(src, HdIl{s_tab, reinterpret_cast<const HdMcu*>(s_mcu)}, ent,
+                          (unsigned long long)(i + 1) * DEC_S, nb);
+      else
+        ex = hd_sync_lane(src, HdPlain{&s_tab[0], &s_tab[1]}, ent, (unsigned long long)(i + 1) * DEC_S, nb);
+    }
     s_exit[t] = ex;
     __syncthreads();
     need = false;
@@ -401,29 +438,45 @@ __constant__ uint8_t c_dec_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32,
                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                                      58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
+// IL: blocks go through HdIlSink (planar placement, padding dropped, DC
+// differences to the staging array dcs); the other instantiation ignores mcu / dcs.
+template <bool IL>
 __global__ void __launch_bounds__(DEC_G) k_dec_write(const uint8_t* __restrict__ files,
                                                      const DecScan* __restrict__ scans,
                                                      const int* __restrict__ grp_scan,
                                                      const HuffDecTab* __restrict__ tabs,
                                                      const unsigned long long* __restrict__ entry,
                                                      const unsigned* __restrict__ blk0, int16_t* __restrict__ coeffs,
-                                                     uint32_t* __restrict__ status) {
-  __shared__ HuffDecTab s_tab[2];
+                                                     uint32_t* __restrict__ status, const HdMcu* __restrict__ mcu,
+                                                     int16_t* __restrict__ dcs) {
+  __shared__ HuffDecTab s_tab[IL ? 4 : 2];
+  __shared__ __attribute__((aligned(8))) uint32_t s_mcu[IL ? MCU_W : 2];
   __shared__ uint32_t s_win[DEC_LDS];
   __shared__ uint8_t s_zz[64];
   const int g = blockIdx.x, t = threadIdx.x;
   const DecScan sc = scans[grp_scan[g]];
   const long long i = (long long)(g - sc.grp0) * DEC_G + t;
   const size_t slot = (size_t)g * DEC_G + t;
-  load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
+  if constexpr (IL)
+    load_il(s_tab, s_mcu, tabs, mcu, DEC_G);
+  else
+    load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
   if (t < 64) s_zz[t] = c_dec_zz[t];
   const DecLdsSrc src = dec_stage(s_win, files + sc.data_off, sc.nbytes, (long long)(g - sc.grp0) * DEC_G * (DEC_S / 8));
   __syncthreads();
   if (i >= sc.nsub) return;
   // stores are clamped to the scan's blocks: hd_run stops at blk == nblocks
-  const uint32_t fl = hd_write_lane(src, &s_tab[0], &s_tab[1], entry[slot],
-                                    (unsigned long long)(i + 1) * DEC_S, (int64_t)blk0[slot], (int64_t)sc.nblocks,
-                                    i == sc.nsub - 1, DecSink{coeffs + sc.coef_off, s_zz});
+  uint32_t fl;
+  if constexpr (IL) {
+    // blk < nblocks keeps base + blk inside the scan's MCUs: the staging array and hd_il_place's grids
+    const HdMcu* m = reinterpret_cast<const HdMcu*>(s_mcu);
+    HdIlSink sink{m, coeffs + sc.coef_off, dcs, s_zz, (int64_t)sc.blk_base};
+    fl = hd_write_lane(src, HdIl{s_tab, m}, entry[slot], (unsigned long long)(i + 1) * DEC_S, (int64_t)blk0[slot],
+                       (int64_t)sc.nblocks, i == sc.nsub - 1, sink);
+  } else {
+    fl = hd_write_lane(src, HdPlain{&s_tab[0], &s_tab[1]}, entry[slot], (unsigned long long)(i + 1) * DEC_S,
+                       (int64_t)blk0[slot], (int64_t)sc.nblocks, i == sc.nsub - 1, DecSink{coeffs + sc.coef_off, s_zz});
+  }
   if (fl) atomicOr(&status[sc.frame], fl);
 }
 
@@ -459,6 +512,52 @@ __global__ void __launch_bounds__(1024) k_dec_dc(const DecScan* __restrict__ sca
   if (bad) atomicOr(&status[sc.frame], HD_DC_RANGE);
 }
 
+// DC differences of an interleaved scan -> values.  Grid (descriptors, 3): one
+// 1024-thread workgroup per descriptor (a scan, or one restart interval of the
+// descriptor route: the sum is segmented there) and component.  A component's
+// differences are a strided subsequence of the staging array -- hs * vs
+// consecutive entries from first[c] in every MCU, padding blocks included --
+// summed in scan order with the shape of k_dec_dc; the values of kept blocks
+// go to their planar place.
+__global__ void __launch_bounds__(1024) k_dec_dc_mcu(const DecScan* __restrict__ scans,
+                                                     const HdMcu* __restrict__ mcu, const int16_t* __restrict__ dcs,
+                                                     int16_t* __restrict__ coeffs, uint32_t* __restrict__ status) {
+  __shared__ long long s_w[16];
+  const DecScan sc = scans[blockIdx.x];
+  if (sc.nblocks == 0) return;
+  const int c = blockIdx.y;  // (uniform: the descriptor's fields below are scalar loads)
+  const int bpm = mcu->bpm, hs = mcu->hs[c], vs = mcu->vs[c], cnt = hs * vs, first = mcu->first[c];
+  const int gw = mcu->gw[c], gh = mcu->gh[c], cols = mcu->mcu_cols;
+  int16_t* cf = coeffs + sc.coef_off + mcu->off[c];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const long long n = sc.nblocks / bpm, mcu0 = sc.blk_base / bpm;  // whole MCUs
+  const long long C = (n + 1023) / 1024, i0 = t * C, i1 = min(n, i0 + C);
+  long long loc = 0;
+  for (long long i = i0; i < i1; ++i)
+    for (int j = 0; j < cnt; ++j) loc += dcs[(mcu0 + i) * bpm + first + j];
+  long long inc = loc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  long long run = inc - loc;
+  for (int w = 0; w < wv; ++w) run += s_w[w];
+  bool bad = false;
+  for (long long i = i0; i < i1; ++i) {
+    const long long my = (mcu0 + i) / cols, mx = (mcu0 + i) - my * cols;
+    for (int j = 0; j < cnt; ++j) {
+      run += dcs[(mcu0 + i) * bpm + first + j];
+      bad = bad || run < -32768 || run > 32767;
+      const long long gx = mx * hs + j % hs, gy = my * vs + j / hs;
+      if (gx < gw && gy < gh) cf[64 * (gy * gw + gx)] = (int16_t)run;
+    }
+  }
+  if (bad) atomicOr(&status[sc.frame], HD_DC_RANGE);
+}
+
 // ------------------------------------------------------------ driver --
 
 // work: dec_hdr_bytes(n) bytes of device scratch; the scans' (offset, length)
@@ -490,7 +589,7 @@ hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned
 // property of any input).  status must hold the frames' initial words.
 hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
                    const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
-                   hipStream_t s, unsigned* rounds, int* too_many) {
+                   hipStream_t s, unsigned* rounds, int* too_many, const HdMcu* mcu_dev, int16_t* dcs) {
   *rounds = 0;
   *too_many = 0;
   hipError_t e = hipMemsetAsync(coeffs, 0, sizeof(int16_t) * (size_t)n_coeffs, s);
@@ -512,9 +611,15 @@ hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long lon
       return hipSuccess;
     }
     if ((e = hipMemsetAsync(d.changed, 0, 4, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dec_sync, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
-                       d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r);
-    kmark(s, "k_dec_sync");
+    if (mcu_dev) {
+      hipLaunchKernelGGL(k_dec_sync<true>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev,
+                         d.entry, d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r, mcu_dev);
+      kmark(s, "k_dec_sync_il");
+    } else {
+      hipLaunchKernelGGL(k_dec_sync<false>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev,
+                         d.entry, d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r, mcu_dev);
+      kmark(s, "k_dec_sync");
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     unsigned ch = 0;
     if ((e = hipMemcpyAsync(&ch, d.changed, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
@@ -524,8 +629,17 @@ hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long lon
   }
   hipLaunchKernelGGL(k_dec_prefix, dim3(nscans), dim3(1024), 0, s, d.scans, d.nblk, d.blk0);
   kmark(s, "k_dec_prefix");
-  hipLaunchKernelGGL(k_dec_write, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry, d.blk0,
-                     coeffs, status);
+  if (mcu_dev) {  // an interleaved scan's descriptors (the whole scan, or its long restart intervals)
+    hipLaunchKernelGGL(k_dec_write<true>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
+                       d.blk0, coeffs, status, mcu_dev, dcs);
+    kmark(s, "k_dec_write_il");
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dec_dc_mcu, dim3(nscans, 3), dim3(1024), 0, s, d.scans, mcu_dev, dcs, coeffs, status);
+    kmark(s, "k_dec_dc_mcu");
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_dec_write<false>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
+                     d.blk0, coeffs, status, mcu_dev, dcs);
   kmark(s, "k_dec_write");
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_dec_dc, dim3(nscans), dim3(1024), 0, s, d.scans, coeffs, status);
@@ -619,10 +733,15 @@ struct DecRstSink {
   }
 };
 
+// IL: an interval is nblk / bpm MCUs of an interleaved scan from scan-order
+// block iv.coef_off on; the lane keeps three DC sums (HdIlRstSink).
+template <bool IL>
 __global__ void __launch_bounds__(RST_G) k_dec_rst(const uint8_t* __restrict__ files, const RstIv* __restrict__ ivs,
                                                    const int niv, const HuffDecTab* __restrict__ tabs,
-                                                   int16_t* __restrict__ coeffs, uint32_t* __restrict__ status) {
+                                                   int16_t* __restrict__ coeffs, uint32_t* __restrict__ status,
+                                                   const HdMcu* __restrict__ mcu) {
   __shared__ HuffDecTab s_tab[4];
+  __shared__ __attribute__((aligned(8))) uint32_t s_mcu[IL ? MCU_W : 2];
   __shared__ uint32_t s_row[RST_G * (RST_ROW + 1)];
   __shared__ uint8_t s_zz[64];
   const int t = threadIdx.x;
@@ -634,15 +753,30 @@ __global__ void __launch_bounds__(RST_G) k_dec_rst(const uint8_t* __restrict__ f
     for (int j = t; j < NW; j += RST_G) o[j] = a[j];
   }
   s_zz[t] = c_dec_zz[t];
+  if constexpr (IL) {
+    const uint32_t* b = reinterpret_cast<const uint32_t*>(mcu);
+    for (int j = t; j < MCU_W; j += RST_G) s_mcu[j] = b[j];
+  }
   RstIv iv{};
   if (i < niv) iv = ivs[i];
   __syncthreads();
   if (iv.nblk <= 0) return;
-  DecRstSink sink{coeffs + iv.coef_off, s_zz, 0, false};
   const uint8_t* d = files + iv.data_off;
-  uint32_t fl = hd_rst_lane(RstRowSrc{s_row + t * (RST_ROW + 1), d, iv.nbytes, (int)((uintptr_t)d & 3u)},
-                            &s_tab[iv.tabs & 255], &s_tab[(iv.tabs >> 8) & 255], 0, iv.nblk, sink);
-  if (sink.bad) fl |= HD_DC_RANGE;
+  const RstRowSrc src{s_row + t * (RST_ROW + 1), d, iv.nbytes, (int)((uintptr_t)d & 3u)};
+  uint32_t fl;
+  bool bad;
+  if constexpr (IL) {
+    // the host laid the intervals out inside the scan's MCUs: base + blk < its blocks
+    const HdMcu* m = reinterpret_cast<const HdMcu*>(s_mcu);
+    HdIlRstSink sink{m, coeffs, s_zz, (int64_t)iv.coef_off};
+    fl = hd_rst_lane(src, HdIl{s_tab, m}, 0, iv.nblk, sink);
+    bad = sink.bad;
+  } else {
+    DecRstSink sink{coeffs + iv.coef_off, s_zz, 0, false};
+    fl = hd_rst_lane(src, HdPlain{&s_tab[iv.tabs & 255], &s_tab[(iv.tabs >> 8) & 255]}, 0, iv.nblk, sink);
+    bad = sink.bad;
+  }
+  if (bad) fl |= HD_DC_RANGE;
   if (fl) atomicOr(&status[iv.frame], fl);
 }
 
@@ -778,12 +912,19 @@ size_t rst_work_bytes(int n, const RstGeo& rg) {
 }
 
 hipError_t launch_dec_rst(const uint8_t* files, const RstIv* ivs_dev, long long niv, const HuffDecTab* tabs_dev,
-                          int16_t* coeffs, uint32_t* status, hipStream_t s) {
+                          int16_t* coeffs, uint32_t* status, hipStream_t s, const HdMcu* mcu_dev) {
   if (niv <= 0) return hipSuccess;
   if (niv > 0x7fffffffll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_dec_rst, dim3((unsigned)((niv + RST_G - 1) / RST_G)), dim3(RST_G), 0, s, files, ivs_dev,
-                     (int)niv, tabs_dev, coeffs, status);
-  kmark(s, "k_dec_rst");
+  const dim3 grid((unsigned)((niv + RST_G - 1) / RST_G));
+  if (mcu_dev) {
+    hipLaunchKernelGGL(k_dec_rst<true>, grid, dim3(RST_G), 0, s, files, ivs_dev, (int)niv, tabs_dev, coeffs, status,
+                       mcu_dev);
+    kmark(s, "k_dec_rst_il");
+  } else {
+    hipLaunchKernelGGL(k_dec_rst<false>, grid, dim3(RST_G), 0, s, files, ivs_dev, (int)niv, tabs_dev, coeffs, status,
+                       mcu_dev);
+    kmark(s, "k_dec_rst");
+  }
   return hipGetLastError();
 }
 
@@ -798,7 +939,7 @@ hipError_t launch_dec_rst_plan(const uint8_t* files, long long stride, const uns
   hipLaunchKernelGGL(k_rst_scan, dim3(n), dim3(1024), 0, s, files, stride, lengths, hdr_dev, hl, rg, mpos, ivs, status);
   kmark(s, "k_rst_scan");
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return launch_dec_rst(files, ivs, (long long)rg.first[3] * n, tabs_dev, coeffs, status, s);
+  return launch_dec_rst(files, ivs, (long long)rg.first[3] * n, tabs_dev, coeffs, status, s, nullptr);
 }
 
 }  // namespace jds

@@ -7,9 +7,10 @@
 //
 // Stream positions are bit positions in the STUFFED scan bytes: the reader
 // skips the 0x00 after every 0xFF itself, so a position never points into a
-// stuffed byte.  A decoder state is (p, k): p the position of the next symbol,
-// k the zigzag index it belongs to (0: a DC symbol is expected), packed as
-// p << 8 | k.
+// stuffed byte.  A decoder state is (p, k, slot): p the position of the next
+// symbol, k the zigzag index it belongs to (0: a DC symbol is expected), slot
+// the block's index within its MCU (always 0 in a non-interleaved scan, whose
+// MCU is one block), packed as p << 16 | slot << 8 | k.
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>
@@ -80,7 +81,45 @@ inline int hd_build(const uint8_t* bits, const uint8_t* vals, HuffDecTab* t) {
   return k;
 }
 
-JDS_HDI uint64_t hd_pack(uint64_t p, int k) { return (p << 8) | (uint64_t)(uint32_t)k; }
+JDS_HDI uint64_t hd_pack(uint64_t p, int k, int slot = 0) {
+  return (p << 16) | ((uint64_t)(uint32_t)slot << 8) | (uint64_t)(uint32_t)k;
+}
+
+// The MCU of an interleaved scan (T.81 A.2.3) and the frame's block grids
+// (host-built; the kernels keep a copy in LDS).  Components come in frame
+// order, so a component's hs * vs slots are consecutive from first[c], in
+// raster order inside the MCU.  A block whose grid coordinates
+// (mx * hs + bx, my * vs + by) lie outside its component's T.81 grid pads the
+// image to whole MCUs: it is decoded, its DC difference counts in the
+// component's prediction, and it is not stored.
+struct HdMcu {
+  int32_t bpm;                 // blocks per MCU: 6 (4:2:0), 4 (4:2:2), 3 (4:4:4)
+  int32_t mcu_cols, mcu_rows;
+  int32_t hs[3], vs[3];        // sampling factors
+  int32_t gw[3], gh[3];        // T.81 block grid: columns, rows
+  int32_t first[3];            // a component's first slot
+  int64_t off[3];              // the first coefficient of a component's plane, from the coeffs base
+  uint8_t comp[8], bx[8], by[8];  // per slot
+  uint8_t dct[8], act[8];         // per slot: DC / AC table, indices into the four-table array
+};
+
+// Table choice per symbol.  HdPlain: one DC and one AC table, no slot (a
+// non-interleaved scan).  HdIl: by slot, from the MCU descriptor.
+struct HdPlain {
+  static constexpr bool IL = false;
+  const HuffDecTab *dc, *ac;
+  JDS_HDI const HuffDecTab* tab(bool isdc, int) const { return isdc ? dc : ac; }
+  JDS_HDI int next(int slot) const { return slot; }
+  JDS_HDI int slot_of(int64_t) const { return 0; }
+};
+struct HdIl {
+  static constexpr bool IL = true;
+  const HuffDecTab* tabs;  // [0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1
+  const HdMcu* m;
+  JDS_HDI const HuffDecTab* tab(bool isdc, int slot) const { return tabs + (isdc ? m->dct[slot] : m->act[slot]); }
+  JDS_HDI int next(int slot) const { return slot + 1 == m->bpm ? 0 : slot + 1; }
+  JDS_HDI int slot_of(int64_t blk) const { return (int)(blk % m->bpm); }
+};
 
 // A scan's stuffed bytes as the decode reads them.  A source has the scan's
 // length n, byte(i) for 0 <= i < n, and bytes10(b, lo, hi): the bytes b .. b+9
@@ -169,13 +208,15 @@ struct HdNullSink {
   JDS_HDI void operator()(int64_t, int, int) const {}
 };
 
-// Decode from (p, k) while p < pend and blk < blk_end: one symbol per
-// iteration, DC and AC through the same body.  sink(blk, k, value) receives
-// every coefficient (the DC entry is the difference).  Returns the defect bits
-// met (the decode stops there).  Reads are bounded by the source's scan.
-template <class Src, class Sink>
-JDS_HDI uint32_t hd_run(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, uint64_t& p, int& k,
-                        uint64_t pend, int64_t& blk, int64_t blk_end, Sink&& sink) {
+// Decode from (p, k, slot) while p < pend and blk < blk_end: one symbol per
+// iteration, DC and AC through the same body, the tables chosen by tc (per
+// slot in an interleaved scan; the slot advances at every block end).
+// sink(blk, k, value) receives every coefficient (the DC entry is the
+// difference).  Returns the defect bits met (the decode stops there).  Reads
+// are bounded by the source's scan.
+template <class TC, class Src, class Sink>
+JDS_HDI uint32_t hd_run(const Src& src, const TC& tc, uint64_t& p, int& k, int& slot, uint64_t pend, int64_t& blk,
+                        int64_t blk_end, Sink&& sink) {
   const uint64_t nbits = (uint64_t)src.n * 8u;
   while (p < pend && p < nbits && blk < blk_end) {
     uint64_t w;
@@ -185,7 +226,7 @@ JDS_HDI uint32_t hd_run(const Src& src, const HuffDecTab* dc, const HuffDecTab* 
     const uint32_t x = (uint32_t)((w << (24u + off)) >> 32);  // the next 32 bits
     const uint32_t v = x >> 16;
     const bool isdc = k == 0;
-    const HuffDecTab* t = isdc ? dc : ac;
+    const HuffDecTab* t = tc.tab(isdc, slot);
     uint32_t len = 0, sym = 0;
     const uint32_t e = t->lut[v >> 8];
     if (e) {
@@ -217,6 +258,7 @@ JDS_HDI uint32_t hd_run(const Src& src, const HuffDecTab* dc, const HuffDecTab* 
       } else {  // EOB
         k = 0;
         ++blk;
+        slot = tc.next(slot);
       }
     } else {
       k += (int)run;
@@ -225,6 +267,7 @@ JDS_HDI uint32_t hd_run(const Src& src, const HuffDecTab* dc, const HuffDecTab* 
       if (++k == 64) {
         k = 0;
         ++blk;
+        slot = tc.next(slot);
       }
     }
     const uint32_t used = len + size, nb = (off + used) >> 3;  // whole data bytes left behind (<= 4)
@@ -237,15 +280,14 @@ JDS_HDI uint32_t hd_run(const Src& src, const HuffDecTab* dc, const HuffDecTab* 
 // Synchronisation pass of one subsequence: decode from `entry` to the
 // subsequence's end; returns the exit state (HD_NONE after an invalid decode)
 // and the blocks completed.
-template <class Src>
-JDS_HDI uint64_t hd_sync_lane(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, uint64_t entry,
-                              uint64_t pend, uint32_t& nblk) {
-  uint64_t p = entry >> 8;
-  int k = (int)(entry & 255u);
+template <class TC, class Src>
+JDS_HDI uint64_t hd_sync_lane(const Src& src, const TC& tc, uint64_t entry, uint64_t pend, uint32_t& nblk) {
+  uint64_t p = entry >> 16;
+  int k = (int)(entry & 255u), slot = (int)((entry >> 8) & 255u);
   int64_t blk = 0;
-  const uint32_t fl = hd_run(src, dc, ac, p, k, pend, blk, (int64_t)1 << 62, HdNullSink());
+  const uint32_t fl = hd_run(src, tc, p, k, slot, pend, blk, (int64_t)1 << 62, HdNullSink());
   nblk = (uint32_t)blk;
-  return (fl & (HD_BAD_CODE | HD_K63)) ? HD_NONE : hd_pack(p, k);
+  return (fl & (HD_BAD_CODE | HD_K63)) ? HD_NONE : hd_pack(p, k, slot);
 }
 
 // The blocks are complete at position p: what follows must be the final data
@@ -259,17 +301,17 @@ JDS_HDI bool hd_tail_ok(const Src& src, uint64_t p) {
 }
 
 // One restart interval, a stream of its own (T.81 E.1.4): decode from state
-// (0, 0) over the interval's stuffed bytes, nblk blocks to the sink from block
+// (0, 0, 0) over the interval's stuffed bytes, nblk blocks to the sink from block
 // blk0 on (the sink sums the DC differences from 0 itself).  Judged alone: the
 // interval must hold exactly its blocks and end in its pad bits.  The GPU lane
-// (k_dec_rst) and the host model run this.
-template <class Src, class Sink>
-JDS_HDI uint32_t hd_rst_lane(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, int64_t blk0, int64_t nblk,
-                             Sink&& sink) {
+// (k_dec_rst) and the host model run this.  An interleaved scan's interval is
+// whole MCUs, so blk0 is a first slot.
+template <class TC, class Src, class Sink>
+JDS_HDI uint32_t hd_rst_lane(const Src& src, const TC& tc, int64_t blk0, int64_t nblk, Sink&& sink) {
   uint64_t p = 0;
-  int k = 0;
+  int k = 0, slot = 0;
   int64_t blk = blk0;
-  const uint32_t fl = hd_run(src, dc, ac, p, k, (uint64_t)src.n * 8u, blk, blk0 + nblk, sink);
+  const uint32_t fl = hd_run(src, tc, p, k, slot, (uint64_t)src.n * 8u, blk, blk0 + nblk, sink);
   if (fl) return fl;
   if (blk != blk0 + nblk) return HD_COUNT;
   return hd_tail_ok(src, p) ? 0u : (uint32_t)HD_COUNT;
@@ -277,16 +319,19 @@ JDS_HDI uint32_t hd_rst_lane(const Src& src, const HuffDecTab* dc, const HuffDec
 
 // Write pass of one subsequence, from its settled entry state and first block
 // index; judges the scan: defects of the decode, data after the last block,
-// or too few blocks (reported by the scan's last subsequence).
-template <class Src, class Sink>
-JDS_HDI uint32_t hd_write_lane(const Src& src, const HuffDecTab* dc, const HuffDecTab* ac, uint64_t entry,
-                               uint64_t pend, int64_t blk0, int64_t nblocks, bool last, Sink&& sink) {
+// or too few blocks (reported by the scan's last subsequence).  In an
+// interleaved scan the settled entry's slot must be the first block's place in
+// its MCU; in a defective scan it may not be (HD_COUNT).
+template <class TC, class Src, class Sink>
+JDS_HDI uint32_t hd_write_lane(const Src& src, const TC& tc, uint64_t entry, uint64_t pend, int64_t blk0,
+                               int64_t nblocks, bool last, Sink&& sink) {
   if (entry == HD_NONE) return last ? HD_COUNT : 0;
   if (blk0 >= nblocks) return 0;
-  uint64_t p = entry >> 8;
-  int k = (int)(entry & 255u);
+  uint64_t p = entry >> 16;
+  int k = (int)(entry & 255u), slot = (int)((entry >> 8) & 255u);
+  if (TC::IL && slot != tc.slot_of(blk0)) return HD_COUNT;
   int64_t blk = blk0;
-  uint32_t fl = hd_run(src, dc, ac, p, k, pend, blk, nblocks, sink);
+  uint32_t fl = hd_run(src, tc, p, k, slot, pend, blk, nblocks, sink);
   if (fl) return fl;
   if (blk == nblocks) {
     // the scan is complete: what follows must be the final data byte's pad bits
@@ -307,7 +352,7 @@ struct DecScan {
   int dc_tab, ac_tab;  // indices into the table array
   int grp0, ngrp;      // its workgroups
   int nsub;            // its subsequences
-  int pad_;
+  int blk_base;        // interleaved: its first block's index in the scan's block order (whole MCUs); else 0
 };
 
 // One restart interval of one frame (k_dec_rst): built on the host for a
@@ -315,7 +360,8 @@ struct DecScan {
 // decoded (its frame is skipped).
 struct RstIv {
   long long data_off;  // the interval's stuffed bytes, from the files base
-  long long coef_off;  // its first block's first coefficient, from the coeffs base
+  long long coef_off;  // its first block's first coefficient, from the coeffs base (interleaved: its first
+                       // block's index in the scan's block order)
   int nbytes;
   int nblk;
   int frame;
@@ -329,6 +375,76 @@ struct RstGeo {
   int first[4];     // first interval of each scan within the frame; first[3]: intervals per frame
   long long off[3];  // the scans' first coefficient within the frame
   long long cpf;     // coefficients per frame
+};
+
+// Where a block of an interleaved scan goes.  n: its index in the scan's block
+// order.  -> the component, and the block's first coefficient in the planar
+// layout (Y, Cb, Cr; each component's T.81 grid in raster order), or null for
+// a block that pads the image to whole MCUs.
+JDS_HDI int16_t* hd_il_place(const HdMcu* m, int16_t* coeffs, int64_t n, int& c) {
+  const int64_t mcu = n / m->bpm;
+  const int slot = (int)(n - mcu * m->bpm);
+  const int my = (int)(mcu / m->mcu_cols), mx = (int)(mcu - (int64_t)my * m->mcu_cols);
+  c = m->comp[slot];
+  const int gx = mx * m->hs[c] + m->bx[slot], gy = my * m->vs[c] + m->by[slot];
+  if (gx >= m->gw[c] || gy >= m->gh[c]) return nullptr;
+  return coeffs + m->off[c] + 64 * ((int64_t)gy * m->gw[c] + gx);
+}
+
+// Write pass of an interleaved scan: AC coefficients to their planar place
+// (dropped for padding), every DC difference, padding included, to the staging
+// array in scan order (the per-component sums run over it afterwards).  base:
+// the scan-order index of the descriptor's block 0.
+struct HdIlSink {
+  const HdMcu* m;
+  int16_t* coeffs;
+  int16_t* dcs;
+  const uint8_t* zz;
+  int64_t base;
+  int64_t cur = -1;
+  int16_t* dst = nullptr;
+  JDS_HDI void operator()(int64_t blk, int k, int v) {
+    if (k == 0) {
+      dcs[base + blk] = (int16_t)v;
+      return;
+    }
+    if (blk != cur) {
+      int c;
+      cur = blk;
+      dst = hd_il_place(m, coeffs, base + blk, c);
+    }
+    if (dst) dst[zz[k]] = (int16_t)v;
+  }
+};
+
+// One restart interval of an interleaved scan, decoded by one lane: three
+// running DC sums from 0 (padding blocks count), judged against int16; kept
+// blocks go to their planar place.
+struct HdIlRstSink {
+  const HdMcu* m;
+  int16_t* coeffs;
+  const uint8_t* zz;
+  int64_t base;
+  int64_t cur = -1;
+  int16_t* dst = nullptr;
+  int c = 0;
+  int acc0 = 0, acc1 = 0, acc2 = 0;
+  bool bad = false;
+  JDS_HDI void operator()(int64_t blk, int k, int v) {
+    if (blk != cur) {
+      cur = blk;
+      dst = hd_il_place(m, coeffs, base + blk, c);
+    }
+    if (k == 0) {
+      const int a = (c == 0 ? acc0 : (c == 1 ? acc1 : acc2)) + v;
+      acc0 = c == 0 ? a : acc0;
+      acc1 = c == 1 ? a : acc1;
+      acc2 = c == 2 ? a : acc2;
+      bad = bad || a < -32768 || a > 32767;
+      v = a;
+    }
+    if (dst) dst[zz[k]] = (int16_t)v;
+  }
 };
 
 // ------------------------------------------------------------- host side --
@@ -565,8 +681,28 @@ struct HdHostSink {
 // bits, the propagation rule of the kernels (entry[i + 1] <- exit[i], changed
 // entries decode again), block prefix, write pass, DC prefix sum.  out:
 // nblocks x 64, zeroed here.  *rounds = decode rounds run.  Returns status bits.
+template <class TC, class Sink>
+inline uint32_t hd_host_sync(const uint8_t* d, int64_t n, const TC& tc, int64_t S, int64_t nblocks, Sink&& sink,
+                             int32_t* rounds);
+
 inline uint32_t hd_host_scan(const uint8_t* d, int64_t n, const HuffDecTab* dc, const HuffDecTab* ac, int64_t S,
                              int64_t nblocks, int16_t* out, int32_t* rounds) {
+  memset(out, 0, sizeof(int16_t) * 64 * (size_t)nblocks);
+  uint32_t st = hd_host_sync(d, n, HdPlain{dc, ac}, S, nblocks, HdHostSink{out}, rounds);
+  int32_t acc = 0;
+  for (int64_t b = 0; b < nblocks; ++b) {
+    acc += out[64 * b];
+    if (acc < -32768 || acc > 32767) st |= HD_DC_RANGE;
+    out[64 * b] = (int16_t)acc;
+  }
+  return st;
+}
+
+// The rounds and the write pass of hd_host_scan for any table choice and sink
+// (the caller zeroes the output and sums the DC differences).
+template <class TC, class Sink>
+inline uint32_t hd_host_sync(const uint8_t* d, int64_t n, const TC& tc, int64_t S, int64_t nblocks, Sink&& sink,
+                             int32_t* rounds) {
   const HdMemSrc src{d, n};
   const int64_t nbits = 8 * n;
   const int64_t nsub = nbits ? (nbits + S - 1) / S : 1;
@@ -579,7 +715,7 @@ inline uint32_t hd_host_scan(const uint8_t* d, int64_t n, const HuffDecTab* dc, 
     bool any = false;
     for (int64_t i = 0; i < nsub; ++i)
       if (need[(size_t)i]) {
-        exitv[(size_t)i] = hd_sync_lane(src, dc, ac, entry[(size_t)i], (uint64_t)((i + 1) * S), nblk[(size_t)i]);
+        exitv[(size_t)i] = hd_sync_lane(src, tc, entry[(size_t)i], (uint64_t)((i + 1) * S), nblk[(size_t)i]);
         any = true;
       }
     if (!any) break;
@@ -593,19 +729,11 @@ inline uint32_t hd_host_scan(const uint8_t* d, int64_t n, const HuffDecTab* dc, 
     need[0] = 0;
   }
   *rounds = r;
-  memset(out, 0, sizeof(int16_t) * 64 * (size_t)nblocks);
   uint32_t st = 0;
   int64_t b0 = 0;
   for (int64_t i = 0; i < nsub; ++i) {
-    st |= hd_write_lane(src, dc, ac, entry[(size_t)i], (uint64_t)((i + 1) * S), b0, nblocks, i == nsub - 1,
-                        HdHostSink{out});
+    st |= hd_write_lane(src, tc, entry[(size_t)i], (uint64_t)((i + 1) * S), b0, nblocks, i == nsub - 1, sink);
     b0 += nblk[(size_t)i];
-  }
-  int32_t acc = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    acc += out[64 * b];
-    if (acc < -32768 || acc > 32767) st |= HD_DC_RANGE;
-    out[64 * b] = (int16_t)acc;
   }
   return st;
 }
@@ -639,7 +767,7 @@ inline uint32_t hd_host_scan_rst(const uint8_t* d, int64_t n, const HuffDecTab* 
     while (e < n && !(d[e] == 0xFF && e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
     const int64_t nb = nblocks - blk0 < ri ? nblocks - blk0 : ri;
     HdRstHostSink sink{out};
-    st |= hd_rst_lane(HdMemSrc{d + a, e - a}, dc, ac, blk0, nb, sink);
+    st |= hd_rst_lane(HdMemSrc{d + a, e - a}, HdPlain{dc, ac}, blk0, nb, sink);
     if (sink.bad) st |= HD_DC_RANGE;
     blk0 += nb;
     if (e >= n) break;
@@ -671,6 +799,308 @@ inline uint32_t hd_host_decode(const uint8_t* data, const jds_jfif_info* info, i
       st |= hd_host_scan(data + sc.offset, sc.length, &dc, &ac, S, nb, coeffs + off, rounds + c);
     }
   }
+  return st;
+}
+
+// --------------------------------------------------- interleaved files --
+
+// Parse a baseline JPEG of either scan form (include/jds.h: jds_jpeg_parse).
+// Never reads outside [data, data + len).
+inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, char* msg, size_t cap) {
+  if (!data || !out || len < 0) return hd_fail(msg, cap, JDS_EINVAL, "null argument");
+  memset(out, 0, sizeof *out);
+  if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return hd_fail(msg, cap, JDS_EINVAL, "not a JPEG file: SOI missing");
+  uint8_t qt[4][64];
+  bool qdef[4] = {false, false, false, false};
+  bool sof = false, seen[4] = {false, false, false, false};
+  int ri = 0;
+  int64_t p = 2;
+  for (;;) {
+    if (p + 2 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated file: EOI missing");
+    if (data[p] != 0xFF) return hd_fail(msg, cap, JDS_EINVAL, "marker expected at byte %lld", (long long)p);
+    const int m = data[p + 1];
+    if (m == 0xFF) {  // fill byte
+      ++p;
+      continue;
+    }
+    if (m == 0xD9) break;  // EOI
+    if (m >= 0xD0 && m <= 0xD7)
+      return hd_fail(msg, cap, JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
+    if (m == 0xD8 || m == 0x01 || m == 0x00)
+      return hd_fail(msg, cap, JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
+    if (p + 4 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
+    const int64_t ln = ((int64_t)data[p + 2] << 8) | data[p + 3];
+    if (ln < 2 || p + 2 + ln > len)
+      return hd_fail(msg, cap, JDS_EINVAL, "segment 0x%02X at byte %lld: length %lld reaches past the end of the file", m,
+                     (long long)p, (long long)ln);
+    const uint8_t* s = data + p + 4;
+    const int64_t sl = ln - 2;
+    if (m == 0xC0) {
+      if (sof) return hd_fail(msg, cap, JDS_EINVAL, "second SOF0");
+      if (sl < 6) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 too short");
+      if (s[0] != 8) return hd_fail(msg, cap, JDS_ENOTSUP, "sample precision %d (12-bit and other depths are not supported)", s[0]);
+      out->H = (s[1] << 8) | s[2];
+      out->W = (s[3] << 8) | s[4];
+      const int nf = s[5];
+      if (nf == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "grayscale files (one component) are not supported");
+      if (nf != 3) return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (three are supported)", nf);
+      if (sl != 6 + 3 * nf) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 length does not match its component count");
+      if (out->H < 1 || out->W < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
+      for (int c = 0; c < 3; ++c)
+        if (s[6 + 3 * c] != c + 1) return hd_fail(msg, cap, JDS_ENOTSUP, "component ids other than 1, 2, 3");
+      const int ys = s[7];
+      if (ys != 0x11 && ys != 0x21 && ys != 0x22)
+        return hd_fail(msg, cap, JDS_ENOTSUP, "luma sampling %dx%d (1x1, 2x1 and 2x2 are supported)", ys >> 4, ys & 15);
+      if (s[10] != 0x11 || s[13] != 0x11) return hd_fail(msg, cap, JDS_ENOTSUP, "subsampled or oversampled chroma factors");
+      out->subsampling = ys == 0x11 ? JDS_SS_444 : (ys == 0x21 ? JDS_SS_422 : JDS_SS_420);
+      const int hmax = ys >> 4, vmax = ys & 15;
+      for (int c = 0; c < 3; ++c) {
+        out->tq[c] = s[8 + 3 * c];
+        if (out->tq[c] > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", out->tq[c]);
+        out->hs[c] = c ? 1 : hmax;
+        out->vs[c] = c ? 1 : vmax;
+        const int64_t xc = (out->W * out->hs[c] + hmax - 1) / hmax, yc = (out->H * out->vs[c] + vmax - 1) / vmax;
+        out->grid_cols[c] = (xc + 7) / 8;
+        out->grid_rows[c] = (yc + 7) / 8;
+        out->coeffs_needed += 64 * out->grid_cols[c] * out->grid_rows[c];
+      }
+      out->single_table = out->tq[0] == out->tq[1] && out->tq[0] == out->tq[2];
+      out->blocks_per_mcu = hmax * vmax + 2;
+      out->mcu_cols = (out->W + 8 * hmax - 1) / (8 * hmax);
+      out->mcu_rows = (out->H + 8 * vmax - 1) / (8 * vmax);
+      int64_t ny = 0, nc = 0;
+      out->reference_grid = hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, nullptr, 0) == JDS_OK;
+      sof = true;
+    } else if ((m >= 0xC1 && m <= 0xCF) && m != 0xC4 && m != 0xC8) {
+      if (m == 0xCC || m >= 0xC9) return hd_fail(msg, cap, JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", m);
+      return hd_fail(msg, cap, JDS_ENOTSUP, "%s (SOF%d) is not supported: baseline SOF0 only", m == 0xC2 ? "progressive JPEG" : "this frame type", m - 0xC0);
+    } else if (m == 0xDD) {
+      if (ln != 4) return hd_fail(msg, cap, JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
+      ri = (s[0] << 8) | s[1];
+    } else if (m == 0xDB) {
+      int64_t q = 0;
+      while (q < sl) {
+        const int pq = s[q] >> 4, id = s[q] & 15;
+        if (pq == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "16-bit DQT is not supported");
+        if (pq != 0 || id > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DQT table header 0x%02X", s[q]);
+        if (q + 65 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DQT");
+        memcpy(qt[id], s + q + 1, 64);
+        qdef[id] = true;
+        q += 65;
+      }
+    } else if (m == 0xC4) {
+      int64_t q = 0;
+      while (q < sl) {
+        if (q + 17 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
+        const int tc = s[q] >> 4, th = s[q] & 15;
+        if (tc > 1 || th > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DHT table header 0x%02X", s[q]);
+        if (th > 1) return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table id %d (baseline has 0 and 1)", th);
+        int nv = 0;
+        for (int i = 0; i < 16; ++i) nv += s[q + 1 + i];
+        if (nv > 256) return hd_fail(msg, cap, JDS_EINVAL, "DHT: BITS sum to %d symbols (more than 256)", nv);
+        if (q + 17 + nv > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
+        jds_jfif_huff* h = &out->huff[2 * tc + th];
+        if (out->n_scans && h->defined)
+          return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table redefined between scans");
+        memset(h, 0, sizeof *h);
+        memcpy(h->bits, s + q + 1, 16);
+        memcpy(h->vals, s + q + 17, (size_t)nv);
+        h->n_vals = nv;
+        HuffDecTab t;
+        if (hd_build(h->bits, h->vals, &t) < 0)
+          return hd_fail(msg, cap, JDS_EINVAL, "DHT %d/%d: BITS over-subscribe the code space", tc, th);
+        h->defined = 1;
+        q += 17 + nv;
+      }
+    } else if (m == 0xDA) {
+      if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
+      if (sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
+      const int ns = s[0];
+      if (ns == 2)
+        return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan of two components (Ns = 2): one scan of three or three of one only");
+      if (ns != 1 && ns != 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS with %d components", ns);
+      if (sl != 4 + 2 * ns) return hd_fail(msg, cap, JDS_EINVAL, "SOS length does not match its component count");
+      if (out->interleaved || (ns == 3 && out->n_scans))
+        return hd_fail(msg, cap, JDS_ENOTSUP, "a mix of interleaved and non-interleaved scans");
+      if (out->n_scans >= 3) return hd_fail(msg, cap, JDS_EINVAL, "more than three scans");
+      jds_jpeg_scan* sc = &out->scan[out->n_scans];
+      memset(sc, 0, sizeof *sc);
+      for (int i = 0; i < ns; ++i) {
+        const int comp = s[1 + 2 * i], td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
+        if (comp < 1 || comp > 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d", comp);
+        if (ns == 3 && comp != i + 1)
+          return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan whose components are not 1, 2, 3 in that order");
+        if (seen[comp]) return hd_fail(msg, cap, JDS_ENOTSUP, "component %d has a second scan", comp);
+        if (td > 1 || ta > 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS table ids %d/%d", td, ta);
+        if (!out->huff[td].defined || !out->huff[2 + ta].defined)
+          return hd_fail(msg, cap, JDS_EINVAL, "SOS refers to a Huffman table the file has not defined");
+        if (!qdef[out->tq[comp - 1]])
+          return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", out->tq[comp - 1]);
+        seen[comp] = true;
+        sc->component[i] = comp;
+        sc->dc_table[i] = td;
+        sc->ac_table[i] = ta;
+      }
+      const uint8_t* t = s + 1 + 2 * ns;
+      if (t[0] != 0 || t[1] != 63 || t[2] != 0)
+        return hd_fail(msg, cap, JDS_ENOTSUP, "spectral selection / successive approximation (progressive scan parameters)");
+      int64_t e = p + 2 + ln;
+      int64_t nm = 0;
+      for (;;) {
+        if (e + 1 >= len) return hd_fail(msg, cap, JDS_EINVAL, "truncated scan data: EOI missing");
+        if (data[e] == 0xFF && data[e + 1] != 0x00) {
+          const int r = data[e + 1] - 0xD0;
+          if (r < 0 || r > 7) break;
+          if (!ri)
+            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)",
+                           out->n_scans, r);
+          if (r != (int)(nm & 7))
+            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)",
+                           out->n_scans, r, (int)(nm & 7), ri);
+          ++nm;
+          e += 2;
+          continue;
+        }
+        ++e;
+      }
+      if (ri) {
+        const int c0 = sc->component[0] - 1;
+        const int64_t nmcu = ns == 3 ? out->mcu_cols * out->mcu_rows : out->grid_cols[c0] * out->grid_rows[c0];
+        const int64_t need = (nmcu + ri - 1) / ri - 1;
+        if (nm != need)
+          return hd_fail(msg, cap, JDS_EINVAL, "scan %d: %lld restart markers where DRI %d needs %lld", out->n_scans,
+                         (long long)nm, ri, (long long)need);
+        if (data[e + 1] == 0xFF)
+          return hd_fail(msg, cap, JDS_ENOTSUP, "scan %d: fill bytes (FF FF) in scan data with a restart interval (DRI %d)",
+                         out->n_scans, ri);
+      }
+      sc->n_components = ns;
+      sc->restart_interval = ri;
+      sc->offset = p + 2 + ln;
+      sc->length = e - sc->offset;
+      out->interleaved = ns == 3;
+      ++out->n_scans;
+      p = e;
+      continue;
+    }
+    // APPn, COM and anything else with a length: skipped
+    p += 2 + ln;
+  }
+  if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
+  if (out->n_scans != (out->interleaved ? 1 : 3))
+    return hd_fail(msg, cap, JDS_EINVAL, "%d scans (one interleaved scan or one per component expected)", out->n_scans);
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < 64; ++k) out->qtable[c][HD_ZZ[k]] = (double)qt[out->tq[c]][k];
+  return JDS_OK;
+}
+
+// The MCU descriptor of a parsed file's interleaved scan.
+inline HdMcu hd_jpeg_mcu(const jds_jpeg_info* info) {
+  HdMcu m;
+  memset(&m, 0, sizeof m);
+  m.bpm = info->blocks_per_mcu;
+  m.mcu_cols = (int32_t)info->mcu_cols;
+  m.mcu_rows = (int32_t)info->mcu_rows;
+  int slot = 0;
+  int64_t off = 0;
+  for (int c = 0; c < 3; ++c) {
+    m.hs[c] = info->hs[c];
+    m.vs[c] = info->vs[c];
+    m.gw[c] = (int32_t)info->grid_cols[c];
+    m.gh[c] = (int32_t)info->grid_rows[c];
+    m.first[c] = slot;
+    m.off[c] = off;
+    off += 64 * info->grid_cols[c] * info->grid_rows[c];
+    for (int j = 0; j < m.hs[c] * m.vs[c]; ++j, ++slot) {
+      m.comp[slot] = (uint8_t)c;
+      m.bx[slot] = (uint8_t)(j % m.hs[c]);
+      m.by[slot] = (uint8_t)(j / m.hs[c]);
+      m.dct[slot] = (uint8_t)info->scan[0].dc_table[c];
+      m.act[slot] = (uint8_t)(2 + info->scan[0].ac_table[c]);
+    }
+  }
+  return m;
+}
+
+// DC differences of an interleaved scan -> values (the host's k_dec_dc_mcu):
+// per component a running sum over the staging array in scan order, padding
+// blocks included, from 0 at blocks [b0, b1) (whole MCUs: a scan, or one
+// restart interval); kept blocks get their value.
+inline uint32_t hd_host_dc_mcu(const HdMcu* m, const int16_t* dcs, int64_t b0, int64_t b1, int16_t* coeffs) {
+  int32_t acc[3] = {0, 0, 0};
+  uint32_t st = 0;
+  for (int64_t n = b0; n < b1; ++n) {
+    int c;
+    int16_t* dst = hd_il_place(m, coeffs, n, c);
+    acc[c] += dcs[n];
+    if (acc[c] < -32768 || acc[c] > 32767) st |= HD_DC_RANGE;
+    if (dst) dst[0] = (int16_t)acc[c];
+  }
+  return st;
+}
+
+// A whole parsed file on the host (jds_selftest_jpegdec, tools/jfif_host_san.cpp):
+// non-interleaved scans as hd_host_decode over the T.81 grids, an interleaved
+// one with the lanes' rules: intervals of at most lane_max blocks one lane
+// each, longer ones (and a scan without intervals) through the rounds.
+// coeffs: info->coeffs_needed int16.  rounds[3]: per scan in file order.
+inline uint32_t hd_jpeg_host_decode(const uint8_t* data, const jds_jpeg_info* info, int64_t S, int64_t lane_max,
+                                    int16_t* coeffs, int32_t* rounds) {
+  uint32_t st = 0;
+  HuffDecTab tabs[4];
+  for (int i = 0; i < 4; ++i) {
+    memset(&tabs[i], 0, sizeof tabs[i]);
+    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0) return HD_BAD_HEADER;
+  }
+  rounds[0] = rounds[1] = rounds[2] = 0;
+  if (!info->interleaved) {
+    for (int i = 0; i < info->n_scans; ++i) {
+      const jds_jpeg_scan& sc = info->scan[i];
+      const int c = sc.component[0] - 1;
+      int64_t off = 0;
+      for (int j = 0; j < c; ++j) off += 64 * info->grid_cols[j] * info->grid_rows[j];
+      const int64_t nb = info->grid_cols[c] * info->grid_rows[c];
+      const HuffDecTab *dc = &tabs[sc.dc_table[0]], *ac = &tabs[2 + sc.ac_table[0]];
+      if (sc.restart_interval > 0)
+        st |= hd_host_scan_rst(data + sc.offset, sc.length, dc, ac, sc.restart_interval, nb, coeffs + off);
+      else
+        st |= hd_host_scan(data + sc.offset, sc.length, dc, ac, S, nb, coeffs + off, rounds + i);
+    }
+    return st;
+  }
+  const HdMcu m = hd_jpeg_mcu(info);
+  const HdIl tc{tabs, &m};
+  const jds_jpeg_scan& sc = info->scan[0];
+  const uint8_t* d = data + sc.offset;
+  const int64_t n = sc.length, nblocks = (int64_t)m.bpm * m.mcu_cols * m.mcu_rows;
+  memset(coeffs, 0, sizeof(int16_t) * (size_t)info->coeffs_needed);
+  std::vector<int16_t> dcs((size_t)nblocks, 0);
+  if (sc.restart_interval == 0) {
+    st |= hd_host_sync(d, n, tc, S, nblocks, HdIlSink{&m, coeffs, dcs.data(), HD_ZZ, 0}, rounds);
+    st |= hd_host_dc_mcu(&m, dcs.data(), 0, nblocks, coeffs);
+    return st;
+  }
+  const int64_t rib = (int64_t)sc.restart_interval * m.bpm;
+  int64_t a = 0, blk0 = 0;
+  while (blk0 < nblocks) {
+    int64_t e = a;
+    while (e < n && !(d[e] == 0xFF && e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
+    const int64_t nb = nblocks - blk0 < rib ? nblocks - blk0 : rib;
+    if (rib <= lane_max) {
+      HdIlRstSink sink{&m, coeffs, HD_ZZ, blk0};
+      st |= hd_rst_lane(HdMemSrc{d + a, e - a}, tc, 0, nb, sink);
+      if (sink.bad) st |= HD_DC_RANGE;
+    } else {
+      int32_t r = 0;
+      st |= hd_host_sync(d + a, e - a, tc, S, nb, HdIlSink{&m, coeffs, dcs.data(), HD_ZZ, blk0}, &r);
+      st |= hd_host_dc_mcu(&m, dcs.data(), blk0, blk0 + nb, coeffs);
+      rounds[0] = r > rounds[0] ? r : rounds[0];
+    }
+    blk0 += nb;
+    if (e >= n) break;
+    a = e + 2;
+  }
+  if (blk0 < nblocks) st |= HD_RESTART;
   return st;
 }
 

@@ -84,6 +84,21 @@ class JfifInfo(C.Structure):
                 ('status', C.c_uint32), ('rounds', C.c_uint32)]
 
 
+class JpegScan(C.Structure):
+    _fields_ = [('n_components', C.c_int32), ('component', C.c_int32 * 3), ('dc_table', C.c_int32 * 3),
+                ('ac_table', C.c_int32 * 3), ('restart_interval', C.c_int32), ('offset', C.c_int64),
+                ('length', C.c_int64)]
+
+
+class JpegInfo(C.Structure):
+    _fields_ = [('H', C.c_int64), ('W', C.c_int64), ('subsampling', C.c_int32), ('n_scans', C.c_int32),
+                ('interleaved', C.c_int32), ('reference_grid', C.c_int32), ('single_table', C.c_int32),
+                ('blocks_per_mcu', C.c_int32), ('hs', C.c_int32 * 3), ('vs', C.c_int32 * 3), ('tq', C.c_int32 * 3),
+                ('mcu_cols', C.c_int64), ('mcu_rows', C.c_int64), ('grid_cols', C.c_int64 * 3),
+                ('grid_rows', C.c_int64 * 3), ('qtable', (C.c_double * 64) * 3), ('scan', JpegScan * 3),
+                ('huff', JfifHuff * 4), ('coeffs_needed', C.c_int64), ('status', C.c_uint32), ('rounds', C.c_uint32)]
+
+
 # frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
 DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE, DEC_RESTART = 1, 2, 4, 8, 16, 32, 64
 
@@ -148,6 +163,10 @@ _SIGS = {
     'jds_entropy_decode_info': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'jds_plan_entropy_decode_rounds': (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     'jds_selftest_huffdec': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
+    'jds_jpeg_parse': (C.c_int, [_P, C.c_int64, C.POINTER(JpegInfo)]),
+    'jds_decode_jpeg': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(JpegInfo)]),
+    'jds_decompress_jpeg': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(JpegInfo)]),
+    'jds_selftest_jpegdec':(C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_area_tab': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P]),

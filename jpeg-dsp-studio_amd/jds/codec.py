@@ -91,6 +91,54 @@ def decompress_jfif(data, device: int = 0, with_info: bool = False):
     return img, {'coeffs': cf, 'H': H, 'W': W, 'mode': d['mode'], 'qtable': d['qtable'], 'rounds': int(info.rounds)}
 
 
+def staged_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids) -> np.ndarray:
+    """The reference's inverse stages on planar coefficients (Y, Cb, Cr; each component's blocks
+    in raster order of its (rows, cols) grid) with one table per component, through the
+    per-stage calls only: dequantise, decode_block, merge and crop to the component's T.81
+    plane size, bilinear chroma upsampling unless 4:4:4, YCbCr -> RGB, clip, truncate."""
+    hmax, vmax = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}[mode]
+    cf = np.asarray(coeffs, np.int16).reshape(-1, 8, 8)
+    planes, b0 = [], 0
+    for c, (gr, gc) in enumerate(grids):
+        hs, vs = (hmax, vmax) if c == 0 else (1, 1)
+        ph, pw = -(-H * vs // vmax), -(-W * hs // hmax)
+        blk = stage_block(stage_quant(cf[b0:b0 + gr * gc], np.asarray(qtables[c], np.float64).reshape(8, 8), True), 3)
+        b0 += gr * gc
+        plane = blk.reshape(gr, gc, 8, 8).transpose(0, 2, 1, 3).reshape(8 * gr, 8 * gc)[:ph, :pw]
+        planes.append(plane if (ph, pw) == (H, W) else stage_resize(plane, H, W, nearest=False))
+    rgb = stage_rgb_ycbcr(np.stack(planes, axis=-1), inverse=True)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+def decompress_jpeg(data, device: int = 0, with_info: bool = False, staged: bool | None = None):
+    """A baseline JPEG with one interleaved scan or three non-interleaved ones -> the HxWx3
+    uint8 image.  Plan route (jds_decompress_jpeg, as decompress_jfif) when one quantisation
+    table serves all components and the block grids are the reference's; otherwise, or with
+    staged=True, the staged route: entropy.decode_jpeg, then staged_inverse with the file's own
+    tables (not a throughput path).  with_info: (image, decode_jpeg's dict plus 'route')."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_parse(p, n, C.byref(info)))
+    plan_ok = bool(info.single_table) and bool(info.reference_grid)
+    if staged is False and not plan_ok:
+        raise ValueError('the plan route needs one quantisation table and the reference block grids')
+    if plan_ok and not staged:
+        H, W = int(info.H), int(info.W)
+        img = np.empty((H, W, 3), np.uint8)
+        cf = np.empty(int(info.coeffs_needed), np.int16)
+        with lease(device) as ctx:
+            check(lib().jds_decompress_jpeg(ctx.handle, p, n, img.ctypes.data, img.size, cf.ctypes.data,
+                                            C.byref(info)))
+        d = entropy._jpeg_dict(info)
+        d.update(coeffs=cf, rounds=int(info.rounds), route='plan')
+    else:
+        d = entropy.decode_jpeg(a, device)
+        d['route'] = 'staged'
+        img = staged_inverse(d['coeffs'], d['H'], d['W'], d['mode'], d['qtables'], d['grids'])
+    return (img, d) if with_info else img
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

@@ -124,6 +124,65 @@ def host_decode_jfif(data, subseq_bits: int = 1024):
     return cf, [int(r) for r in rounds]
 
 
+def _jpeg_dict(info: _abi.JpegInfo) -> dict:
+    names = ('dc0', 'dc1', 'ac0', 'ac1')
+    huff = {nm: (list(info.huff[i].bits), list(info.huff[i].vals)[:info.huff[i].n_vals])
+            for i, nm in enumerate(names) if info.huff[i].defined}
+    scans = []
+    for s in info.scan[:info.n_scans]:
+        n = int(s.n_components)
+        scans.append({'components': list(s.component)[:n], 'dc_tables': list(s.dc_table)[:n],
+                      'ac_tables': list(s.ac_table)[:n], 'restart_interval': int(s.restart_interval),
+                      'offset': int(s.offset), 'length': int(s.length)})
+    return {'H': int(info.H), 'W': int(info.W), 'mode': _MODE_NAMES[info.subsampling],
+            'interleaved': bool(info.interleaved), 'reference_grid': bool(info.reference_grid),
+            'single_table': bool(info.single_table),
+            'qtables': np.ctypeslib.as_array(info.qtable).astype(np.float64).reshape(3, 8, 8),
+            'tq': list(info.tq), 'sampling': [(int(info.hs[c]), int(info.vs[c])) for c in range(3)],
+            'grids': [(int(info.grid_rows[c]), int(info.grid_cols[c])) for c in range(3)],
+            'mcu': {'rows': int(info.mcu_rows), 'cols': int(info.mcu_cols), 'blocks': int(info.blocks_per_mcu)},
+            'scans': scans, 'huffman': huff, 'coeffs_needed': int(info.coeffs_needed)}
+
+
+def parse_jpeg(data) -> dict:
+    """jds_jpeg_parse (host only, no GPU): a baseline JPEG with one interleaved scan or three
+    non-interleaved ones, up to three quantisation tables, T.81 block grids.  'grids': (rows,
+    columns) of each component's block grid; 'mcu': the MCU grid and the blocks of an
+    interleaved MCU; 'reference_grid': the grids are the ones parse_jfif accepts.  ValueError
+    naming the feature for anything else."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_parse(p, n, C.byref(info)))
+    return _jpeg_dict(info)
+
+
+def decode_jpeg(data, device: int = 0) -> dict:
+    """One file -> parse_jpeg's dict plus 'coeffs' (int16: Y, Cb, Cr planar, each component's
+    blocks in raster order of its T.81 grid) and 'rounds'."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.coeffs_needed), np.int16)
+    with _abi.lease(device) as ctx:
+        check(lib().jds_decode_jpeg(ctx.handle, p, n, cf.ctypes.data, cf.size, C.byref(info)))
+    d = _jpeg_dict(info)
+    d['coeffs'] = cf
+    d['rounds'] = int(info.rounds)
+    return d
+
+
+def host_decode_jpeg(data, subseq_bits: int = 1024):
+    """Test aid (jds_selftest_jpegdec): decode_jpeg's algorithm on the host with the kernels'
+    shared core -> (coeffs, [rounds per scan in file order]).  No GPU."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.coeffs_needed), np.int16)
+    rounds = (C.c_int32 * 3)()
+    check(lib().jds_selftest_jpegdec(p, n, int(subseq_bits), cf.ctypes.data, cf.size, rounds))
+    return cf, [int(r) for r in rounds][:int(info.n_scans)]
+
+
 def bitrate_from_jfif(nbytes: int, shape) -> dict:
     """bpp / compression ratio of a real file, in estimate_bitrate_no_entropy's
     terms (utils/metrics.py:62-92: 24-bit originals)."""

@@ -8,8 +8,13 @@
 // Parses every file of DIR from an exactly-sized heap copy (so a read past the
 // end is a sanitizer report) and host-decodes the ones that parse, with each
 // subsequence size (default 64, 128, 1024; scans with restart intervals decode
-// one interval at a time whatever the size).  Rejected and defective files are
-// expected; the program exits 0 unless it cannot read DIR.  No HIP, no GPU.
+// one interval at a time whatever the size).  Every file goes through both
+// parsers: hd_parse with hd_host_decode (this library's profile) and
+// hd_jpeg_parse with hd_jpeg_host_decode (interleaved scans, a table per
+// component, T.81 grids; restart intervals by lane up to 128 blocks, then by
+// descriptor, and with a limit of 0 all by descriptor).  Rejected and defective
+// files are expected; the program exits 0 unless it cannot read DIR.  No HIP,
+// no GPU.
 #include <dirent.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,7 +42,7 @@ int main(int argc, char** argv) {
     perror(argv[1]);
     return 2;
   }
-  long files = 0, parsed = 0, decoded = 0, defective = 0;
+  long files = 0, parsed = 0, decoded = 0, defective = 0, jparsed = 0, jdecoded = 0, jdefective = 0;
   while (dirent* e = readdir(dir)) {
     if (e->d_name[0] == '.') continue;
     const std::string path = std::string(argv[1]) + "/" + e->d_name;
@@ -69,9 +74,24 @@ int main(int argc, char** argv) {
         free(cf);
       }
     }
+    jds_jpeg_info ji;
+    if (jds::hd_jpeg_parse(data, n, &ji, msg, sizeof msg) == JDS_OK && ji.coeffs_needed <= (int64_t)1 << 28) {
+      ++jparsed;
+      int16_t* cf = (int16_t*)malloc(sizeof(int16_t) * (size_t)ji.coeffs_needed);
+      if (cf) {
+        for (int s : sizes)
+          for (int64_t lane_max : {(int64_t)128, (int64_t)0}) {
+            int32_t rounds[3] = {0, 0, 0};
+            const uint32_t st = jds::hd_jpeg_host_decode(data, &ji, s, lane_max, cf, rounds);
+            st ? ++jdefective : ++jdecoded;
+          }
+        free(cf);
+      }
+    }
     free(data);
   }
   closedir(dir);
   printf("%ld files, %ld parsed, %ld decodes clean, %ld defective\n", files, parsed, decoded, defective);
+  printf("jpeg parser: %ld parsed, %ld decodes clean, %ld defective\n", jparsed, jdecoded, jdefective);
   return 0;
 }
