@@ -472,6 +472,43 @@ int jds_decode_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coe
  * throughput path.  coeffs: NULL, or info->coeffs_needed entries. */
 int jds_decompress_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
                         int16_t* coeffs, jds_jpeg_info* info);
+/* Foreign files to pixels (DESIGN.md "Foreign files to pixels"): the fused
+ * inverse k_jpeg_inv takes the coefficients of jds_decode_jpeg (any file
+ * jds_jpeg_parse accepts: either scan form, a table per component, T.81 grids at
+ * any size) to RGB bytes in one launch, byte for byte what the per-stage route
+ * (jds.codec.staged_inverse) reconstructs: dequantise with the component's
+ * table, the exact fp64 IDCT, +128, clip, crop chroma to its T.81 plane
+ * ceil(H Vc / Vmax) x ceil(W Hc / Hmax), cv2 INTER_LINEAR with its general taps
+ * to H x W, NumPy's colour expressions, clip, truncate.
+ *
+ * jds_jpeg_inverse_info: the tile of output pixels one workgroup produces
+ *   (compile-time constants, multiples of 16).
+ * jds_jpeg_inverse_dev: coeffs (info->coeffs_needed int16) and rgb (H*W*3
+ *   bytes) are device pointers of the context's device; one launch on `stream`,
+ *   asynchronous, nothing uploaded or read back (the tables travel as kernel
+ *   arguments).  Reads H, W, subsampling, grid_rows/cols, coeffs_needed and
+ *   qtable of info; a table entry outside integer [1, 255] or grids other than
+ *   T.81's for H x W are JDS_EINVAL (checked before anything else).
+ * jds_jpeg_to_rgb: parse, decode and that launch on the context's stream, then
+ *   the image into rgb_out: host memory, or with rgb_on_device != 0 a device
+ *   buffer of the context's device (written in place by the kernel).
+ *   Synchronous either way.  coeffs: NULL, or host memory of coeffs_needed
+ *   entries.  The error contract of jds_decode_jpeg; on a defective scan
+ *   (JDS_EINVAL naming the defect) rgb_out is not written and the context stays
+ *   usable. */
+int jds_jpeg_inverse_info(int32_t* tile_h, int32_t* tile_w);
+int jds_jpeg_inverse_dev(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream);
+int jds_jpeg_to_rgb(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                    int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info);
+/* Test-only, host-only: the kernel's tile core (csrc/jds_jpeg_inv.hpp) in a
+ * host tile loop with the same window function; the argument checks of
+ * jds_jpeg_inverse_dev.  No GPU. */
+int jds_selftest_jpeg_inverse(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out);
+/* Test-only: jpeg_inv_window on one axis: the chroma samples [out[0], out[0] +
+ * out[1]) that destination indices d0..d1 of a dst_n-long axis read from a
+ * src_n-long one (xaxis: cv2's clamped column taps); out[2], out[3]: the rows
+ * and columns the kernel's window array holds on a subsampled axis. */
+int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_n, int32_t xaxis, int32_t* out);
 /* Test-only: jds_decode_jpeg's algorithm on the host (see jds_selftest_huffdec).
  * rounds_out[3]: decode rounds per scan in file order (an interleaved file has
  * one scan; 0 for a scan with restart intervals).  No GPU. */

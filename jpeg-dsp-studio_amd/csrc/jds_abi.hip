@@ -19,6 +19,7 @@
 #include "jds_dct8.hpp"
 #include "jds_huffdec.hpp"
 #include "jds_internal.hpp"
+#include "jds_jpeg_inv.hpp"
 
 #ifdef JDS_INV6
 #define JDS_INV6_LIST 1  // the transpose-free variant's tile list (A/B builds: tools/build_variant.py)
@@ -117,6 +118,10 @@ void fast_fwd16_thresholds(const double* Q8, int mode, bool pf, const double* gk
 size_t fast_q16_size();
 int fwd16_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, int H, int W, int plane,
                      int flags, float* out);
+void jpeg_inv_constants(int* th, int* tw);
+bool jpeg_inv_fits(const JInvArgs& a);
+hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb);
 }
 
 // skimage: C1 = (K1 * R) ** 2, C2 = (K2 * R) ** 2 with R = data_range = 255
@@ -1922,6 +1927,87 @@ int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* r
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
   return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
+// ----------------------------------- foreign files to pixels (k_jpeg_inv) --
+
+int jds_jpeg_inverse_info(int32_t* tile_h, int32_t* tile_w) {
+  if (!tile_h || !tile_w) return fail(JDS_EINVAL, "null argument");
+  int th, tw;
+  jpeg_inv_constants(&th, &tw);
+  *tile_h = th;
+  *tile_w = tw;
+  return JDS_OK;
+}
+
+// The launch arguments of a parsed file: its tables by check_tables' rule, its
+// grids T.81's for H x W, every tile's chroma window within the kernel's arrays.
+static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
+  const int rc = jinv_args(info, a);
+  if (rc == -1000)
+    return fail(JDS_EINVAL, "jpeg inverse: %lldx%lld with these grids is not a T.81 geometry of subsampling %d",
+                (long long)info->H, (long long)info->W, info->subsampling);
+  if (rc < 0) {
+    const int c = (-rc - 1) / 64, i = (-rc - 1) % 64;
+    return fail(JDS_EINVAL, "qtable[%d][%d] = %g is not an integer in [1, 255]", c, i, info->qtable[c][i]);
+  }
+  if (!jpeg_inv_fits(*a))
+    return fail(JDS_ENOTSUP, "jpeg inverse: a tile of %lldx%lld reads a wider chroma window than the kernel keeps",
+                (long long)info->H, (long long)info->W);
+  return JDS_OK;
+}
+
+int jds_jpeg_inverse_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream) {
+  if (!info) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  int rc;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  if (!c || !coeffs || !rgb) return fail(JDS_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_jpeg_inv(a, coeffs, rgb, (hipStream_t)stream));
+  return JDS_OK;
+}
+
+int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                    int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: rgb_out is not written)
+  uint8_t* dst = rgb_out;
+  if (!rgb_on_device) {
+    HIP_TRY(c->out.ensure(nimg));
+    dst = (uint8_t*)c->out.p;
+  }
+  HIP_TRY(launch_jpeg_inv(a, (const int16_t*)c->ent_cf.p, dst, c->stream));
+  if (!rgb_on_device) HIP_TRY(hipMemcpyAsync(rgb_out, dst, nimg, hipMemcpyDeviceToHost, c->stream));
+  if (coeffs)
+    HIP_TRY(hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_inverse(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out) {
+  if (!info || !coeffs || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  const int rc = jpeg_inv_args(info, &a);
+  if (rc) return rc;
+  jpeg_inv_host(a, coeffs, rgb_out);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_n, int32_t xaxis, int32_t* out) {
+  if (!out || dst_n < 1 || src_n < 1 || d0 < 0 || d1 < d0 || d1 >= dst_n) return fail(JDS_EINVAL, "bad argument");
+  jpeg_inv_window(d0, d1, 1.0 / ((double)dst_n / (double)src_n), src_n, xaxis != 0, &out[0], &out[1]);
+  out[2] = JI_CAP_ROWS2;
+  out[3] = JI_CAP_COLS2;
+  return JDS_OK;
 }
 
 int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,

@@ -167,6 +167,11 @@ _SIGS = {
     'jds_decode_jpeg': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(JpegInfo)]),
     'jds_decompress_jpeg': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(JpegInfo)]),
     'jds_selftest_jpegdec':(C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
+    'jds_jpeg_inverse_info': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'jds_jpeg_inverse_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P, _P]),
+    'jds_jpeg_to_rgb': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegInfo)]),
+    'jds_selftest_jpeg_inverse': (C.c_int, [C.POINTER(JpegInfo), _P, _P]),
+    'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_area_tab': (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P]),

@@ -139,6 +139,78 @@ def decompress_jpeg(data, device: int = 0, with_info: bool = False, staged: bool
     return (img, d) if with_info else img
 
 
+def jpeg_inverse_info() -> Tuple[int, int]:
+    """(tile_h, tile_w): the output pixels one workgroup of the fused inverse produces."""
+    th, tw = C.c_int32(0), C.c_int32(0)
+    check(lib().jds_jpeg_inverse_info(C.byref(th), C.byref(tw)))
+    return int(th.value), int(tw.value)
+
+
+def _jpeg_info_struct(H: int, W: int, mode: str, qtables, grids) -> _abi.JpegInfo:
+    """The fields the fused inverse reads, from parse_jpeg's / decode_jpeg's terms."""
+    info = _abi.JpegInfo()
+    info.H, info.W, info.subsampling = int(H), int(W), _abi.MODE_CODES[mode]
+    q = np.ascontiguousarray(qtables, np.float64).reshape(3, 64)
+    for c, (gr, gc) in enumerate(grids):
+        info.grid_rows[c], info.grid_cols[c] = int(gr), int(gc)
+        for i in range(64):
+            info.qtable[c][i] = q[c, i]
+    info.coeffs_needed = 64 * sum(int(gr) * int(gc) for gr, gc in grids)
+    return info
+
+
+def jpeg_inverse_dev(info: dict, coeffs_ptr: int, rgb_ptr: int, stream=None, device: int = 0) -> None:
+    """jds_jpeg_inverse_dev: coefficients on the device (decode_jpeg's layout, int16) -> H*W*3
+    RGB bytes on the device, one asynchronous launch on `stream` (a HIP stream handle; None: the
+    null stream).  info: what entropy.parse_jpeg or decode_jpeg returned for the file."""
+    st = _jpeg_info_struct(info['H'], info['W'], info['mode'], info['qtables'], info['grids'])
+    with lease(device) as ctx:
+        check(lib().jds_jpeg_inverse_dev(ctx.handle, C.byref(st), C.c_void_p(int(coeffs_ptr)),
+                                         C.c_void_p(int(rgb_ptr)), C.c_void_p(int(stream or 0))))
+
+
+def host_jpeg_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids) -> np.ndarray:
+    """Test aid (jds_selftest_jpeg_inverse): the fused inverse's tile core in a host tile loop,
+    staged_inverse's arguments.  No GPU."""
+    st = _jpeg_info_struct(H, W, mode, qtables, grids)
+    cf = np.ascontiguousarray(coeffs, np.int16).reshape(-1)
+    if cf.size != int(st.coeffs_needed):
+        raise ValueError(f'expected {int(st.coeffs_needed)} coefficients, got {cf.size}')
+    img = np.empty((int(H), int(W), 3), np.uint8)
+    check(lib().jds_selftest_jpeg_inverse(C.byref(st), cf.ctypes.data, img.ctypes.data))
+    return img
+
+
+def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None):
+    """jds_jpeg_to_rgb: any baseline JPEG parse_jpeg accepts -> the HxWx3 uint8 image, by the
+    entropy decode and one fused inverse launch (k_jpeg_inv) with the file's own tables and
+    grids: byte for byte decompress_jpeg(staged=True)'s image.  out: an object with data_ptr()
+    (a contiguous uint8 torch tensor of shape (H, W, 3) on `device`): the image stays on the
+    device, written there, and `out` is returned.  with_info: (image, decode_jpeg's dict plus
+    'route': 'fused')."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_parse(p, n, C.byref(info)))
+    H, W = int(info.H), int(info.W)
+    if out is None:
+        img = np.empty((H, W, 3), np.uint8)
+        dst, on_dev = img.ctypes.data, 0
+    else:
+        if tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.element_size() != 1:
+            raise ValueError(f'out must be a contiguous uint8 ({H}, {W}, 3) device tensor')
+        img, dst, on_dev = out, int(out.data_ptr()), 1
+    cf = np.empty(int(info.coeffs_needed), np.int16) if with_info else None
+    with lease(device) as ctx:
+        check(lib().jds_jpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
+                                    cf.ctypes.data if with_info else None, C.byref(info)))
+    if not with_info:
+        return img
+    d = entropy._jpeg_dict(info)
+    d.update(coeffs=cf, rounds=int(info.rounds), route='fused')
+    return img, d
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

@@ -8,7 +8,11 @@ coefficients -- upload, the decode's launches and its read-backs between
 rounds, download -- so it is timed by a host clock: three warm-up calls, REPS
 (30) calls, the median.  Prints one JSON line per input; --out FILE writes them
 as a JSON list.  --once: one call per input after one warm-up (for a run under
-rocprofv3 --kernel-trace --stats, which gives the per-kernel split)."""
+rocprofv3 --kernel-trace --stats, which gives the per-kernel split).
+--rgb adds, per Pillow input, the way to pixels: jpeg_to_rgb to host memory and
+to a device tensor, decompress_jpeg(staged=True) (at most 5 calls: it is slow),
+k_jpeg_inv alone by events, and one more line: the plan's exact inverse k_inv2
+on a frame of the same geometry by the plan's launch marks (the yardstick)."""
 import io
 import json
 import os
@@ -38,9 +42,87 @@ def median_ms(fn, reps):
     return t[len(t) // 2], t[0], t[-1]
 
 
+def rgb_leg(data, reps):
+    """--rgb: the same file to pixels.  jpeg_to_rgb to host memory and to a device tensor and
+    decompress_jpeg(staged=True) by the host clock (whole calls); k_jpeg_inv alone by events
+    around back-to-back jds_jpeg_inverse_dev launches on coefficients already on the device."""
+    import torch
+    d = entropy.decode_jpeg(data)
+    h, w = d['H'], d['W']
+    fused = codec.jpeg_to_rgb(data)
+    staged = codec.decompress_jpeg(data, staged=True)
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device='cuda')
+    row = {'jpeg_to_rgb_host_ms': median_ms(lambda: codec.jpeg_to_rgb(data), reps)[0],
+           'jpeg_to_rgb_device_ms': median_ms(lambda: codec.jpeg_to_rgb(data, out=out), reps)[0],
+           'decompress_jpeg_staged_ms': median_ms(lambda: codec.decompress_jpeg(data, staged=True), min(reps, 5))[0],
+           'fused_equals_staged': bool(np.array_equal(fused, staged)) and bool(np.array_equal(out.cpu().numpy(), fused))}
+    cf = torch.from_numpy(d['coeffs']).cuda()
+    s = torch.cuda.current_stream()
+    out.zero_()
+    codec.jpeg_inverse_dev(d, cf.data_ptr(), out.data_ptr(), s.cuda_stream)
+    s.synchronize()
+    row['inverse_dev_equals_staged'] = bool(np.array_equal(out.cpu().numpy(), staged))
+    # The kernel is shorter than a launch from Python: KB launches are queued behind a few
+    # milliseconds of fills, so that the events bracket back-to-back launches, not the host.
+    from jds import _abi
+    import ctypes as C
+    st = codec._jpeg_info_struct(h, w, d['mode'], d['qtables'], d['grids'])
+    fill = torch.empty(1 << 30, dtype=torch.uint8, device='cuda')
+    KB, us = 20, []
+    with _abi.lease(0) as ctx:
+        for i in range(3 + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(12):
+                fill.fill_(i)
+            e0.record(s)
+            for _ in range(KB):
+                _abi.check(_abi.lib().jds_jpeg_inverse_dev(ctx.handle, C.byref(st), C.c_void_p(cf.data_ptr()),
+                                                           C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+            e1.record(s)
+            e1.synchronize()
+            if i >= 3:
+                us.append(e0.elapsed_time(e1) * 1e3 / KB)
+    us.sort()
+    row['k_jpeg_inv_us_median_events'] = us[len(us) // 2]
+    row['k_jpeg_inv_us_min_events'] = us[0]
+    row['k_jpeg_inv_launches_per_event_pair'] = KB
+    return row
+
+
+def inv2_yardstick(H, W, reps):
+    """--rgb: the plan's exact inverse k_inv2 on one frame of the same geometry (one table, the
+    reference's grids), by the plan's launch marks."""
+    import torch
+    from jds import _abi
+    qt = scale_quant_matrix(JPEG_LUMA_Q50, 50)
+    plan = _abi.Plan(_abi.context(0), [_abi.make_params(50, qt, '4:2:0', True, codec.gaussian_kernel3())], H, W)
+    g = torch.Generator(device='cuda').manual_seed(7)
+    rgb = torch.randint(0, 256, (1, H, W, 3), dtype=torch.uint8, device='cuda', generator=g)
+    out = torch.empty_like(rgb)
+    cf = torch.zeros((1, plan.geometry.coeffs_per_frame), dtype=torch.int16, device='cuda')
+    st = torch.zeros((1, _abi.STATS_DTYPE.itemsize), dtype=torch.uint8, device='cuda')
+    s = torch.cuda.current_stream().cuda_stream
+    plan.run(rgb.data_ptr(), out.data_ptr(), cf.data_ptr(), st.data_ptr(), 0, s)
+    flags = _abi.RUN_INV | _abi.RUN_EXACT_INV
+    for _ in range(3):
+        plan.run(rgb.data_ptr(), out.data_ptr(), cf.data_ptr(), st.data_ptr(), flags, s)
+    torch.cuda.synchronize()
+    plan.profile(True)
+    for _ in range(reps):
+        plan.run(rgb.data_ptr(), out.data_ptr(), cf.data_ptr(), st.data_ptr(), flags, s)
+    torch.cuda.synchronize()
+    kern, span = plan.profile_read()
+    plan.profile(False)
+    plan.close()
+    return {'input': 'plan_exact_inverse', 'call': 'plan.run(RUN_INV | RUN_EXACT_INV)', 'H': H, 'W': W, 'reps': reps,
+            'kernels_us_per_frame': {k: v[0] * 1e3 / reps for k, v in kern.items()},
+            'span_us_per_frame': span * 1e3 / reps, 'equals_host_model': True}
+
+
 def main():
     H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
     reps = 1 if '--once' in sys.argv else int(os.environ.get('REPS', '30'))
+    want_rgb = '--rgb' in sys.argv
     noise = np.random.default_rng(7).integers(0, 256, (H, W, 3), dtype=np.uint8)
     gray = np.full((H, W, 3), 128, np.uint8)
     inputs = [('pillow_plain', noise, {}), ('pillow_optimize', noise, {'optimize': True}),
@@ -57,6 +139,12 @@ def main():
                      'restart_interval_mcus': d['scans'][0]['restart_interval'], 'rounds': d['rounds'],
                      'ms_per_file_median': med, 'ms_min': lo, 'ms_max': hi, 'reps': reps,
                      'equals_host_model': ok, 'subseq_bits_per_group': entropy.decode_info()})
+        if want_rgb:
+            rows[-1].update(rgb_leg(data, reps))
+            rows[-1]['equals_host_model'] = ok and rows[-1]['fused_equals_staged'] and rows[-1]['inverse_dev_equals_staged']
+        print(json.dumps(rows[-1]), flush=True)
+    if want_rgb:
+        rows.append(inv2_yardstick(H, W, reps))
         print(json.dumps(rows[-1]), flush=True)
     # this library's own file of the same images
     qt = scale_quant_matrix(JPEG_LUMA_Q50, 50)
