@@ -171,6 +171,13 @@ typedef struct {
 } jds_kernel_time;
 int jds_plan_profile(jds_plan* plan, int enable);
 int jds_plan_profile_read(jds_plan* plan, jds_kernel_time* out, int max, int* n_out, double* span_ms);
+/* The same marks for the batch calls of a context (jds_jpeg_batch_to_rgb): the
+ * kernels by name, "(batch upload)" (the one host-to-device copy and the
+ * zero-fills), "(batch download)", "(between calls)".  The first k_dec_sync of a
+ * call includes the descriptors' upload, and every one the host read of the
+ * round before it. */
+int jds_ctx_profile(jds_ctx* ctx, int enable);
+int jds_ctx_profile_read(jds_ctx* ctx, jds_kernel_time* out, int max, int* n_out, double* span_ms);
 
 /* Host-buffer path: the drop-in for engines.pipeline.compress_reconstruct
  * (engines/pipeline.py:17-167).  Synchronous.  rgb: HxWx3 u8, C-contiguous.
@@ -514,6 +521,58 @@ int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_
  * one scan; 0 for a scan with restart intervals).  No GPU. */
 int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
                          int32_t* rounds_out);
+
+/* Batches of foreign files (DESIGN.md "Batches of foreign files"): n files of
+ * any mix of sizes, subsampling modes, tables, restart intervals and scan forms
+ * through ONE set of launches -- the entropy decode over the descriptors of
+ * every file (as many propagation rounds as the slowest file needs), then
+ * k_jpeg_inv_batch once per subsampling mode present -- into one output buffer.
+ *
+ * Layout: file i's image starts at items[i].rgb_off, a multiple of 256, and the
+ *   images follow one another in batch order; rgb_bytes is the sum of the
+ *   images' sizes, each rounded up to 256.  The bytes between an image's end
+ *   and the next multiple of 256 are never written.  Its coefficients
+ *   (jds_decode_jpeg's layout) are entries [coef_off, coef_off + coeffs_needed)
+ *   of the batch's coefficient buffer, end to end; coef_entries is their sum.
+ * A file jds_jpeg_parse rejects, or whose tables or geometry the checks of
+ *   jds_jpeg_inverse_dev refuse, is an ITEM error: items[i].rc carries the code
+ *   that call gives for the file alone, the file takes no space (rgb_off and
+ *   coef_off -1, coeffs_needed 0) and the batch goes on.  The call then still
+ *   returns JDS_OK, and jds_last_error names the first such file by index
+ *   ("file 3: ...").
+ * A file whose SCAN DATA are defective keeps its space: items[i].status carries
+ *   the JDS_DEC_* bits jds_decode_jpeg reports for it, its pixels are all zero
+ *   (the inverse reads the status word on the device), its coefficients are
+ *   unspecified, and no other file's bytes are affected.
+ * jds_jpeg_batch_layout: host only; parse every file, lay the outputs out.
+ * jds_jpeg_batch_to_rgb: synchronous.  rgb: rgb_cap >= rgb_bytes bytes of host
+ *   memory, or with rgb_on_device != 0 of the context's device (the images are
+ *   written in place and only the status words come back).  coeffs: NULL, or
+ *   host memory of coef_entries entries.  rounds (nullable): the propagation
+ *   rounds of the batch, the largest any of its files needs.  n == 0 is valid.
+ *   The file bytes are gathered into one pinned staging buffer of the context
+ *   (each file at a 16-byte boundary) and uploaded once together with the
+ *   descriptors, table sets, MCU and inverse records.  JDS_ENOTSUP: more blocks,
+ *   tiles or intervals than the grids and 32-bit indices take.
+ * jds_selftest_jpeg_batch: test-only, host only: the same layout, the host
+ *   decode model per file (jds_selftest_jpegdec) and the host model of the batch
+ *   inverse (the same tile map and per-image records).  coeffs may be NULL. */
+typedef struct {
+  int32_t rc;        /* JDS_OK, or the code jds_jpeg_parse / the inverse's checks gave this file */
+  uint32_t status;   /* JDS_DEC_* bits of its scan data; 0: decoded */
+  int64_t H, W;
+  int32_t subsampling, interleaved;
+  int64_t rgb_off;   /* its image's first byte in the output; a multiple of 256 */
+  int64_t coef_off;  /* its first coefficient in the batch's coefficient buffer */
+  int64_t coeffs_needed;
+} jds_jpeg_batch_item;
+int jds_jpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                          int64_t* rgb_bytes, int64_t* coef_entries);
+int jds_jpeg_batch_to_rgb(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                          int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                          uint32_t* rounds);
+int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                            uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items);
 
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,

@@ -14,6 +14,8 @@
 #include <vector>
 #include <mutex>
 #include <new>
+#include <string>
+#include <thread>
 
 #include "jds_dct16.hpp"
 #include "jds_dct8.hpp"
@@ -94,6 +96,7 @@ hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* 
                               const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                               unsigned long long* scan_bits, hipStream_t s);
 void rst_constants(int* lane_max);
+int rst_group_lanes();
 size_t rst_work_bytes(int n, const RstGeo& rg);
 hipError_t launch_dec_rst(const uint8_t* files, const RstIv* ivs_dev, long long niv, const HuffDecTab* tabs_dev,
                           int16_t* coeffs, uint32_t* status, hipStream_t s, const HdMcu* mcu_dev);
@@ -109,6 +112,9 @@ hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned
 hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
                    const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
                    hipStream_t s, unsigned* rounds, int* too_many, const HdMcu* mcu_dev, int16_t* dcs);
+hipError_t dec_run_groups(const uint8_t* files, const DecGroup* grp, int ngrp, const HuffDecTab* tabs_dev,
+                          int16_t* coeffs, long long n_coeffs, uint32_t* status, hipStream_t s, unsigned* rounds,
+                          int* too_many, const HdMcu* mcu_dev, int16_t* dcs);
 hipError_t launch_codec16(int mode, bool pf, const Geo& g, int n, const uint8_t* rgb, uint8_t* rgb_out,
                           int16_t* coeffs, const FrameQ* fq, const double* gk, jds_frame_stats* st, double* part,
                           double* planes, bool want_sse, double* err_y, double* err_rgb, hipStream_t s,
@@ -122,6 +128,9 @@ void jpeg_inv_constants(int* th, int* tw);
 bool jpeg_inv_fits(const JInvArgs& a);
 hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb);
+hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[3], const int nmap[3],
+                                 const int tiles[3], const uint32_t* status, const int16_t* coeffs, uint8_t* rgb,
+                                 hipStream_t s);
 }
 
 // skimage: C1 = (K1 * R) ** 2, C2 = (K2 * R) ** 2 with R = data_range = 255
@@ -193,6 +202,14 @@ struct jds_ctx {
   DevBuf dec_file, dec_tab, dec_scr, dec_st;  // entropy decoder (jds_decode_jfif): file, tables, scratch, status
   DevBuf dec_iv;                              // its restart interval table
   DevBuf dec_mcu;                             // interleaved scans (jds_decode_jpeg): MCU descriptor, DC staging array
+  // jds_jpeg_batch_to_rgb: everything a batch uploads (file bytes, table sets, MCU and inverse records, tile maps,
+  // interval lists, initial status words) is gathered in one pinned host buffer and copied once to bat
+  DevBuf bat;
+  void* bat_host = nullptr;
+  size_t bat_host_cap = 0;
+  // jds_ctx_profile: launch marks of the batch calls on this context
+  KMarks marks;
+  bool prof_on = false;
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
   size_t ss_budget = 0;  // SSIM scratch budget per launch group (0: SSIM_SCRATCH; jds_ctx_set_ssim_scratch)
 };
@@ -375,6 +392,16 @@ struct MarkScope {
   ~MarkScope() { t_kmarks = nullptr; }
 };
 
+// The same for a profiled context (jds_jpeg_batch_to_rgb's scope).
+struct CtxMarkScope {
+  explicit CtxMarkScope(jds_ctx* c, hipStream_t s) {
+    if (!c->prof_on) return;
+    t_kmarks = &c->marks;
+    kmark(s, "(between calls)");
+  }
+  ~CtxMarkScope() { t_kmarks = nullptr; }
+};
+
 static void marks_release(KMarks& m) {
   for (int i = 0; i < m.cap; ++i) (void)hipEventDestroy(m.ev[i]);
   free(m.ev);
@@ -518,6 +545,33 @@ static int gen_prepare(const Geo& g, int n_frames, int n, DevBuf& tab, DevBuf& s
 
 // ------------------------------------------------------------------ ABI --
 
+// fn(i) for i in [0, n) on up to BATCH_THREADS host threads (files are
+// independent: a 1080p file's parse walks its 850 KB of scan data for markers,
+// and its gather copies them).
+constexpr int BATCH_THREADS = 8;
+template <class F>
+static void batch_parallel(int n, F fn) {
+  const int nt = n < 4 ? 1 : (n / 2 < BATCH_THREADS ? n / 2 : BATCH_THREADS);
+  if (nt <= 1) {
+    for (int i = 0; i < n; ++i) fn(i);
+    return;
+  }
+  std::vector<std::thread> th;
+  th.reserve((size_t)nt);
+  for (int t = 1; t < nt; ++t) {
+    auto share = [=] {
+      for (int i = t; i < n; i += nt) fn(i);
+    };
+    try {
+      th.emplace_back(share);
+    } catch (...) {  // no thread to be had: this one does the share
+      share();
+    }
+  }
+  for (int i = 0; i < n; i += nt) fn(i);
+  for (std::thread& t : th) t.join();
+}
+
 extern "C" {
 
 int jds_abi_version(void) { return JDS_ABI_VERSION; }
@@ -614,6 +668,9 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->dec_st.release();
   c->dec_iv.release();
   c->dec_mcu.release();
+  c->bat.release();
+  if (c->bat_host) (void)hipHostFree(c->bat_host);
+  marks_release(c->marks);
   c->gen_tab.release();
   c->gen_sub.release();
   c->gen_rec.release();
@@ -916,10 +973,10 @@ int jds_plan_run(jds_plan* p, const uint8_t* rgb, uint8_t* rgb_out, int16_t* coe
   return JDS_OK;
 }
 
-int jds_plan_profile(jds_plan* p, int enable) {
-  if (!p) return fail(JDS_EINVAL, "null argument");
-  if (enable && !p->marks.cap) {
-    HIP_TRY(hipSetDevice(p->ctx->device));
+// The launch marks of a plan or of a context (jds_plan_profile, jds_ctx_profile).
+static int marks_enable(KMarks& marks, bool& on, int device, int enable) {
+  if (enable && !marks.cap) {
+    HIP_TRY(hipSetDevice(device));
     const int cap = 8192;  // marks until the next read: ~7 per run
     KMarks m;
     m.ev = (hipEvent_t*)calloc(cap, sizeof(hipEvent_t));
@@ -939,17 +996,21 @@ int jds_plan_profile(jds_plan* p, int enable) {
         return fail(JDS_EHIP, "hipEventCreate: %s", hipGetErrorString(e));
       }
     }
-    p->marks = m;
+    marks = m;
   }
-  p->prof_on = enable != 0;
-  p->marks.n = 0;
-  p->marks.dropped = 0;
+  on = enable != 0;
+  marks.n = 0;
+  marks.dropped = 0;
   return JDS_OK;
 }
 
-int jds_plan_profile_read(jds_plan* p, jds_kernel_time* out, int max, int* n_out, double* span_ms) {
-  if (!p || !n_out || (max > 0 && !out)) return fail(JDS_EINVAL, "null argument");
-  KMarks& m = p->marks;
+int jds_plan_profile(jds_plan* p, int enable) {
+  if (!p) return fail(JDS_EINVAL, "null argument");
+  return marks_enable(p->marks, p->prof_on, p->ctx->device, enable);
+}
+
+static int marks_read(KMarks& m, int device, jds_kernel_time* out, int max, int* n_out, double* span_ms) {
+  if (!n_out || (max > 0 && !out)) return fail(JDS_EINVAL, "null argument");
   *n_out = 0;
   if (span_ms) *span_ms = 0.0;
   if (m.dropped) {  // the pool filled up: partial totals would under-report, so none are returned
@@ -964,7 +1025,7 @@ int jds_plan_profile_read(jds_plan* p, jds_kernel_time* out, int max, int* n_out
     m.n = 0;
     return JDS_OK;
   }
-  HIP_TRY(hipSetDevice(p->ctx->device));
+  HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipEventSynchronize(m.ev[m.n - 1]));
   int k = 0;
   for (int i = 1; i < m.n; ++i) {
@@ -989,6 +1050,21 @@ int jds_plan_profile_read(jds_plan* p, jds_kernel_time* out, int max, int* n_out
   *n_out = k;
   m.n = 0;
   return JDS_OK;
+}
+
+int jds_plan_profile_read(jds_plan* p, jds_kernel_time* out, int max, int* n_out, double* span_ms) {
+  if (!p) return fail(JDS_EINVAL, "null argument");
+  return marks_read(p->marks, p->ctx->device, out, max, n_out, span_ms);
+}
+
+int jds_ctx_profile(jds_ctx* c, int enable) {
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  return marks_enable(c->marks, c->prof_on, c->device, enable);
+}
+
+int jds_ctx_profile_read(jds_ctx* c, jds_kernel_time* out, int max, int* n_out, double* span_ms) {
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  return marks_read(c->marks, c->device, out, max, n_out, span_ms);
 }
 
 void jds_plan_destroy(jds_plan* p) {
@@ -1619,39 +1695,52 @@ int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, 
   return JDS_OK;
 }
 
-// Upload one parsed file and decode it into c->ent_cf (device coefficients).
-static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfif_info* info) {
-  hipStream_t s = c->stream;
-  HuffDecTab tabs[4];
-  for (int i = 0; i < 4; ++i) {
-    memset(&tabs[i], 0, sizeof tabs[i]);
-    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0)
-      return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
+// Where a file's descriptors point in launches that serve several files
+// (jds_jpeg_batch_to_rgb); the single-file calls pass zeros.
+struct FilePlace {
+  int file;            // its table set (tabs + 4 * file), MCU record (mcu + file) and status word
+  long long data_off;  // its first byte, from the files base
+  long long coef_off;  // its first coefficient, from the coeffs base
+  long long dcs_off;   // interleaved: its first entry in the DC staging array
+};
+
+// The next RSTm marker of n bytes of scan data at or after byte a (n: none).
+static long long next_rst(const uint8_t* d, long long a, long long n) {
+  while (a < n) {
+    const uint8_t* p = (const uint8_t*)memchr(d + a, 0xFF, (size_t)(n - a));
+    if (!p) break;
+    const long long e = p - d;
+    if (e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7) return e;
+    a = e + 1;
   }
-  // A scan without restart intervals is one descriptor of the self-synchronising
-  // kernels.  With an interval of at most lane_max blocks every interval goes to
-  // a lane of k_dec_rst; with a larger one every interval is a descriptor of its
-  // own (byte range, block count, destination), whose DC sum is the interval's.
-  int lane_max;
-  rst_constants(&lane_max);
-  std::vector<DecScan> sc;
-  std::vector<RstIv> ivs;
+  return n;
+}
+
+// Appends the descriptors and lane intervals of a parsed file with three
+// non-interleaved scans.  A scan without restart intervals is one descriptor of
+// the self-synchronising kernels.  With an interval of at most lane_max blocks
+// every interval goes to a lane of k_dec_rst; with a larger one every interval
+// is a descriptor of its own (byte range, block count, destination), whose DC
+// sum is the interval's.
+static int plain_descriptors(const uint8_t* data, const jds_jfif_info* info, const FilePlace& pl, int lane_max,
+                             std::vector<DecScan>& sc, std::vector<RstIv>& ivs) {
   for (int i = 0; i < 3; ++i) {
     const jds_jfif_scan& f = info->scan[i];
     const int comp = f.component - 1;
     if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
-    const long long coef_off = comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks);
+    const long long coef_off = pl.coef_off + (comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks));
     const long long nblocks = comp ? info->c_blocks : info->y_blocks;
     const long long ri = f.restart_interval;
     auto descriptor = [&](long long off, long long nbytes, long long blk0, long long nb) {
       DecScan d{};
-      d.data_off = off;
+      d.data_off = pl.data_off + off;
       d.nbytes = nbytes;
       d.coef_off = coef_off + 64 * blk0;
       d.nblocks = (int)nb;
-      d.frame = 0;
-      d.dc_tab = f.dc_table;
-      d.ac_tab = 2 + f.ac_table;
+      d.frame = pl.file;
+      d.file = pl.file;
+      d.dc_tab = 4 * pl.file + f.dc_table;
+      d.ac_tab = 4 * pl.file + 2 + f.ac_table;
       sc.push_back(d);
     };
     if (ri == 0) {
@@ -1662,17 +1751,17 @@ static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfi
     const uint8_t* d = data + f.offset;
     long long a = 0, blk0 = 0;
     while (blk0 < nblocks) {
-      long long e = a;
-      while (e < f.length && !(d[e] == 0xFF && e + 1 < f.length && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
+      const long long e = next_rst(d, a, f.length);
       const long long nb = nblocks - blk0 < ri ? nblocks - blk0 : ri;
       if (ri <= lane_max) {
         if (e - a > 0x7fffffffll) return fail(JDS_ENOTSUP, "restart interval of %lld bytes", e - a);
         RstIv v{};
-        v.data_off = f.offset + a;
+        v.data_off = pl.data_off + f.offset + a;
         v.coef_off = coef_off + 64 * blk0;
         v.nbytes = (int)(e - a);
         v.nblk = (int)nb;
-        v.frame = 0;
+        v.frame = pl.file;
+        v.file = pl.file;
         v.tabs = f.dc_table | ((2 + f.ac_table) << 8);
         ivs.push_back(v);
       } else {
@@ -1683,6 +1772,24 @@ static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfi
       if (e >= f.length && blk0 < nblocks) return fail(JDS_EINVAL, "restart markers missing from the scan data (DRI %lld)", ri);
     }
   }
+  return JDS_OK;
+}
+
+// Upload one parsed file and decode it into c->ent_cf (device coefficients).
+static int decode_file_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfif_info* info) {
+  hipStream_t s = c->stream;
+  HuffDecTab tabs[4];
+  for (int i = 0; i < 4; ++i) {
+    memset(&tabs[i], 0, sizeof tabs[i]);
+    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0)
+      return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
+  }
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<DecScan> sc;
+  std::vector<RstIv> ivs;
+  int rc = plain_descriptors(data, info, FilePlace{0, 0, 0, 0}, lane_max, sc, ivs);
+  if (rc) return rc;
   if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
   const int nsc = (int)sc.size();
   int max_ngrp = 0;
@@ -1757,10 +1864,61 @@ int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, 
   return JDS_OK;
 }
 
+// Appends the descriptors and lane intervals of a parsed file with one
+// interleaved scan (m: its MCU record, whose off[] hold the file's place in the
+// coefficient buffer).  Routing as plain_descriptors': no restart interval ->
+// one descriptor; intervals of at most lane_max blocks (Ri * blocks per MCU) ->
+// one lane of k_dec_rst each; longer ones -> one descriptor each.
+static int il_descriptors(const uint8_t* data, const jds_jpeg_info* info, const HdMcu& m, const FilePlace& pl,
+                          int lane_max, std::vector<DecScan>& sc, std::vector<RstIv>& ivs) {
+  const jds_jpeg_scan& f = info->scan[0];
+  if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
+  const long long nblocks = (long long)m.bpm * m.mcu_cols * m.mcu_rows;
+  if (nblocks > 0x7fffffffll) return fail(JDS_ENOTSUP, "scan of %lld blocks", nblocks);
+  const long long rib = (long long)f.restart_interval * m.bpm;
+  auto descriptor = [&](long long off, long long nbytes, long long blk0, long long nb) {
+    DecScan d{};
+    d.data_off = pl.data_off + off;
+    d.nbytes = nbytes;
+    d.coef_off = 0;
+    d.dcs_off = pl.dcs_off;
+    d.nblocks = (int)nb;
+    d.frame = pl.file;
+    d.file = pl.file;
+    d.blk_base = (int)blk0;
+    sc.push_back(d);
+  };
+  if (rib == 0) {
+    descriptor(f.offset, f.length, 0, nblocks);
+    return JDS_OK;
+  }
+  const uint8_t* d = data + f.offset;
+  long long a = 0, blk0 = 0;
+  while (blk0 < nblocks) {
+    const long long e = next_rst(d, a, f.length);
+    const long long nb = nblocks - blk0 < rib ? nblocks - blk0 : rib;
+    if (rib <= lane_max) {
+      if (e - a > 0x7fffffffll) return fail(JDS_ENOTSUP, "restart interval of %lld bytes", e - a);
+      RstIv v{};
+      v.data_off = pl.data_off + f.offset + a;
+      v.coef_off = blk0;
+      v.nbytes = (int)(e - a);
+      v.nblk = (int)nb;
+      v.frame = pl.file;
+      v.file = pl.file;
+      ivs.push_back(v);
+    } else {
+      descriptor(f.offset + a, e - a, blk0, nb);
+    }
+    blk0 += nb;
+    a = e + 2;
+    if (e >= f.length && blk0 < nblocks)
+      return fail(JDS_EINVAL, "restart markers missing from the scan data (DRI %d)", f.restart_interval);
+  }
+  return JDS_OK;
+}
+
 // Upload a parsed file with one interleaved scan and decode it into c->ent_cf.
-// Routing as decode_file_dev's: no restart interval -> one descriptor; intervals
-// of at most lane_max blocks (Ri * blocks per MCU) -> one lane of k_dec_rst
-// each; longer ones -> one descriptor each.
 static int decode_il_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
   hipStream_t s = c->stream;
   HuffDecTab tabs[4];
@@ -1770,52 +1928,13 @@ static int decode_il_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_
       return fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
   }
   const HdMcu m = hd_jpeg_mcu(info);
-  const jds_jpeg_scan& f = info->scan[0];
-  if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
   const long long nblocks = (long long)m.bpm * m.mcu_cols * m.mcu_rows;
-  if (nblocks > 0x7fffffffll) return fail(JDS_ENOTSUP, "scan of %lld blocks", nblocks);
   int lane_max;
   rst_constants(&lane_max);
   std::vector<DecScan> sc;
   std::vector<RstIv> ivs;
-  const long long rib = (long long)f.restart_interval * m.bpm;
-  auto descriptor = [&](long long off, long long nbytes, long long blk0, long long nb) {
-    DecScan d{};
-    d.data_off = off;
-    d.nbytes = nbytes;
-    d.coef_off = 0;
-    d.nblocks = (int)nb;
-    d.frame = 0;
-    d.blk_base = (int)blk0;
-    sc.push_back(d);
-  };
-  if (rib == 0) {
-    descriptor(f.offset, f.length, 0, nblocks);
-  } else {
-    const uint8_t* d = data + f.offset;
-    long long a = 0, blk0 = 0;
-    while (blk0 < nblocks) {
-      long long e = a;
-      while (e < f.length && !(d[e] == 0xFF && e + 1 < f.length && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
-      const long long nb = nblocks - blk0 < rib ? nblocks - blk0 : rib;
-      if (rib <= lane_max) {
-        if (e - a > 0x7fffffffll) return fail(JDS_ENOTSUP, "restart interval of %lld bytes", e - a);
-        RstIv v{};
-        v.data_off = f.offset + a;
-        v.coef_off = blk0;
-        v.nbytes = (int)(e - a);
-        v.nblk = (int)nb;
-        v.frame = 0;
-        ivs.push_back(v);
-      } else {
-        descriptor(f.offset + a, e - a, blk0, nb);
-      }
-      blk0 += nb;
-      a = e + 2;
-      if (e >= f.length && blk0 < nblocks)
-        return fail(JDS_EINVAL, "restart markers missing from the scan data (DRI %d)", f.restart_interval);
-    }
-  }
+  int rc = il_descriptors(data, info, m, FilePlace{0, 0, 0, 0}, lane_max, sc, ivs);
+  if (rc) return rc;
   if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
   const int nsc = (int)sc.size();
   int max_ngrp = 0;
@@ -1856,6 +1975,28 @@ static int decode_il_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_
   return JDS_OK;
 }
 
+// A file of three non-interleaved scans in the terms of the first decoder.
+static void jfif_view(const jds_jpeg_info* info, jds_jfif_info* fi) {
+  memset(fi, 0, sizeof *fi);
+  fi->H = info->H;
+  fi->W = info->W;
+  fi->subsampling = info->subsampling;
+  fi->n_scans = 3;
+  for (int i = 0; i < 3; ++i) {
+    const jds_jpeg_scan& f = info->scan[i];
+    fi->scan[i].component = f.component[0];
+    fi->scan[i].dc_table = f.dc_table[0];
+    fi->scan[i].ac_table = f.ac_table[0];
+    fi->scan[i].restart_interval = f.restart_interval;
+    fi->scan[i].offset = f.offset;
+    fi->scan[i].length = f.length;
+  }
+  memcpy(fi->huff, info->huff, sizeof fi->huff);
+  fi->y_blocks = info->grid_cols[0] * info->grid_rows[0];
+  fi->c_blocks = info->grid_cols[1] * info->grid_rows[1];
+  fi->coeffs_needed = info->coeffs_needed;
+}
+
 // A parsed file of either scan form into c->ent_cf.
 static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
   int rc;
@@ -1865,24 +2006,7 @@ static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpe
     // three non-interleaved scans: the existing route, over the T.81 grids (a
     // non-interleaved scan holds exactly its component's grid, T.81 A.2.2)
     jds_jfif_info fi;
-    memset(&fi, 0, sizeof fi);
-    fi.H = info->H;
-    fi.W = info->W;
-    fi.subsampling = info->subsampling;
-    fi.n_scans = 3;
-    for (int i = 0; i < 3; ++i) {
-      const jds_jpeg_scan& f = info->scan[i];
-      fi.scan[i].component = f.component[0];
-      fi.scan[i].dc_table = f.dc_table[0];
-      fi.scan[i].ac_table = f.ac_table[0];
-      fi.scan[i].restart_interval = f.restart_interval;
-      fi.scan[i].offset = f.offset;
-      fi.scan[i].length = f.length;
-    }
-    memcpy(fi.huff, info->huff, sizeof fi.huff);
-    fi.y_blocks = info->grid_cols[0] * info->grid_rows[0];
-    fi.c_blocks = info->grid_cols[1] * info->grid_rows[1];
-    fi.coeffs_needed = info->coeffs_needed;
+    jfif_view(info, &fi);
     rc = decode_file_dev(c, data, len, &fi);
     info->status = fi.status;
     info->rounds = fi.rounds;
@@ -2007,6 +2131,295 @@ int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_
   jpeg_inv_window(d0, d1, 1.0 / ((double)dst_n / (double)src_n), src_n, xaxis != 0, &out[0], &out[1]);
   out[2] = JI_CAP_ROWS2;
   out[3] = JI_CAP_COLS2;
+  return JDS_OK;
+}
+
+// ------------------------------------------- batches of foreign files --
+// (DESIGN.md "Batches of foreign files")
+
+// What the layout keeps per batch: the parsed files, the inverse records of the
+// ones that take part (in batch order) and the tile maps of the three launches.
+struct BatchPlan {
+  std::vector<jds_jpeg_info> info;  // per file
+  std::vector<int> rec_of;          // per file: its record, or -1
+  std::vector<int> file_of;         // per record: its file
+  std::vector<JInvRec> recs;
+  std::vector<JInvMap> map[3];
+  int64_t rgb_bytes = 0, coef_entries = 0;
+  int first_bad = -1;
+  char first_msg[400] = "";
+};
+
+// Parse every file, check what the single call checks before it decodes, and
+// lay the outputs out: images JI_RGB_ALIGN apart at least, coefficients end to
+// end.  A file that fails takes no space and does not stop the batch.
+static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                        BatchPlan& bp) {
+  if (n < 0 || (n > 0 && (!data || !lens || !items))) return fail(JDS_EINVAL, "null argument");
+  bp.info.resize((size_t)n);
+  bp.rec_of.assign((size_t)n, -1);
+  std::vector<JInvRec> parsed((size_t)n);
+  std::vector<std::string> msg((size_t)n);  // (the message of a failing file: g_err is per thread)
+  batch_parallel(n, [&](int i) {
+    jds_jpeg_batch_item& it = items[i];
+    memset(&it, 0, sizeof it);
+    it.rgb_off = -1;
+    it.coef_off = -1;
+    jds_jpeg_info& info = bp.info[(size_t)i];
+    JInvRec& r = parsed[(size_t)i];
+    memset(&r, 0, sizeof r);
+    int rc = data[i] && lens[i] >= 0 ? jds_jpeg_parse(data[i], lens[i], &info) : fail(JDS_EINVAL, "null file");
+    if (rc == JDS_OK) {
+      it.H = info.H;
+      it.W = info.W;
+      it.subsampling = info.subsampling;
+      it.interleaved = info.interleaved;
+      rc = jpeg_inv_args(&info, &r.a);
+    }
+    if (rc == JDS_OK) {
+      HuffDecTab t;
+      for (int k = 0; k < 4 && rc == JDS_OK; ++k)
+        if (info.huff[k].defined && hd_build(info.huff[k].bits, info.huff[k].vals, &t) < 0)
+          rc = fail(JDS_EINVAL, "DHT: BITS over-subscribe the code space");
+    }
+    it.rc = rc;
+    if (rc != JDS_OK) msg[(size_t)i] = g_err;
+  });
+  for (int i = 0; i < n; ++i) {
+    jds_jpeg_batch_item& it = items[i];
+    const jds_jpeg_info& info = bp.info[(size_t)i];
+    JInvRec& r = parsed[(size_t)i];
+    if (it.rc != JDS_OK) {
+      if (bp.first_bad < 0) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", msg[(size_t)i].c_str());
+      }
+      continue;
+    }
+    long long rb = bp.rgb_bytes, ce = bp.coef_entries;
+    jinv_batch_place(r, (int)bp.recs.size(), info.coeffs_needed, &rb, &ce);
+    bp.rgb_bytes = rb;
+    bp.coef_entries = ce;
+    it.rgb_off = r.rgb_off;
+    it.coef_off = r.coef_off;
+    it.coeffs_needed = info.coeffs_needed;
+    bp.rec_of[(size_t)i] = r.st;
+    bp.file_of.push_back(i);
+    bp.recs.push_back(r);
+  }
+  // what the grids and the 32-bit indices of the kernels take
+  if (bp.coef_entries / 64 > 0x7fffffffll || !jinv_batch_maps(bp.recs.data(), (int)bp.recs.size(), bp.map))
+    return fail(JDS_ENOTSUP, "batch of %d files: too many blocks or tiles for one set of launches", n);
+  return JDS_OK;
+}
+
+// The first failing file by index, where jds_last_error finds it.
+static void batch_note(const BatchPlan& bp) {
+  if (bp.first_bad >= 0) {
+    char m[400];
+    snprintf(m, sizeof m, "%s", bp.first_msg);
+    fail(0, "file %d: %s", bp.first_bad, m);
+  } else {
+    g_err[0] = 0;
+  }
+}
+
+int jds_jpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                          int64_t* rgb_bytes, int64_t* coef_entries) {
+  if (!rgb_bytes || !coef_entries) return fail(JDS_EINVAL, "null argument");
+  BatchPlan bp;
+  const int rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  *rgb_bytes = bp.rgb_bytes;
+  *coef_entries = bp.coef_entries;
+  batch_note(bp);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                            uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items) {
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  BatchPlan bp;
+  const int rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
+    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+  std::vector<int16_t> own;
+  if (!coeffs) {
+    own.resize((size_t)bp.coef_entries);
+    coeffs = own.data();
+  }
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<uint32_t> st(bp.recs.size() + 1, 0u);
+  for (size_t k = 0; k < bp.recs.size(); ++k) {
+    const int i = bp.file_of[k];
+    int32_t rounds[3];
+    st[k] = hd_jpeg_host_decode(data[i], &bp.info[(size_t)i], subseq_bits, lane_max, coeffs + bp.recs[k].coef_off, rounds);
+    items[i].status = st[k];
+  }
+  const JInvMap* maps[3] = {bp.map[0].data(), bp.map[1].data(), bp.map[2].data()};
+  const int nmap[3] = {(int)bp.map[0].size() - 1, (int)bp.map[1].size() - 1, (int)bp.map[2].size() - 1};
+  jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  batch_note(bp);
+  return JDS_OK;
+}
+
+int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                          int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                          uint32_t* rounds_out) {
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  BatchPlan bp;
+  int rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  if (rounds_out) *rounds_out = 0;
+  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
+    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+  const int nv = (int)bp.recs.size();
+  if (nv == 0) {
+    batch_note(bp);
+    return JDS_OK;
+  }
+  hipStream_t s = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  int lane_max;
+  rst_constants(&lane_max);
+  const int rst_g = rst_group_lanes();
+  // the upload: every part at a 256-byte boundary, files at 16-byte ones inside theirs
+  auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+  std::vector<size_t> foff((size_t)nv);
+  size_t o = 0;
+  for (int k = 0; k < nv; ++k) {
+    foff[(size_t)k] = o;
+    o = up(o + (size_t)lens[bp.file_of[(size_t)k]], 16);
+  }
+  // descriptors of both decode groups, lane intervals of both forms (a file's padded to whole workgroups)
+  std::vector<DecScan> sc_il, sc_pl;
+  std::vector<RstIv> iv_il, iv_pl;
+  std::vector<HuffDecTab> tabs(4 * (size_t)nv);
+  std::vector<HdMcu> mcus((size_t)nv);
+  std::vector<uint32_t> st0((size_t)nv, 0u);
+  long long dcs_n = 0;
+  for (int k = 0; k < nv; ++k) {
+    const int i = bp.file_of[(size_t)k];
+    const jds_jpeg_info& info = bp.info[(size_t)i];
+    for (int t = 0; t < 4; ++t) {
+      memset(&tabs[4 * (size_t)k + t], 0, sizeof(HuffDecTab));
+      if (info.huff[t].defined) (void)hd_build(info.huff[t].bits, info.huff[t].vals, &tabs[4 * (size_t)k + t]);
+    }
+    memset(&mcus[(size_t)k], 0, sizeof(HdMcu));
+    const FilePlace pl{k, (long long)foff[(size_t)k], bp.recs[(size_t)k].coef_off, dcs_n};
+    std::vector<DecScan>& sc = info.interleaved ? sc_il : sc_pl;
+    std::vector<RstIv>& iv = info.interleaved ? iv_il : iv_pl;
+    const size_t nsc0 = sc.size(), niv0 = iv.size();
+    if (info.interleaved) {
+      HdMcu m = hd_jpeg_mcu(&info);
+      for (int cc = 0; cc < 3; ++cc) m.off[cc] += pl.coef_off;
+      mcus[(size_t)k] = m;
+      rc = il_descriptors(data[i], &info, m, pl, lane_max, sc, iv);
+      dcs_n += (long long)m.bpm * m.mcu_cols * m.mcu_rows;
+    } else {
+      jds_jfif_info fi;
+      jfif_view(&info, &fi);
+      rc = plain_descriptors(data[i], &fi, pl, lane_max, sc, iv);
+    }
+    if (rc == JDS_EINVAL) {  // restart markers missing from the scan data: a defective scan, nothing of it is decoded
+      sc.resize(nsc0);
+      iv.resize(niv0);
+      st0[(size_t)k] = HD_RESTART;
+      rc = JDS_OK;
+    }
+    if (rc) return rc;
+    while (iv.size() % (size_t)rst_g) {
+      RstIv v{};
+      v.file = v.frame = k;
+      iv.push_back(v);
+    }
+  }
+  if (sc_il.size() > 0x7fffffffull || sc_pl.size() > 0x7fffffffull || iv_il.size() > 0x7fffffffull ||
+      iv_pl.size() > 0x7fffffffull)
+    return fail(JDS_ENOTSUP, "too many restart intervals");
+  int mx_il = 0, mx_pl = 0;
+  const long long ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
+  const long long ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
+  if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
+  int map_off[3], nmap[3], tiles[3], nm = 0;
+  for (int m = 0; m < 3; ++m) {
+    map_off[m] = nm;
+    nmap[m] = (int)bp.map[m].size() - 1;
+    tiles[m] = bp.map[m].back().tile0;
+    nm += (int)bp.map[m].size();
+  }
+  const size_t o_files = 0, o_tabs = up(o, 256), o_mcu = up(o_tabs + sizeof(HuffDecTab) * tabs.size(), 256),
+               o_rec = up(o_mcu + sizeof(HdMcu) * mcus.size(), 256), o_map = up(o_rec + sizeof(JInvRec) * (size_t)nv, 256),
+               o_ivil = up(o_map + sizeof(JInvMap) * (size_t)nm, 256), o_ivpl = up(o_ivil + sizeof(RstIv) * iv_il.size(), 256),
+               o_st = up(o_ivpl + sizeof(RstIv) * iv_pl.size(), 256), total = up(o_st + 4 * (size_t)nv, 256);
+  if (total > c->bat_host_cap) {
+    if (c->bat_host) (void)hipHostFree(c->bat_host);
+    c->bat_host = nullptr;
+    c->bat_host_cap = 0;
+    HIP_TRY(hipHostMalloc(&c->bat_host, total, hipHostMallocDefault));
+    c->bat_host_cap = total;
+  }
+  char* h = (char*)c->bat_host;
+  batch_parallel(nv, [&](int k) {
+    const int i = bp.file_of[(size_t)k];
+    memcpy(h + o_files + foff[(size_t)k], data[i], (size_t)lens[i]);
+  });
+  memcpy(h + o_tabs, tabs.data(), sizeof(HuffDecTab) * tabs.size());
+  memcpy(h + o_mcu, mcus.data(), sizeof(HdMcu) * mcus.size());
+  memcpy(h + o_rec, bp.recs.data(), sizeof(JInvRec) * (size_t)nv);
+  for (int m = 0; m < 3; ++m)
+    memcpy(h + o_map + sizeof(JInvMap) * (size_t)map_off[m], bp.map[m].data(), sizeof(JInvMap) * bp.map[m].size());
+  if (!iv_il.empty()) memcpy(h + o_ivil, iv_il.data(), sizeof(RstIv) * iv_il.size());
+  if (!iv_pl.empty()) memcpy(h + o_ivpl, iv_pl.data(), sizeof(RstIv) * iv_pl.size());
+  memcpy(h + o_st, st0.data(), 4 * (size_t)nv);
+  const size_t scr_il = (dec_scratch_bytes(ng_il, (int)sc_il.size()) + 255) & ~(size_t)255;
+  HIP_TRY(c->bat.ensure(total));
+  HIP_TRY(c->dec_scr.ensure(scr_il + dec_scratch_bytes(ng_pl, (int)sc_pl.size())));
+  HIP_TRY(c->dec_mcu.ensure(sizeof(int16_t) * (size_t)dcs_n));
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)bp.coef_entries));
+  uint8_t* dst = rgb;
+  if (!rgb_on_device) {
+    HIP_TRY(c->out.ensure((size_t)bp.rgb_bytes));
+    dst = (uint8_t*)c->out.p;
+  }
+  char* dv = (char*)c->bat.p;
+  const CtxMarkScope marks_(c, s);
+  HIP_TRY(hipMemcpyAsync(dv, h, total, hipMemcpyHostToDevice, s));
+  if (dcs_n) HIP_TRY(hipMemsetAsync(c->dec_mcu.p, 0, sizeof(int16_t) * (size_t)dcs_n, s));
+  kmark(s, "(batch upload)");
+  const uint8_t* files_d = (const uint8_t*)(dv + o_files);
+  const HuffDecTab* tabs_d = (const HuffDecTab*)(dv + o_tabs);
+  const HdMcu* mcu_d = (const HdMcu*)(dv + o_mcu);
+  uint32_t* st_d = (uint32_t*)(dv + o_st);
+  int16_t* cf_d = (int16_t*)c->ent_cf.p;
+  const DecGroup grp[2] = {{sc_il.data(), (int)sc_il.size(), ng_il, mx_il, c->dec_scr.p, true},
+                           {sc_pl.data(), (int)sc_pl.size(), ng_pl, mx_pl, (char*)c->dec_scr.p + scr_il, false}};
+  unsigned rounds = 0;
+  int too_many = 0;
+  HIP_TRY(dec_run_groups(files_d, grp, 2, tabs_d, cf_d, bp.coef_entries, st_d, s, &rounds, &too_many, mcu_d,
+                         (int16_t*)c->dec_mcu.p));
+  if (too_many)
+    return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
+  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivil), (long long)iv_il.size(), tabs_d, cf_d, st_d, s, mcu_d));
+  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivpl), (long long)iv_pl.size(), tabs_d, cf_d, st_d, s, nullptr));
+  HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles, st_d,
+                                cf_d, dst, s));
+  if (!rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
+    for (int k = 0; k < nv; ++k) {
+      const JInvRec& r = bp.recs[(size_t)k];
+      HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)r.a.H * (size_t)r.a.W * 3, hipMemcpyDeviceToHost,
+                             s));
+    }
+  if (coeffs)
+    HIP_TRY(hipMemcpyAsync(coeffs, cf_d, sizeof(int16_t) * (size_t)bp.coef_entries, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(st0.data(), st_d, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
+  kmark(s, "(batch download)");
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < nv; ++k) items[bp.file_of[(size_t)k]].status = st0[(size_t)k];
+  if (rounds_out) *rounds_out = rounds;
+  batch_note(bp);
   return JDS_OK;
 }
 

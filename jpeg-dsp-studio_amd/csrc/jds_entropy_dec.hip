@@ -363,7 +363,7 @@ __global__ void __launch_bounds__(DEC_G) k_dec_sync(const uint8_t* __restrict__ 
     }
   }
   if constexpr (IL)
-    load_il(s_tab, s_mcu, tabs, mcu, DEC_G);
+    load_il(s_tab, s_mcu, tabs + 4 * sc.file, mcu + sc.file, DEC_G);
   else
     load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
   const DecLdsSrc src = dec_stage(s_win, d, n, (long long)gl * DEC_G * (DEC_S / 8));
@@ -458,7 +458,7 @@ __global__ void __launch_bounds__(DEC_G) k_dec_write(const uint8_t* __restrict__
   const long long i = (long long)(g - sc.grp0) * DEC_G + t;
   const size_t slot = (size_t)g * DEC_G + t;
   if constexpr (IL)
-    load_il(s_tab, s_mcu, tabs, mcu, DEC_G);
+    load_il(s_tab, s_mcu, tabs + 4 * sc.file, mcu + sc.file, DEC_G);
   else
     load_tabs(s_tab, tabs, sc.dc_tab, sc.ac_tab);
   if (t < 64) s_zz[t] = c_dec_zz[t];
@@ -470,7 +470,7 @@ __global__ void __launch_bounds__(DEC_G) k_dec_write(const uint8_t* __restrict__
   if constexpr (IL) {
     // blk < nblocks keeps base + blk inside the scan's MCUs: the staging array and hd_il_place's grids
     const HdMcu* m = reinterpret_cast<const HdMcu*>(s_mcu);
-    HdIlSink sink{m, coeffs + sc.coef_off, dcs, s_zz, (int64_t)sc.blk_base};
+    HdIlSink sink{m, coeffs + sc.coef_off, dcs + sc.dcs_off, s_zz, (int64_t)sc.blk_base};
     fl = hd_write_lane(src, HdIl{s_tab, m}, entry[slot], (unsigned long long)(i + 1) * DEC_S, (int64_t)blk0[slot],
                        (int64_t)sc.nblocks, i == sc.nsub - 1, sink);
   } else {
@@ -526,6 +526,8 @@ __global__ void __launch_bounds__(1024) k_dec_dc_mcu(const DecScan* __restrict__
   const DecScan sc = scans[blockIdx.x];
   if (sc.nblocks == 0) return;
   const int c = blockIdx.y;  // (uniform: the descriptor's fields below are scalar loads)
+  mcu += sc.file;
+  dcs += sc.dcs_off;
   const int bpm = mcu->bpm, hs = mcu->hs[c], vs = mcu->vs[c], cnt = hs * vs, first = mcu->first[c];
   const int gw = mcu->gw[c], gh = mcu->gh[c], cols = mcu->mcu_cols;
   int16_t* cf = coeffs + sc.coef_off + mcu->off[c];
@@ -582,69 +584,108 @@ hipError_t launch_dec_hdr(const uint8_t* files, long long stride, const unsigned
   return hipGetLastError();
 }
 
-// The decode of host-described scans (sc: nscans entries laid out by
-// dec_layout, ngroups workgroups, the longest scan max_ngrp): uploads the
+// The decode of host-described scans, in up to two groups: descriptors of
+// interleaved scans and of non-interleaved ones are different instantiations and
+// cannot share a launch (a batch of files of both forms has both groups; every
+// other caller has one).  A group: nscans entries laid out by dec_layout, ngroups
+// workgroups, the longest scan max_ngrp, its own scratch.  Uploads the
 // descriptors, zero-fills n_coeffs coefficients, synchronises between
-// propagation rounds.  *too_many: the round bound was exceeded (a bug, not a
-// property of any input).  status must hold the frames' initial words.
-hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
-                   const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
-                   hipStream_t s, unsigned* rounds, int* too_many, const HdMcu* mcu_dev, int16_t* dcs) {
+// propagation rounds: the groups' round loops run in step on one `changed`
+// counter and one host read per round, so *rounds is the largest any scan of
+// either group needs.  A group that has settled early is launched again (its
+// workgroups see no changed hand-off and return).  *too_many: the round bound
+// was exceeded (a bug, not a property of any input).  status must hold the
+// frames' initial words.
+hipError_t dec_run_groups(const uint8_t* files, const DecGroup* grp, int ngrp, const HuffDecTab* tabs_dev,
+                          int16_t* coeffs, long long n_coeffs, uint32_t* status, hipStream_t s, unsigned* rounds,
+                          int* too_many, const HdMcu* mcu_dev, int16_t* dcs) {
   *rounds = 0;
   *too_many = 0;
   hipError_t e = hipMemsetAsync(coeffs, 0, sizeof(int16_t) * (size_t)n_coeffs, s);
-  if (e != hipSuccess || ngroups == 0) return e;
-  const DecScratch d = dec_scratch(scratch, ngroups, nscans);
-  int* gs = (int*)malloc(4 * (size_t)ngroups);
-  if (!gs) return hipErrorOutOfMemory;
-  for (int i = 0; i < nscans; ++i)
-    for (int g = 0; g < sc[i].ngrp; ++g) gs[sc[i].grp0 + g] = i;
-  e = hipMemcpyAsync(d.scans, sc, sizeof(DecScan) * (size_t)nscans, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d.grp_scan, gs, 4 * (size_t)ngroups, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);  // gs is freed below
-  free(gs);
   if (e != hipSuccess) return e;
-  const unsigned grid = (unsigned)ngroups;
+  DecScratch d[2];
+  const DecGroup* act[2];
+  int na = 0, bound = 0;
+  for (int i = 0; i < ngrp && na < 2; ++i)
+    if (grp[i].ngroups > 0) {
+      d[na] = dec_scratch(grp[i].scratch, grp[i].ngroups, grp[i].nscans);
+      bound = grp[i].max_ngrp > bound ? grp[i].max_ngrp : bound;
+      act[na++] = &grp[i];
+    }
+  if (na == 0) return hipSuccess;
+  std::vector<int> gs[2];
+  for (int a = 0; a < na; ++a) {
+    const DecGroup& G = *act[a];
+    gs[a].resize((size_t)G.ngroups);
+    for (int i = 0; i < G.nscans; ++i)
+      for (int g = 0; g < G.sc[i].ngrp; ++g) gs[a][G.sc[i].grp0 + g] = i;
+    e = hipMemcpyAsync(d[a].scans, G.sc, sizeof(DecScan) * (size_t)G.nscans, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(d[a].grp_scan, gs[a].data(), 4 * (size_t)G.ngroups, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) break;
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);  // gs is released at return
+  if (e != hipSuccess) return e;
+  if (e2 != hipSuccess) return e2;
+  unsigned* changed = d[0].changed;
   for (int r = 0;; ++r) {
-    if (r >= max_ngrp) {  // entries of workgroups 0..r are settled after launch r
+    if (r >= bound) {  // entries of workgroups 0..r are settled after launch r
       *too_many = 1;
       return hipSuccess;
     }
-    if ((e = hipMemsetAsync(d.changed, 0, 4, s)) != hipSuccess) return e;
-    if (mcu_dev) {
-      hipLaunchKernelGGL(k_dec_sync<true>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev,
-                         d.entry, d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r, mcu_dev);
-      kmark(s, "k_dec_sync_il");
-    } else {
-      hipLaunchKernelGGL(k_dec_sync<false>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev,
-                         d.entry, d.exitv, d.nblk, d.gx[(r & 1) ^ 1], d.gx[r & 1], d.changed, r, mcu_dev);
-      kmark(s, "k_dec_sync");
+    if ((e = hipMemsetAsync(changed, 0, 4, s)) != hipSuccess) return e;
+    for (int a = 0; a < na; ++a) {
+      const unsigned grid = (unsigned)act[a]->ngroups;
+      if (act[a]->il) {
+        hipLaunchKernelGGL(k_dec_sync<true>, dim3(grid), dim3(DEC_G), 0, s, files, d[a].scans, d[a].grp_scan, tabs_dev,
+                           d[a].entry, d[a].exitv, d[a].nblk, d[a].gx[(r & 1) ^ 1], d[a].gx[r & 1], changed, r,
+                           mcu_dev);
+        kmark(s, "k_dec_sync_il");
+      } else {
+        hipLaunchKernelGGL(k_dec_sync<false>, dim3(grid), dim3(DEC_G), 0, s, files, d[a].scans, d[a].grp_scan,
+                           tabs_dev, d[a].entry, d[a].exitv, d[a].nblk, d[a].gx[(r & 1) ^ 1], d[a].gx[r & 1], changed,
+                           r, mcu_dev);
+        kmark(s, "k_dec_sync");
+      }
+      if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
     unsigned ch = 0;
-    if ((e = hipMemcpyAsync(&ch, d.changed, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&ch, changed, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     *rounds = (unsigned)(r + 1);
     if (!ch) break;
   }
-  hipLaunchKernelGGL(k_dec_prefix, dim3(nscans), dim3(1024), 0, s, d.scans, d.nblk, d.blk0);
-  kmark(s, "k_dec_prefix");
-  if (mcu_dev) {  // an interleaved scan's descriptors (the whole scan, or its long restart intervals)
-    hipLaunchKernelGGL(k_dec_write<true>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
-                       d.blk0, coeffs, status, mcu_dev, dcs);
-    kmark(s, "k_dec_write_il");
+  for (int a = 0; a < na; ++a) {
+    const DecGroup& G = *act[a];
+    const unsigned grid = (unsigned)G.ngroups;
+    hipLaunchKernelGGL(k_dec_prefix, dim3(G.nscans), dim3(1024), 0, s, d[a].scans, d[a].nblk, d[a].blk0);
+    kmark(s, "k_dec_prefix");
+    if (G.il) {  // an interleaved scan's descriptors (the whole scan, or its long restart intervals)
+      hipLaunchKernelGGL(k_dec_write<true>, dim3(grid), dim3(DEC_G), 0, s, files, d[a].scans, d[a].grp_scan, tabs_dev,
+                         d[a].entry, d[a].blk0, coeffs, status, mcu_dev, dcs);
+      kmark(s, "k_dec_write_il");
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_dec_dc_mcu, dim3(G.nscans, 3), dim3(1024), 0, s, d[a].scans, mcu_dev, dcs, coeffs, status);
+      kmark(s, "k_dec_dc_mcu");
+    } else {
+      hipLaunchKernelGGL(k_dec_write<false>, dim3(grid), dim3(DEC_G), 0, s, files, d[a].scans, d[a].grp_scan, tabs_dev,
+                         d[a].entry, d[a].blk0, coeffs, status, mcu_dev, dcs);
+      kmark(s, "k_dec_write");
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_dec_dc, dim3(G.nscans), dim3(1024), 0, s, d[a].scans, coeffs, status);
+      kmark(s, "k_dec_dc");
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dec_dc_mcu, dim3(nscans, 3), dim3(1024), 0, s, d.scans, mcu_dev, dcs, coeffs, status);
-    kmark(s, "k_dec_dc_mcu");
-    return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_dec_write<false>, dim3(grid), dim3(DEC_G), 0, s, files, d.scans, d.grp_scan, tabs_dev, d.entry,
-                     d.blk0, coeffs, status, mcu_dev, dcs);
-  kmark(s, "k_dec_write");
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_dec_dc, dim3(nscans), dim3(1024), 0, s, d.scans, coeffs, status);
-  kmark(s, "k_dec_dc");
-  return hipGetLastError();
+  return hipSuccess;
+}
+
+// One group: interleaved when mcu_dev is given.
+hipError_t dec_run(const uint8_t* files, const DecScan* sc, int nscans, long long ngroups, int max_ngrp,
+                   const HuffDecTab* tabs_dev, void* scratch, int16_t* coeffs, long long n_coeffs, uint32_t* status,
+                   hipStream_t s, unsigned* rounds, int* too_many, const HdMcu* mcu_dev, int16_t* dcs) {
+  const DecGroup g{sc, nscans, ngroups, max_ngrp, scratch, mcu_dev != nullptr};
+  return dec_run_groups(files, &g, 1, tabs_dev, coeffs, n_coeffs, status, s, rounds, too_many, mcu_dev, dcs);
 }
 
 // ------------------------------------------------- restart intervals --
@@ -680,6 +721,7 @@ constexpr int RST_G = 64;                       // intervals per workgroup: one 
 static_assert(RST_G == 64, "one wave: s_zz is filled by its 64 lanes");
 
 void rst_constants(int* lane_max) { *lane_max = RST_LANE_MAX; }
+int rst_group_lanes() { return RST_G; }
 
 // The row holds RST_ROW dwords of the interval from a dword-aligned address on;
 // a read outside it refills it (whole dwords inside the interval, single bytes
@@ -746,15 +788,16 @@ __global__ void __launch_bounds__(RST_G) k_dec_rst(const uint8_t* __restrict__ f
   __shared__ uint8_t s_zz[64];
   const int t = threadIdx.x;
   const long long i = (long long)blockIdx.x * RST_G + t;
+  const int file = ivs[(long long)blockIdx.x * RST_G].file;  // (the grid is ceil(niv / RST_G): inside the list)
   {
     constexpr int NW = (int)(4 * sizeof(HuffDecTab) / 4);
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(tabs);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(tabs + 4 * file);
     uint32_t* o = reinterpret_cast<uint32_t*>(s_tab);
     for (int j = t; j < NW; j += RST_G) o[j] = a[j];
   }
   s_zz[t] = c_dec_zz[t];
   if constexpr (IL) {
-    const uint32_t* b = reinterpret_cast<const uint32_t*>(mcu);
+    const uint32_t* b = reinterpret_cast<const uint32_t*>(mcu + file);
     for (int j = t; j < MCU_W; j += RST_G) s_mcu[j] = b[j];
   }
   RstIv iv{};

@@ -342,22 +342,42 @@ JDS_HDI uint32_t hd_write_lane(const Src& src, const TC& tc, uint64_t entry, uin
   return fl;
 }
 
-// One scan of one frame (host-built, jds_abi.hip).
+// One scan of one frame (host-built, jds_abi.hip).  A launch serves descriptors
+// of different files (jds_jpeg_batch_to_rgb): `file` selects the file's four
+// decode tables (tabs + 4 * file) and, interleaved, its MCU descriptor
+// (mcu + file), whose off[] then include the file's place in the batch's
+// coefficient buffer; a non-interleaved descriptor's dc_tab / ac_tab already
+// index the whole table array.  Single-file calls and plans leave file at 0.
 struct DecScan {
   long long data_off;  // the scan's stuffed bytes, from the files base
   long long nbytes;
   long long coef_off;  // the scan's first coefficient, from the coeffs base
+  long long dcs_off;   // interleaved: the file's first entry in the DC staging array
   int nblocks;
   int frame;
   int dc_tab, ac_tab;  // indices into the table array
   int grp0, ngrp;      // its workgroups
   int nsub;            // its subsequences
   int blk_base;        // interleaved: its first block's index in the scan's block order (whole MCUs); else 0
+  int file;            // table set (and MCU descriptor) of the descriptor's file
+};
+
+// The descriptors of one instantiation of the decode kernels (dec_run_groups):
+// laid out by dec_layout; scratch: dec_scratch_bytes(ngroups, nscans) device bytes.
+struct DecGroup {
+  const DecScan* sc;
+  int nscans;
+  long long ngroups;
+  int max_ngrp;
+  void* scratch;
+  bool il;  // interleaved scans: the <true> instantiations
 };
 
 // One restart interval of one frame (k_dec_rst): built on the host for a
 // parsed file, on the device (k_rst_scan) for a plan's batch.  nblk == 0: not
-// decoded (its frame is skipped).
+// decoded (its frame is skipped).  A workgroup of k_dec_rst stages one table set:
+// the RST_G intervals of a workgroup belong to one file (the first one's `file`;
+// a batch pads each file's intervals to whole workgroups with nblk == 0 entries).
 struct RstIv {
   long long data_off;  // the interval's stuffed bytes, from the files base
   long long coef_off;  // its first block's first coefficient, from the coeffs base (interleaved: its first
@@ -365,7 +385,9 @@ struct RstIv {
   int nbytes;
   int nblk;
   int frame;
-  int tabs;  // dc table index | ac table index << 8 (into the table array)
+  int tabs;  // dc table index | ac table index << 8 (into the file's four tables)
+  int file;  // table set (tabs + 4 * file) and, interleaved, MCU descriptor (mcu + file)
+  int pad_;
 };
 
 // What a plan knows about its restart files before it sees them.

@@ -21,14 +21,15 @@ static_assert(sizeof(JShared<JDS_SS_422>) <= 80 * 1024 && sizeof(JShared<JDS_SS_
 // One workgroup per tile, eight lanes per block (lane v: column v, then row v).
 // A block's two passes run on 8 lanes of one wave, whose LDS operations execute
 // in order: wave barriers (no instruction, a scheduling fence) between them, a
-// workgroup barrier only once the chroma window is complete.
+// workgroup barrier only once the chroma window is complete.  a: uniform -- the
+// kernel argument (k_jpeg_inv) or the image's record in global memory
+// (k_jpeg_inv_batch); either way its fields arrive by scalar loads.
 template <int SS>
-__global__ void __launch_bounds__(JI_NT)
-k_jpeg_inv(const JInvArgs a, const int16_t* __restrict__ coeffs, uint8_t* __restrict__ rgb) {
+__device__ __forceinline__ void jinv_tile_dev(JShared<SS>& sh, const JInvArgs& a, const int tile,
+                                              const int16_t* __restrict__ coeffs, uint8_t* __restrict__ rgb) {
   using C = JInvCfg<SS>;
-  __shared__ JShared<SS> sh;
   const int tid = threadIdx.x, v = tid & 7, lb = tid >> 3;
-  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const JWin w = jinv_tile_window<SS>(a, ty, tx);
   if (tid < 192) sh.q[tid] = a.q[tid >> 6][tid & 63];
   if (tid < JI_TW) jinv_xtap<SS>(sh, a, w, tid);
@@ -72,6 +73,43 @@ k_jpeg_inv(const JInvArgs a, const int16_t* __restrict__ coeffs, uint8_t* __rest
   jinv_colour_store(Yv, Cb, Cr, rgb + ((size_t)y * a.W + x0) * 3, nx);
 }
 
+template <int SS>
+__global__ void __launch_bounds__(JI_NT)
+k_jpeg_inv(const JInvArgs a, const int16_t* __restrict__ coeffs, uint8_t* __restrict__ rgb) {
+  __shared__ JShared<SS> sh;
+  jinv_tile_dev<SS>(sh, a, blockIdx.x, coeffs, rgb);
+}
+
+// The tiles of a batch's images of one subsampling mode (jds_jpeg_inv.hpp
+// "batches"): a workgroup finds its image in the launch's map, takes the image's
+// arguments, coefficient base and pixel base from its record, and runs the tile
+// core above.  An image whose status word is set (its scan data were defective:
+// the word is final, every decode kernel precedes this one on the stream) gets
+// zeros instead, so no host decision sits between decode and inverse.
+template <int SS>
+__global__ void __launch_bounds__(JI_NT)
+k_jpeg_inv_batch(const JInvRec* __restrict__ recs, const JInvMap* __restrict__ map, const int nmap,
+                 const uint32_t* __restrict__ status, const int16_t* __restrict__ coeffs,
+                 uint8_t* __restrict__ rgb) {
+  __shared__ JShared<SS> sh;
+  const int mi = jinv_find(map, nmap, (int)blockIdx.x);
+  const JInvRec& r = recs[map[mi].rec];
+  const int tile = (int)blockIdx.x - map[mi].tile0;
+  uint8_t* o = rgb + r.rgb_off;
+  if (status[r.st] != 0u) {  // (uniform)
+    const JInvArgs& a = r.a;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const JWin w = jinv_tile_window<SS>(a, ty, tx);
+    const int rb = 3 * (w.x1 - w.X0 + 1), nb = rb * (w.y1 - w.Y0 + 1);  // inside the image: <= 3 * JI_TW * JI_TH
+    for (int i = threadIdx.x; i < nb; i += JI_NT) {
+      const int y = i / rb;
+      o[((size_t)(w.Y0 + y) * a.W + w.X0) * 3 + (i - y * rb)] = 0;
+    }
+    return;
+  }
+  jinv_tile_dev<SS>(sh, r.a, tile, coeffs + r.coef_off, o);
+}
+
 void jpeg_inv_constants(int* th, int* tw) {
   *th = JI_TH;
   *tw = JI_TW;
@@ -94,6 +132,30 @@ hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rg
     k_jpeg_inv<JDS_SS_444><<<grid, block, 0, s>>>(a, coeffs, rgb);
   kmark(s, "k_jpeg_inv<%d>", a.ss);
   return hipGetLastError();
+}
+
+// The batch: one launch per mode present.  maps: the three modes' maps one
+// after another in device memory (map_off[m]: a mode's first entry; nmap[m]
+// images, tiles[m] tiles).
+hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[3], const int nmap[3],
+                                 const int tiles[3], const uint32_t* status, const int16_t* coeffs, uint8_t* rgb,
+                                 hipStream_t s) {
+  const dim3 block(JI_NT);
+  for (int m = 0; m < 3; ++m) {
+    if (nmap[m] < 1) continue;
+    const dim3 grid((unsigned)tiles[m]);
+    const JInvMap* mp = maps + map_off[m];
+    if (m == JDS_SS_420)
+      k_jpeg_inv_batch<JDS_SS_420><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
+    else if (m == JDS_SS_422)
+      k_jpeg_inv_batch<JDS_SS_422><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
+    else
+      k_jpeg_inv_batch<JDS_SS_444><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
+    kmark(s, "k_jpeg_inv_batch<%d>", m);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb) {

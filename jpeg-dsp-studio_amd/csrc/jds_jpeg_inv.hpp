@@ -19,6 +19,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "jds.h"
 #include "jds_dct8.hpp"
 
@@ -356,53 +358,156 @@ JDS_HDI void jinv_colour_store(const double (&Yv)[8], const double (&Cb)[8], con
   }
 }
 
-// The host tile loop: the kernel's steps with loops in place of lanes and of
-// the barriers between them.  No GPU.
+// One tile on the host: the kernel's steps with loops in place of lanes and of
+// the barriers between them.  sh.q holds the image's tables.  No GPU.
+template <int SS>
+inline void jinv_host_tile(JShared<SS>& sh, const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, int ty, int tx) {
+  using C = JInvCfg<SS>;
+  const JWin w = jinv_tile_window<SS>(a, ty, tx);
+  for (int k = 0; k < JI_TW; ++k) jinv_xtap<SS>(sh, a, w, k);
+  if (C::SX == 2)
+    for (int t0 = 0; t0 < 2 * w.ncbr * w.ncbc; t0 += JI_NB) {
+      for (int t = t0; t < t0 + JI_NB; ++t)
+        for (int v = 0; v < 8; ++v) jinv_chroma_col<SS>(sh, a, w, coeffs, t, v);
+      for (int t = t0; t < t0 + JI_NB; ++t)
+        for (int u = 0; u < 8; ++u) jinv_chroma_row<SS>(sh, a, w, t, u);
+    }
+  for (int lb = 0; lb < JI_NB; ++lb) {
+    int by, bx;
+    if (!jinv_luma_block(a, w, lb, &by, &bx)) continue;
+    double* mid = sh.mid + lb * JI_MS;
+    const long long boff = ((long long)by * a.gc[0] + bx) * 64;
+    double Yv[8][8], Cb[8][8], Cr[8][8];
+    for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[0] + boff, sh.q, v, mid);
+    for (int u = 0; u < 8; ++u) jinv_row(mid, u, Yv[u]);
+    if (C::SX == 1) {
+      for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[1] + boff, sh.q + 64, v, mid);
+      for (int u = 0; u < 8; ++u) jinv_row(mid, u, Cb[u]);
+      for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[2] + boff, sh.q + 128, v, mid);
+      for (int u = 0; u < 8; ++u) jinv_row(mid, u, Cr[u]);
+    }
+    for (int u = 0; u < 8; ++u) {
+      const int y = by * 8 + u, x0 = bx * 8;
+      if (y > w.y1) continue;
+      if (C::SX == 2) {
+        jinv_chroma_up<SS>(sh, a, w, y, x0, 0, Cb[u]);
+        jinv_chroma_up<SS>(sh, a, w, y, x0, 1, Cr[u]);
+      }
+      const int nx = w.x1 + 1 - x0 < 8 ? w.x1 + 1 - x0 : 8;
+      jinv_colour_store(Yv[u], Cb[u], Cr[u], rgb + ((size_t)y * a.W + x0) * 3, nx);
+    }
+  }
+}
+
+// The host tile loop of one image.
 template <int SS>
 inline void jinv_host_image(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb) {
-  using C = JInvCfg<SS>;
   JShared<SS>* shp = new JShared<SS>();  // (zeroed: the lanes past the image's right edge read finite samples)
-  JShared<SS>& sh = *shp;
   for (int c = 0; c < 3; ++c)
-    for (int i = 0; i < 64; ++i) sh.q[64 * c + i] = a.q[c][i];
+    for (int i = 0; i < 64; ++i) shp->q[64 * c + i] = a.q[c][i];
   for (int ty = 0; ty < a.tiles_y; ++ty)
-    for (int tx = 0; tx < a.tiles_x; ++tx) {
-      const JWin w = jinv_tile_window<SS>(a, ty, tx);
-      for (int k = 0; k < JI_TW; ++k) jinv_xtap<SS>(sh, a, w, k);
-      if (C::SX == 2)
-        for (int t0 = 0; t0 < 2 * w.ncbr * w.ncbc; t0 += JI_NB) {
-          for (int t = t0; t < t0 + JI_NB; ++t)
-            for (int v = 0; v < 8; ++v) jinv_chroma_col<SS>(sh, a, w, coeffs, t, v);
-          for (int t = t0; t < t0 + JI_NB; ++t)
-            for (int u = 0; u < 8; ++u) jinv_chroma_row<SS>(sh, a, w, t, u);
-        }
-      for (int lb = 0; lb < JI_NB; ++lb) {
-        int by, bx;
-        if (!jinv_luma_block(a, w, lb, &by, &bx)) continue;
-        double* mid = sh.mid + lb * JI_MS;
-        const long long boff = ((long long)by * a.gc[0] + bx) * 64;
-        double Yv[8][8], Cb[8][8], Cr[8][8];
-        for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[0] + boff, sh.q, v, mid);
-        for (int u = 0; u < 8; ++u) jinv_row(mid, u, Yv[u]);
-        if (C::SX == 1) {
-          for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[1] + boff, sh.q + 64, v, mid);
-          for (int u = 0; u < 8; ++u) jinv_row(mid, u, Cb[u]);
-          for (int v = 0; v < 8; ++v) jinv_col(coeffs + a.off[2] + boff, sh.q + 128, v, mid);
-          for (int u = 0; u < 8; ++u) jinv_row(mid, u, Cr[u]);
-        }
-        for (int u = 0; u < 8; ++u) {
-          const int y = by * 8 + u, x0 = bx * 8;
-          if (y > w.y1) continue;
-          if (C::SX == 2) {
-            jinv_chroma_up<SS>(sh, a, w, y, x0, 0, Cb[u]);
-            jinv_chroma_up<SS>(sh, a, w, y, x0, 1, Cr[u]);
-          }
-          const int nx = w.x1 + 1 - x0 < 8 ? w.x1 + 1 - x0 : 8;
-          jinv_colour_store(Yv[u], Cb[u], Cr[u], rgb + ((size_t)y * a.W + x0) * 3, nx);
-        }
-      }
-    }
+    for (int tx = 0; tx < a.tiles_x; ++tx) jinv_host_tile<SS>(*shp, a, coeffs, rgb, ty, tx);
   delete shp;
+}
+
+// ------------------------------------------------------------- batches --
+//
+// k_jpeg_inv_batch (DESIGN.md "Batches of foreign files"): one launch per
+// subsampling mode over the tiles of that mode's images.  The per-image records
+// live in a device array; a launch has a map of its images -- (first tile,
+// record) per image in batch order, closed by a sentinel holding the launch's
+// tile count -- and a workgroup finds its image by a binary search over the
+// first tiles (jinv_find: scalar loads, log2(images) steps).
+
+// One image of a batch: its launch arguments, where its coefficients and its
+// pixels start in the batch's buffers, and its status word (an image whose
+// decode set a bit there is not inverted: its pixels are zero).
+struct JInvRec {
+  JInvArgs a;
+  long long coef_off;  // entries from the batch's coefficient base
+  long long rgb_off;   // bytes from the batch's output base: a multiple of JI_RGB_ALIGN
+  int st;              // index of its status word
+  int pad_;
+};
+constexpr long long JI_RGB_ALIGN = 256;
+
+// The layout step: image k of a batch (its arguments in r.a) goes behind the
+// ones placed so far -- pixels at the next multiple of JI_RGB_ALIGN, coefficients
+// end to end -- and gets status word k.
+inline void jinv_batch_place(JInvRec& r, int k, long long coeffs_needed, long long* rgb_bytes, long long* coef_entries) {
+  r.coef_off = *coef_entries;
+  r.rgb_off = *rgb_bytes;
+  r.st = k;
+  *coef_entries += coeffs_needed;
+  const long long nimg = (long long)r.a.H * r.a.W * 3;
+  *rgb_bytes += (nimg + JI_RGB_ALIGN - 1) / JI_RGB_ALIGN * JI_RGB_ALIGN;
+}
+
+struct JInvMap {
+  int tile0;  // the image's first tile in its mode's launch (sentinel: the launch's tiles)
+  int rec;    // its record
+};
+
+// The map entry of tile t: the last i in [0, n) with map[i].tile0 <= t (n >= 1
+// images, map[0].tile0 == 0, t < map[n].tile0; an image has at least one tile).
+JDS_HDI int jinv_find(const JInvMap* map, int n, int t) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (map[mid].tile0 <= t)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// The host model of the batch launches: the same map walk and the same records
+// through jinv_host_tile; a flagged image's tiles are zero-filled.
+template <int SS>
+inline void jinv_host_batch_mode(const JInvRec* recs, const JInvMap* map, int nmap, const uint32_t* status,
+                                 const int16_t* coeffs, uint8_t* rgb) {
+  if (nmap < 1) return;
+  JShared<SS>* shp = new JShared<SS>();
+  for (int t = 0; t < map[nmap].tile0; ++t) {
+    const int mi = jinv_find(map, nmap, t);
+    const JInvRec& r = recs[map[mi].rec];
+    const JInvArgs& a = r.a;
+    const int lt = t - map[mi].tile0, ty = lt / a.tiles_x, tx = lt - ty * a.tiles_x;
+    uint8_t* o = rgb + r.rgb_off;
+    if (status[r.st]) {
+      const JWin w = jinv_tile_window<SS>(a, ty, tx);
+      for (int y = w.Y0; y <= w.y1; ++y) memset(o + ((size_t)y * a.W + w.X0) * 3, 0, 3 * (size_t)(w.x1 - w.X0 + 1));
+      continue;
+    }
+    for (int c = 0; c < 3; ++c)
+      for (int i = 0; i < 64; ++i) shp->q[64 * c + i] = a.q[c][i];
+    jinv_host_tile<SS>(*shp, a, coeffs + r.coef_off, o, ty, tx);
+  }
+  delete shp;
+}
+
+// map[m] / nmap[m]: the launch of subsampling code m (JDS_SS_444, _422, _420 = 0, 1, 2).
+inline void jpeg_inv_batch_host(const JInvRec* recs, const JInvMap* const map[3], const int nmap[3],
+                                const uint32_t* status, const int16_t* coeffs, uint8_t* rgb) {
+  jinv_host_batch_mode<JDS_SS_444>(recs, map[JDS_SS_444], nmap[JDS_SS_444], status, coeffs, rgb);
+  jinv_host_batch_mode<JDS_SS_422>(recs, map[JDS_SS_422], nmap[JDS_SS_422], status, coeffs, rgb);
+  jinv_host_batch_mode<JDS_SS_420>(recs, map[JDS_SS_420], nmap[JDS_SS_420], status, coeffs, rgb);
+}
+
+// The maps of a batch from its records (in batch order).  false: a mode's tiles
+// exceed what a grid and a 32-bit tile index take.
+inline bool jinv_batch_maps(const JInvRec* recs, int nrec, std::vector<JInvMap> (&map)[3]) {
+  long long tiles[3] = {0, 0, 0};
+  for (int m = 0; m < 3; ++m) map[m].clear();
+  for (int i = 0; i < nrec; ++i) {
+    const int m = recs[i].a.ss;
+    map[m].push_back(JInvMap{(int)tiles[m], i});
+    tiles[m] += (long long)recs[i].a.tiles_y * recs[i].a.tiles_x;
+    if (tiles[m] > 0x7fffffffll) return false;
+  }
+  for (int m = 0; m < 3; ++m) map[m].push_back(JInvMap{(int)tiles[m], -1});
+  return true;
 }
 
 }  // namespace jds

@@ -99,6 +99,12 @@ class JpegInfo(C.Structure):
                 ('huff', JfifHuff * 4), ('coeffs_needed', C.c_int64), ('status', C.c_uint32), ('rounds', C.c_uint32)]
 
 
+class JpegBatchItem(C.Structure):
+    _fields_ = [('rc', C.c_int32), ('status', C.c_uint32), ('H', C.c_int64), ('W', C.c_int64),
+                ('subsampling', C.c_int32), ('interleaved', C.c_int32), ('rgb_off', C.c_int64),
+                ('coef_off', C.c_int64), ('coeffs_needed', C.c_int64)]
+
+
 # frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
 DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE, DEC_RESTART = 1, 2, 4, 8, 16, 32, 64
 
@@ -129,6 +135,8 @@ _SIGS = {
     'jds_plan_profile': (C.c_int, [_P, C.c_int]),
     'jds_plan_profile_read': (C.c_int, [_P, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int),
                                         C.POINTER(C.c_double)]),
+    'jds_ctx_profile': (C.c_int, [_P, C.c_int]),
+    'jds_ctx_profile_read': (C.c_int, [_P, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     'jds_compress_reconstruct': (C.c_int, [_P, C.POINTER(Params), _P, C.c_int64, C.c_int64, _P, _P,
                                            C.POINTER(FrameStats), _P, _P, C.c_int32, C.c_int32,
                                            C.POINTER(SelectedBlock), C.POINTER(C.c_int32)]),
@@ -171,6 +179,11 @@ _SIGS = {
     'jds_jpeg_inverse_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P, _P]),
     'jds_jpeg_to_rgb': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegInfo)]),
     'jds_selftest_jpeg_inverse': (C.c_int, [C.POINTER(JpegInfo), _P, _P]),
+    'jds_jpeg_batch_layout': (C.c_int, [_P, _P, C.c_int32, C.POINTER(JpegBatchItem), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
+    'jds_jpeg_batch_to_rgb': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegBatchItem),
+                                        C.POINTER(C.c_uint32)]),
+    'jds_selftest_jpeg_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.POINTER(JpegBatchItem)]),
     'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
@@ -255,6 +268,17 @@ class Context:
     def set_ssim_scratch(self, nbytes: int = 0):
         """SSIM luma scratch budget per launch group (jds_ctx_set_ssim_scratch; 0 = default)."""
         check(lib().jds_ctx_set_ssim_scratch(self.handle, int(nbytes)))
+
+    def profile(self, enable: bool = True):
+        """Launch marks on the batch calls of this context (jds_ctx_profile)."""
+        check(lib().jds_ctx_profile(self.handle, 1 if enable else 0))
+
+    def profile_read(self):
+        """({name: (total_ms, launches)}, span_ms) of the calls since the last read."""
+        arr = (KernelTime * 64)()
+        n, span = C.c_int(0), C.c_double(0.0)
+        check(lib().jds_ctx_profile_read(self.handle, arr, 64, C.byref(n), C.byref(span)))
+        return {arr[i].name.decode(): (arr[i].total_ms, int(arr[i].launches)) for i in range(n.value)}, span.value
 
     def close(self):
         if self.handle:

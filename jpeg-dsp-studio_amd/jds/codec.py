@@ -211,6 +211,129 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None):
     return img, d
 
 
+def _batch_args(files):
+    """(keep-alive arrays, pointer array, length array) of a sequence of bytes-like files; an
+    empty one keeps its place with length 0 (the parser names it)."""
+    keep = []
+    for f in files:
+        a = np.ascontiguousarray(f, np.uint8).reshape(-1) if isinstance(f, np.ndarray) else np.frombuffer(bytes(f), np.uint8)
+        keep.append((a, a if a.size else np.zeros(1, np.uint8)))
+    n = len(keep)
+    ptrs = (C.c_void_p * max(n, 1))(*[k[1].ctypes.data for k in keep])
+    lens = (C.c_int64 * max(n, 1))(*[int(k[0].size) for k in keep])
+    return keep, ptrs, lens
+
+
+def _batch_item_dict(it) -> dict:
+    from . import entropy
+    ok = it.rc == 0
+    return {'rc': int(it.rc), 'status': int(it.status), 'H': int(it.H), 'W': int(it.W),
+            'mode': entropy._MODE_NAMES.get(int(it.subsampling)) if it.H > 0 else None,
+            'interleaved': bool(it.interleaved), 'rgb_off': int(it.rgb_off) if ok else -1,
+            'coef_off': int(it.coef_off) if ok else -1, 'coeffs_needed': int(it.coeffs_needed)}
+
+
+def jpeg_batch_layout(files):
+    """jds_jpeg_batch_layout (host only): (per-file dicts, rgb_bytes, coef_entries) of a batch.
+    A file's image is bytes [rgb_off, rgb_off + H*W*3) of the batch's output (rgb_off a multiple
+    of 256), its coefficients entries [coef_off, coef_off + coeffs_needed); a file that does not
+    parse has rc != 0 and takes no space."""
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    items = (_abi.JpegBatchItem * max(n, 1))()
+    rb, ce = C.c_int64(0), C.c_int64(0)
+    check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
+    return [_batch_item_dict(items[i]) for i in range(n)], int(rb.value), int(ce.value)
+
+
+def _batch_first_error(items) -> str:
+    msg = lib().jds_last_error().decode(errors='replace')
+    for i, it in enumerate(items):
+        if it['rc'] != 0:
+            return msg or f'file {i}: error {it["rc"]}'
+        if it['status'] != 0:
+            return f'file {i}: defective scan data (status 0x{it["status"]:x})'
+    return ''
+
+
+def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False, errors: str = 'raise', ctx=None):
+    """jds_jpeg_batch_to_rgb: a sequence of baseline JPEGs (bytes-likes; any mix of sizes,
+    subsampling modes, tables, restart intervals and scan forms) -> their images, decoded in one
+    set of launches; each image is byte for byte jpeg_to_rgb's.  out=None: a list of HxWx3 uint8
+    arrays; out='device': torch.uint8 tensors, views into one allocation on `device`; out a 1-D
+    uint8 device tensor of at least jpeg_batch_layout's rgb_bytes: views into that.  A file that
+    does not parse, or whose scan data are defective, does not stop the others: errors='raise'
+    raises ValueError naming the first such index after the batch has run, errors='return' puts
+    None in its place.  with_info: (images, {'items': per-file dicts, 'rounds': the batch's
+    propagation rounds, 'rgb_bytes', 'coef_entries'}).  ctx: a caller-owned Context of that device
+    (e.g. a profiled one) instead of a pooled one."""
+    if errors not in ('raise', 'return'):
+        raise ValueError("errors must be 'raise' or 'return'")
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    items = (_abi.JpegBatchItem * max(n, 1))()
+    if out is None or isinstance(out, str):
+        # the output is sized here, from the layout; a caller's buffer is checked by the call itself
+        rb, ce = C.c_int64(0), C.c_int64(0)
+        check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
+        cap = int(rb.value)
+    if out is None:
+        buf = np.empty(max(cap, 1), np.uint8)
+        dst, on_dev = buf.ctypes.data, 0
+    else:
+        if isinstance(out, str):
+            if out != 'device':
+                raise ValueError("out must be None, 'device' or a 1-D uint8 device tensor")
+            import torch
+            buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=f'cuda:{device}')
+        else:
+            buf = out
+            if buf.dim() != 1 or buf.element_size() != 1 or not buf.is_contiguous():
+                raise ValueError('out must be a contiguous 1-D uint8 device tensor')
+            cap = int(buf.numel())
+        dst, on_dev = int(buf.data_ptr()), 1
+    rounds = C.c_uint32(0)
+    if ctx is not None:
+        check(lib().jds_jpeg_batch_to_rgb(ctx.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
+                                          C.byref(rounds)))
+    else:
+        with lease(device) as c:
+            check(lib().jds_jpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
+                                              C.byref(rounds)))
+    info = [_batch_item_dict(items[i]) for i in range(n)]
+    first = _batch_first_error(info)
+    if first and errors == 'raise':
+        raise ValueError(first)
+    imgs = []
+    for it in info:
+        if it['rc'] != 0 or it['status'] != 0:
+            imgs.append(None)
+            continue
+        o, sz = it['rgb_off'], it['H'] * it['W'] * 3
+        imgs.append(buf[o:o + sz].reshape(it['H'], it['W'], 3))
+    if not with_info:
+        return imgs
+    ok = [it for it in info if it['rc'] == 0]
+    return imgs, {'items': info, 'rounds': int(rounds.value),
+                  'rgb_bytes': sum(-(-it['H'] * it['W'] * 3 // 256) * 256 for it in ok),
+                  'coef_entries': sum(it['coeffs_needed'] for it in ok)}
+
+
+def host_jpeg_batch(files, subseq_bits: int = 1024):
+    """Test aid (jds_selftest_jpeg_batch): the batch's layout, the host decode model per file and
+    the host model of the batch inverse.  -> (rgb buffer, coefficient buffer, per-file dicts).  No GPU."""
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    items = (_abi.JpegBatchItem * max(n, 1))()
+    rb, ce = C.c_int64(0), C.c_int64(0)
+    check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
+    rgb = np.full(max(int(rb.value), 1), 0xA5, np.uint8)
+    cf = np.zeros(max(int(ce.value), 1), np.int16)
+    check(lib().jds_selftest_jpeg_batch(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
+                                        cf.ctypes.data, items))
+    return rgb[:int(rb.value)], cf[:int(ce.value)], [_batch_item_dict(items[i]) for i in range(n)]
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

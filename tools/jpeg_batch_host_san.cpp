@@ -1,0 +1,132 @@
+// jpeg_batch_host_san.cpp — stand-alone host program over the batch form of the
+// fused inverse for foreign JPEGs (csrc/jds_jpeg_inv.hpp "batches"), for
+// sanitizer runs:
+//
+//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -ffp-contract=off -Iinclude -Ijpeg-dsp-studio_amd/csrc tools/jpeg_batch_host_san.cpp -o jpeg_batch_host_san
+//   ./jpeg_batch_host_san [batches [seed]]
+//
+// Builds batches of random geometry -- 1 to 12 images, every mode, sizes up to
+// 40 x 40 and around one to three tiles -- lays them out with the library's
+// placement step (jinv_batch_place) and tile maps (jinv_batch_maps), and runs
+// the host model of the batch launches (jpeg_inv_batch_host: the kernels' map
+// search, records and tile step) from exactly-sized heap arrays: the
+// concatenated coefficients hold the images' T.81 grids and nothing more, the
+// output rgb_bytes bytes, so a read or write outside either is a sanitizer
+// report.  Checked besides: every pixel of every image is written, no gap byte
+// (an image's end up to the next multiple of 256) is, every image equals
+// jinv_host_image alone, and an image whose status word is set is all zero.
+// No HIP, no GPU.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
+
+#include "jds_jpeg_inv.hpp"
+
+static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
+static uint32_t rnd() {
+  g_rng ^= g_rng << 13;
+  g_rng ^= g_rng >> 7;
+  g_rng ^= g_rng << 17;
+  return (uint32_t)(g_rng >> 16);
+}
+
+static bool fits(const jds::JInvArgs& a) {
+  return a.ss == JDS_SS_420   ? jds::jinv_windows_fit<JDS_SS_420>(a)
+         : a.ss == JDS_SS_422 ? jds::jinv_windows_fit<JDS_SS_422>(a)
+                              : jds::jinv_windows_fit<JDS_SS_444>(a);
+}
+
+static void single(const jds::JInvArgs& a, const int16_t* cf, uint8_t* o) {
+  if (a.ss == JDS_SS_420)
+    jds::jinv_host_image<JDS_SS_420>(a, cf, o);
+  else if (a.ss == JDS_SS_422)
+    jds::jinv_host_image<JDS_SS_422>(a, cf, o);
+  else
+    jds::jinv_host_image<JDS_SS_444>(a, cf, o);
+}
+
+static int dim(bool wide) {
+  if (rnd() % 3) return 1 + (int)(rnd() % 40);
+  const int t = 1 + (int)(rnd() % 3), d = (int)(rnd() % 5) - 2;
+  return t * (wide ? jds::JI_TW : jds::JI_TH) + d;
+}
+
+static int run_batch() {
+  const int n = 1 + (int)(rnd() % 12);
+  std::vector<jds::JInvRec> recs((size_t)n);
+  std::vector<long long> need((size_t)n);
+  long long rgb_bytes = 0, coef_entries = 0;
+  for (int k = 0; k < n; ++k) {
+    jds_jpeg_info info;
+    memset(&info, 0, sizeof info);
+    const int H = dim(false), W = dim(true), ss = (int)(rnd() % 3);
+    info.H = H;
+    info.W = W;
+    info.subsampling = ss;
+    const int vmax = ss == JDS_SS_420 ? 2 : 1, hmax = ss == JDS_SS_444 ? 1 : 2;
+    for (int c = 0; c < 3; ++c) {
+      const int h = c ? (H + vmax - 1) / vmax : H, w = c ? (W + hmax - 1) / hmax : W;
+      info.grid_rows[c] = (h + 7) / 8;
+      info.grid_cols[c] = (w + 7) / 8;
+      info.coeffs_needed += 64 * info.grid_rows[c] * info.grid_cols[c];
+      for (int i = 0; i < 64; ++i) info.qtable[c][i] = 1 + rnd() % 255;
+    }
+    memset(&recs[(size_t)k], 0, sizeof(jds::JInvRec));
+    if (jds::jinv_args(&info, &recs[(size_t)k].a) != 0 || !fits(recs[(size_t)k].a)) {
+      fprintf(stderr, "%dx%d mode %d: arguments rejected\n", H, W, ss);
+      return 1;
+    }
+    need[(size_t)k] = info.coeffs_needed;
+    jds::jinv_batch_place(recs[(size_t)k], k, info.coeffs_needed, &rgb_bytes, &coef_entries);
+  }
+  std::vector<jds::JInvMap> map[3];
+  if (!jds::jinv_batch_maps(recs.data(), n, map)) return 1;
+  int16_t* cf = (int16_t*)malloc(sizeof(int16_t) * (size_t)coef_entries);
+  uint8_t* rgb = (uint8_t*)malloc((size_t)rgb_bytes);
+  uint8_t* again = (uint8_t*)malloc((size_t)rgb_bytes);
+  std::vector<uint32_t> st((size_t)n, 0u);
+  if (!cf || !rgb || !again) return 1;
+  for (long long i = 0; i < coef_entries; ++i)
+    cf[i] = (rnd() % 10 < 7 || i % 64 == 0) ? (int16_t)((int)(rnd() % 2047) - 1023) : (int16_t)0;
+  if (n > 2 && rnd() % 4 == 0) st[(size_t)(rnd() % (uint32_t)n)] = 2u;  // a defective image: zeros
+  // two runs over differently pre-filled outputs: they agree where a byte is written, differ where not
+  memset(rgb, 0x00, (size_t)rgb_bytes);
+  memset(again, 0xFF, (size_t)rgb_bytes);
+  const jds::JInvMap* maps[3] = {map[0].data(), map[1].data(), map[2].data()};
+  const int nmap[3] = {(int)map[0].size() - 1, (int)map[1].size() - 1, (int)map[2].size() - 1};
+  for (uint8_t* o : {rgb, again}) jds::jpeg_inv_batch_host(recs.data(), maps, nmap, st.data(), cf, o);
+  int bad = 0;
+  for (int k = 0; k < n && !bad; ++k) {
+    const jds::JInvRec& r = recs[(size_t)k];
+    const size_t nimg = (size_t)r.a.H * r.a.W * 3;
+    const size_t end = (size_t)r.rgb_off + nimg, next = k + 1 < n ? (size_t)recs[(size_t)k + 1].rgb_off : (size_t)rgb_bytes;
+    if (r.rgb_off % jds::JI_RGB_ALIGN || next < end || next - end >= (size_t)jds::JI_RGB_ALIGN) bad = 1;
+    if (memcmp(rgb + r.rgb_off, again + r.rgb_off, nimg) != 0) bad = 2;  // a pixel was not written
+    for (size_t i = end; i < next; ++i)
+      if (rgb[i] != 0x00 || again[i] != 0xFF) bad = 3;  // a gap byte was
+    uint8_t* alone = (uint8_t*)malloc(nimg);
+    if (!alone) return 1;
+    if (st[(size_t)k])
+      memset(alone, 0, nimg);
+    else
+      single(r.a, cf + r.coef_off, alone);
+    if (memcmp(alone, rgb + r.rgb_off, nimg) != 0) bad = 4;
+    free(alone);
+    if (bad) fprintf(stderr, "batch of %d, image %d (%dx%d mode %d): check %d failed\n", n, k, r.a.H, r.a.W, r.a.ss, bad);
+  }
+  free(cf);
+  free(rgb);
+  free(again);
+  return bad != 0;
+}
+
+int main(int argc, char** argv) {
+  const int batches = argc > 1 ? atoi(argv[1]) : 300;
+  if (argc > 2) g_rng ^= (uint64_t)atoll(argv[2]) * 0x2545f4914f6cdd1dull;
+  long failed = 0;
+  for (int b = 0; b < batches; ++b) failed += run_batch();
+  printf("%d batches through the host model of the batch inverse, %ld failed\n", batches, failed);
+  return failed ? 1 : 0;
+}

@@ -12,7 +12,13 @@ rocprofv3 --kernel-trace --stats, which gives the per-kernel split).
 --rgb adds, per Pillow input, the way to pixels: jpeg_to_rgb to host memory and
 to a device tensor, decompress_jpeg(staged=True) (at most 5 calls: it is slow),
 k_jpeg_inv alone by events, and one more line: the plan's exact inverse k_inv2
-on a frame of the same geometry by the plan's launch marks (the yardstick)."""
+on a frame of the same geometry by the plan's launch marks (the yardstick).
+--batch N (default 64) instead: N 1080p Pillow Q50 4:2:0 files of different seeded noise images
+through jpeg_batch_to_rgb(out='device') against N sequential jpeg_to_rgb(out=tensor) calls in
+the same process (median of 10 after 2 warm-ups each), the rounds of the batch and the
+per-kernel times from the context's launch marks; then a mixed leg: the same N split over Q50 /
+Q95 / optimize=True / restart_marker_rows=1 and the three subsampling modes, at two sizes.
+Writes profiles/jpeg_batch_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -119,7 +125,89 @@ def inv2_yardstick(H, W, reps):
             'span_us_per_frame': span * 1e3 / reps, 'equals_host_model': True}
 
 
+def timed(fn, reps=10, warm=2):
+    for _ in range(warm):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    t.sort()
+    return {'median_ms': t[len(t) // 2], 'min_ms': t[0], 'max_ms': t[-1], 'reps': reps}
+
+
+def pillow_file(img, quality=50, subsampling=2, **kw):
+    buf = io.BytesIO()
+    Image.fromarray(img).save(buf, 'JPEG', quality=quality, subsampling=subsampling, **kw)
+    return buf.getvalue()
+
+
+def batch_leg(name, files, pixels):
+    """One batch against the sequence of single calls on the same files."""
+    import torch
+    from jds import _abi
+    n = len(files)
+    items, rgb_bytes, _ = codec.jpeg_batch_layout(files)
+    out = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    outs = [torch.empty((it['H'], it['W'], 3), dtype=torch.uint8, device='cuda') for it in items]
+    ctx = _abi.Context(0)
+    views, info = codec.jpeg_batch_to_rgb(files, out=out, with_info=True, ctx=ctx)
+    torch.cuda.synchronize()
+    for f, o in zip(files, outs):
+        codec.jpeg_to_rgb(f, out=o)
+    equal = all(bool(torch.equal(v, o)) for v, o in zip(views, outs))
+    tb = timed(lambda: codec.jpeg_batch_to_rgb(files, out=out, ctx=ctx))
+
+    def sequence():
+        for f, o in zip(files, outs):
+            codec.jpeg_to_rgb(f, out=o)
+    ts = timed(sequence)
+    ctx.profile(True)
+    reps = 5
+    for _ in range(reps):
+        codec.jpeg_batch_to_rgb(files, out=out, ctx=ctx)
+    kern, span = ctx.profile_read()
+    ctx.profile(False)
+    ctx.close()
+    inv_us = sum(v[0] for k, v in kern.items() if k.startswith('k_jpeg_inv_batch')) * 1e3 / reps / n
+    return {'leg': name, 'n': n, 'file_bytes_total': int(sum(len(f) for f in files)), 'pixels_total': int(pixels),
+            'batch': tb, 'sequence': ts, 'batch_ms_per_image': tb['median_ms'] / n,
+            'sequence_ms_per_image': ts['median_ms'] / n, 'factor': ts['median_ms'] / tb['median_ms'],
+            'batch_images_per_s': 1e3 * n / tb['median_ms'], 'rounds': info['rounds'],
+            'batch_equals_sequence': equal,
+            'kernels_ms_per_batch': {k: v[0] / reps for k, v in kern.items()},
+            'kernel_launches_per_batch': {k: v[1] / reps for k, v in kern.items()},
+            'marks_span_ms_per_batch': span / reps, 'k_jpeg_inv_batch_us_per_image': inv_us}
+
+
+def batch_main():
+    i = sys.argv.index('--batch')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    plain = [pillow_file(np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8)) for k in range(n)]
+    rows = [batch_leg('pillow_q50_420_1080p', plain, n * H * W)]
+    print(json.dumps(rows[-1]), flush=True)
+    kinds = [{'quality': 50}, {'quality': 95}, {'quality': 50, 'optimize': True}, {'quality': 50, 'restart_marker_rows': 1}]
+    sizes = [(H, W), (2 * H // 3, 2 * W // 3)]
+    mixed, px = [], 0
+    for k in range(n):
+        h, w = sizes[(k // 12) % 2]
+        img = np.random.default_rng(500 + k).integers(0, 256, (h, w, 3), dtype=np.uint8)
+        mixed.append(pillow_file(img, subsampling=(2, 0, 1)[k % 3], **kinds[(k // 3) % 4]))
+        px += h * w
+    rows.append(batch_leg('pillow_mixed', mixed, px))
+    print(json.dumps(rows[-1]), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'jpeg_batch_probe.json')
+    with open(out, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r['batch_equals_sequence'] for r in rows) else 1
+
+
 def main():
+    if '--batch' in sys.argv:
+        return batch_main()
     H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
     reps = 1 if '--once' in sys.argv else int(os.environ.get('REPS', '30'))
     want_rgb = '--rgb' in sys.argv
