@@ -280,6 +280,14 @@ def test_parser_and_core_clean_under_host_sanitizers(tmp_path):
              codec_file(1, 9, '4:4:4', 50)[0], codec_file(64, 96, '4:2:2', 50)[0], synthetic_file('extreme')[0]]
     for i, d in enumerate(valid):
         (corpus / f'valid_{i}.jpg').write_bytes(d)
+    # hostile tables and 0xFF-dense scans (tests/huff_hostile.py), one of them a three-scan file of this profile
+    import huff_hostile as hh
+    hostile = [hh.case('ladder8', 'ff_dense', 17, 23, '4:2:0')[0], hh.case('ladder8', 'ff_mixed', 33, 35, '4:2:2', ri=4)[0],
+               hh.case('mixed', 'sparse_random', 20, 28, '4:4:4', crossed=True)[0],
+               hh.case('gap', 'long_codes', 40, 56, '4:2:0', ri=5, interleaved=False, one_qt=True)[0]]
+    hostile += list(hh.defective_files().values())
+    for i, d in enumerate(hostile):
+        (corpus / f'hostile_{i}.jpg').write_bytes(d)
     small = valid[2]
     for n in range(len(small)):
         (corpus / f'trunc_{n}.jpg').write_bytes(small[:n])
@@ -294,4 +302,6 @@ def test_parser_and_core_clean_under_host_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-4000:]
     assert r.stderr == '', r.stderr[-4000:]
     files, parsed = int(r.stdout.split()[0]), int(r.stdout.split()[2])
-    assert files == len(os.listdir(corpus)) and parsed >= len(valid)
+    assert files == len(os.listdir(corpus)) and parsed >= len(valid) + 1
+    jpeg = r.stdout.splitlines()[1].split()       # 'jpeg parser: N parsed, N decodes clean, N defective'
+    assert int(jpeg[2]) >= len(valid) + len(hostile) and int(jpeg[4]) >= 6 * (len(valid) + len(hostile) - 2)
