@@ -408,6 +408,47 @@ int jds_encode_jfif_rst(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W,
 int jds_plan_entropy_decode_rst(jds_plan* plan, int32_t interval, const uint8_t* files, int64_t stride,
                                 const uint64_t* lengths, int16_t* coeffs, uint32_t* status, void* stream);
 
+/* Optimised Huffman tables (DESIGN.md "Optimised tables"): each frame is coded
+ * with its own four tables, built from the frame's symbol counts (libjpeg
+ * -optimize, Pillow optimize=True).  Byte-for-byte definition:
+ * tests/huffopt_ref.py over oracle/jpeg_entropy.py.  The file holds SOI, APP0,
+ * DQT, SOF0 as the standard route writes them, four DHT segments (0x00, 0x10,
+ * 0x01, 0x11) that list only the symbols the frame uses, DRI for a restart
+ * file, and the three scans.  Luma tables count the Y scan, chroma tables the
+ * Cb and Cr scans together; with a restart interval the DC differences restart
+ * at every interval, so the two file forms have different tables.  The tables
+ * are T.81 K.2 with libjpeg's tie rules and K.3; a class whose codes would
+ * exceed 32 bits before K.3 (about 15 million symbols) keeps its Annex K table.
+ *   interval: 0, or the writer's (jds_entropy_restart_info); anything else is
+ *     JDS_ENOTSUP.
+ *   jds_plan_entropy_capacity_opt: the route's own worst case.  Any symbol may
+ *     get a 16-bit code, so a block is bounded by 1665 bits instead of 1660 and
+ *     the bound is larger than jds_plan_entropy_capacity[_rst]'s.
+ *   jds_plan_entropy_opt: as jds_plan_entropy[_rst]; ASYNCHRONOUS -- counts,
+ *     tables, headers and files are made on the device, nothing is read back.
+ *     lengths[i] == 0 keeps its meaning (a frame baseline JPEG cannot code).
+ *   jds_encode_jfif_opt: as jds_encode_jfif[_rst].
+ * Reading: jds_decode_jfif, jds_decompress_jfif, jds_decode_jpeg and
+ * jds_jpeg_batch_to_rgb take the files (they read each file's DHT).
+ * jds_plan_entropy_decode[_rst] compare headers with the plan's own and mark
+ * optimised files JDS_DEC_HEADER. */
+int jds_plan_entropy_capacity_opt(const jds_plan* plan, int32_t interval, int64_t* bytes_per_frame);
+int jds_plan_entropy_opt(jds_plan* plan, int32_t interval, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
+                         uint64_t* lengths, uint64_t* scan_bits, void* stream);
+int jds_encode_jfif_opt(jds_ctx* ctx, const jds_params* p, int64_t H, int64_t W, int32_t interval,
+                        const int16_t* coeffs, uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits);
+/* Test-only.  jds_selftest_huffopt (host, no GPU): the table of freq[0..255] by
+ * the core the kernel shares (csrc/jds_huffopt.hpp): BITS[1..16], HUFFVAL (256
+ * bytes, n_vals used), fell_back = 1 when a code would exceed 32 bits, in which
+ * case the Annex K AC luma table is returned.  jds_selftest_huffopt_dev: the
+ * same fields from k_ent_opt_tables for n histograms (freqs: n x 256 counts,
+ * bits_out n x 16, vals_out n x 256, n_vals and fell_back n each; host
+ * pointers). */
+int jds_selftest_huffopt(const uint32_t* freq, uint8_t* bits_out, uint8_t* vals_out, int32_t* n_vals,
+                         int32_t* fell_back);
+int jds_selftest_huffopt_dev(jds_ctx* ctx, const uint32_t* freqs, int32_t n, uint8_t* bits_out, uint8_t* vals_out,
+                             int32_t* n_vals, int32_t* fell_back);
+
 /* Baseline JPEGs from elsewhere (DESIGN.md "Interleaved scans").  The calls
  * above read the profile this library writes; libjpeg, Pillow, cameras and
  * browsers write another: ONE interleaved scan (Ns = 3, MCUs of Y.. Cb Cr

@@ -20,6 +20,7 @@
 #include "jds_dct16.hpp"
 #include "jds_dct8.hpp"
 #include "jds_huffdec.hpp"
+#include "jds_huffopt.hpp"
 #include "jds_internal.hpp"
 #include "jds_jpeg_inv.hpp"
 
@@ -95,6 +96,18 @@ long long ent_capacity_rst(const Geo& g);
 hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
                               const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                               unsigned long long* scan_bits, hipStream_t s);
+// the optimised-table route (jds_entropy.hip, jds_huffopt.hip)
+long long ent_capacity_opt(const Geo& g, bool rst);
+hipError_t launch_entropy_opt(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
+                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
+                              unsigned long long* scan_bits, hipStream_t s);
+hipError_t launch_entropy_rst_opt(const Geo& g, int n, const int16_t* coeffs, void* const* buf,
+                                  const uint8_t* hdr_dev, const void* tab_dev, uint8_t* out, long long stride,
+                                  unsigned long long* lengths, unsigned long long* scan_bits, hipStream_t s);
+int ent_std_table(int idx, const uint8_t** bits, const uint8_t** vals);
+void opt_table_host(const uint32_t* freq, HoTable* t);
+hipError_t launch_opt_tables_selftest(int n, const uint32_t* freq, uint8_t* bits, uint8_t* vals, int32_t* nv,
+                                      int32_t* fell, hipStream_t s);
 void rst_constants(int* lane_max);
 int rst_group_lanes();
 size_t rst_work_bytes(int n, const RstGeo& rg);
@@ -1563,10 +1576,10 @@ static int check_writer_interval(int32_t interval) {
 }
 
 static int plan_entropy(jds_plan* p, bool rst, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
-                        uint64_t* lengths, uint64_t* scan_bits, void* stream) {
+                        uint64_t* lengths, uint64_t* scan_bits, void* stream, bool opt = false) {
   if (!p || !coeffs || !out || !lengths) return fail(JDS_EINVAL, "null argument");
   if (p->g.bs != 8) return fail(JDS_ENOTSUP, "JPEG entropy coding needs 8x8 blocks (block_size %d)", p->g.bs);
-  const long long cap = rst ? ent_capacity_rst(p->g) : ent_capacity(p->g);
+  const long long cap = opt ? ent_capacity_opt(p->g, rst) : (rst ? ent_capacity_rst(p->g) : ent_capacity(p->g));
   if (out_stride < cap)
     return fail(JDS_EINVAL, "out_stride %lld < worst-case file size %lld", (long long)out_stride, cap);
   HIP_TRY(hipSetDevice(p->ctx->device));
@@ -1578,9 +1591,10 @@ static int plan_entropy(jds_plan* p, bool rst, const int16_t* coeffs, uint8_t* o
   void* bufs[8];
   for (int i = 0; i < 8; ++i) bufs[i] = p->ent[i].p;
   const MarkScope marks_(p, s);
-  HIP_TRY((rst ? launch_entropy_rst : launch_entropy)(p->g, p->n, coeffs, bufs, (const uint8_t*)p->ent_hdr.p,
-                                                      p->ent_tab.p, out, out_stride, (unsigned long long*)lengths,
-                                                      (unsigned long long*)scan_bits, s));
+  auto* launch = opt ? (rst ? launch_entropy_rst_opt : launch_entropy_opt)
+                     : (rst ? launch_entropy_rst : launch_entropy);
+  HIP_TRY(launch(p->g, p->n, coeffs, bufs, (const uint8_t*)p->ent_hdr.p, p->ent_tab.p, out, out_stride,
+                 (unsigned long long*)lengths, (unsigned long long*)scan_bits, s));
   return JDS_OK;
 }
 
@@ -1615,7 +1629,7 @@ int jds_plan_entropy_rst(jds_plan* p, int32_t interval, const int16_t* coeffs, u
 }
 
 static int encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, bool rst, const int16_t* coeffs,
-                       uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
+                       uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits, bool opt = false) {
   if (!c || !prm || !coeffs || !out || !out_len) return fail(JDS_EINVAL, "null argument");
   Geo g;
   int mode;
@@ -1624,7 +1638,7 @@ static int encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, 
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   if ((rc = ent_prepare(g, mode, 1, prm->qtable, c->ent, c->ent_hdr, c->ent_tab, s))) return rc;
-  const long long cap = rst ? ent_capacity_rst(g) : ent_capacity(g);
+  const long long cap = opt ? ent_capacity_opt(g, rst) : (rst ? ent_capacity_rst(g) : ent_capacity(g));
   HIP_TRY(c->ent_cf.ensure((size_t)g.cpf * sizeof(int16_t)));
   HIP_TRY(c->ent_out.ensure((size_t)cap));
   HIP_TRY(c->ent_meta.ensure(4 * sizeof(unsigned long long)));
@@ -1632,9 +1646,10 @@ static int encode_jfif(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, 
   void* bufs[8];
   for (int i = 0; i < 8; ++i) bufs[i] = c->ent[i].p;
   unsigned long long* meta = (unsigned long long*)c->ent_meta.p;
-  HIP_TRY((rst ? launch_entropy_rst : launch_entropy)(g, 1, (const int16_t*)c->ent_cf.p, bufs,
-                                                      (const uint8_t*)c->ent_hdr.p, c->ent_tab.p,
-                                                      (uint8_t*)c->ent_out.p, cap, meta, meta + 1, s));
+  auto* launch = opt ? (rst ? launch_entropy_rst_opt : launch_entropy_opt)
+                     : (rst ? launch_entropy_rst : launch_entropy);
+  HIP_TRY(launch(g, 1, (const int16_t*)c->ent_cf.p, bufs, (const uint8_t*)c->ent_hdr.p, c->ent_tab.p,
+                 (uint8_t*)c->ent_out.p, cap, meta, meta + 1, s));
   unsigned long long m[4];
   HIP_TRY(hipMemcpyAsync(m, meta, sizeof m, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1659,6 +1674,85 @@ int jds_encode_jfif_rst(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W,
   const int rc = check_writer_interval(interval);
   if (rc) return rc;
   return encode_jfif(c, prm, H, W, true, coeffs, out, out_cap, out_len, scan_bits);
+}
+
+// Optimised tables (DESIGN.md "Optimised tables"): interval 0 or the writer's.
+static int check_opt_interval(int32_t interval) { return interval ? check_writer_interval(interval) : JDS_OK; }
+
+int jds_plan_entropy_capacity_opt(const jds_plan* p, int32_t interval, int64_t* bytes_per_frame) {
+  if (!p || !bytes_per_frame) return fail(JDS_EINVAL, "null argument");
+  if (p->g.bs != 8) return fail(JDS_ENOTSUP, "JPEG entropy coding needs 8x8 blocks (block_size %d)", p->g.bs);
+  const int rc = check_opt_interval(interval);
+  if (rc) return rc;
+  *bytes_per_frame = ent_capacity_opt(p->g, interval != 0);
+  return JDS_OK;
+}
+
+int jds_plan_entropy_opt(jds_plan* p, int32_t interval, const int16_t* coeffs, uint8_t* out, int64_t out_stride,
+                         uint64_t* lengths, uint64_t* scan_bits, void* stream) {
+  const int rc = check_opt_interval(interval);
+  if (rc) return rc;
+  return plan_entropy(p, interval != 0, coeffs, out, out_stride, lengths, scan_bits, stream, true);
+}
+
+int jds_encode_jfif_opt(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, int32_t interval,
+                        const int16_t* coeffs, uint8_t* out, int64_t out_cap, int64_t* out_len, uint64_t* scan_bits) {
+  const int rc = check_opt_interval(interval);
+  if (rc) return rc;
+  return encode_jfif(c, prm, H, W, interval != 0, coeffs, out, out_cap, out_len, scan_bits, true);
+}
+
+// The fields jds_selftest_huffopt[_dev] return for a table that fell back: the Annex K AC luma table.
+static void huffopt_fallback(uint8_t* bits_out, uint8_t* vals_out, int32_t* n_vals) {
+  const uint8_t *b, *v;
+  const int n = ent_std_table(1, &b, &v);
+  memcpy(bits_out, b, 16);
+  memset(vals_out, 0, 256);
+  memcpy(vals_out, v, (size_t)n);
+  *n_vals = n;
+}
+
+int jds_selftest_huffopt(const uint32_t* freq, uint8_t* bits_out, uint8_t* vals_out, int32_t* n_vals,
+                         int32_t* fell_back) {
+  if (!freq || !bits_out || !vals_out || !n_vals || !fell_back) return fail(JDS_EINVAL, "null argument");
+  HoTable t;
+  opt_table_host(freq, &t);
+  *fell_back = t.fell_back;
+  if (t.fell_back) {
+    huffopt_fallback(bits_out, vals_out, n_vals);
+    return JDS_OK;
+  }
+  memcpy(bits_out, t.bits, 16);
+  memcpy(vals_out, t.vals, 256);
+  *n_vals = t.n_vals;
+  return JDS_OK;
+}
+
+int jds_selftest_huffopt_dev(jds_ctx* c, const uint32_t* freqs, int32_t n, uint8_t* bits_out, uint8_t* vals_out,
+                             int32_t* n_vals, int32_t* fell_back) {
+  if (!c || !freqs || !bits_out || !vals_out || !n_vals || !fell_back) return fail(JDS_EINVAL, "null argument");
+  if (n < 1 || n > 65536) return fail(JDS_EINVAL, "n = %d histograms (1..65536)", n);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  DevBuf d;
+  const size_t o_bits = 1024 * (size_t)n, o_vals = o_bits + 16 * (size_t)n, o_nv = o_vals + 256 * (size_t)n,
+               o_fell = o_nv + 4 * (size_t)n, total = o_fell + 4 * (size_t)n;
+  HIP_TRY(d.ensure(total));
+  char* base = (char*)d.p;
+  hipError_t e = hipMemcpyAsync(base, freqs, o_bits, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess)
+    e = launch_opt_tables_selftest(n, (const uint32_t*)base, (uint8_t*)base + o_bits, (uint8_t*)base + o_vals,
+                                   (int32_t*)(base + o_nv), (int32_t*)(base + o_fell), s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bits_out, base + o_bits, 16 * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vals_out, base + o_vals, 256 * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(n_vals, base + o_nv, 4 * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(fell_back, base + o_fell, 4 * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  d.release();
+  HIP_TRY(e);
+  for (int i = 0; i < n; ++i)
+    if (fell_back[i]) huffopt_fallback(bits_out + 16 * (size_t)i, vals_out + 256 * (size_t)i, n_vals + i);
+  return JDS_OK;
 }
 
 // ------------------------------------------------------ entropy decoding --

@@ -26,6 +26,9 @@
 //   k_ent_emit3  stuffed copy to the file (0x00 after every 0xFF).
 // With restart interval 64 a segment is a restart interval and one wave codes
 // it from start to end: k_rst_code, k_rst_fscan, k_rst_emit (further down).
+// The optimised route (jds_encode_jfif_opt, jds_plan_entropy_opt) runs the
+// same kernels as OPT = true instantiations behind jds_huffopt.hip's histogram
+// and table builder: per-frame tables, headers and header lengths (OptFrame).
 // (The rounds 1-3 multi-pass coder -- a counting walk, a block scan, a packing
 // walk with LDS atomics, per-chunk stuffing -- measured 0.54 ms per 64 x 1080p
 // against this one's 0.30, and a one-launch form with a decoupled look-back
@@ -36,6 +39,7 @@
 
 #include <initializer_list>
 
+#include "jds_entropy_common.hpp"
 #include "jds_internal.hpp"
 
 namespace jds {
@@ -81,22 +85,7 @@ struct EntTab {
   uint8_t zz[64];
 };
 
-// left-aligned symbols: code << (32 - len) | len (len <= 16 sits below the code)
-// AC table row stride: (run, size) at run * 11 + size spreads a wave's lookups
-// over the LDS banks (32: 0.271 vs 11: 0.258 ms per 64 x 1080p; a stride of 32
-// put every even run on the same 11 banks)
-constexpr int ES_RS = 11;
-static_assert(ES_RS >= 11, "sizes 0..10");
-struct EsTab {
-  uint32_t ac[2][16 * ES_RS];  // (run & 15, size) -> AC symbol, size clamped to 10 (code_ac's clamp); 0 for size 0
-  uint32_t dc[2][16];
-  uint32_t zrl[2], eob[2];
-};
-
-__host__ __device__ __forceinline__ uint32_t es_left(uint32_t e) {  // (len << 16 | code) -> left-aligned | len
-  const uint32_t len = e >> 16;
-  return len ? (((e & 0xFFFFu) << (32u - len)) | len) : 0u;
-}
+// (the left-aligned symbols of the single-pass coder, EsTab: jds_entropy_common.hpp)
 
 // T.81 Annex C: code lengths and codes in order of increasing length
 static void huff_codes(const uint8_t* bits, const uint8_t* vals, uint32_t* out, int nsym) {
@@ -133,9 +122,6 @@ size_t ent_tab_size() { return sizeof(EntTab) + sizeof(EsTab); }
 
 // JFIF header template (oracle/jpeg_entropy.py::jfif_headers): returns its length
 // (ENT_HDR bytes) or -1 if the table is not baseline (integers in [1, 255]).
-constexpr int ENT_HDR = 2 + 18 + 69 + 19 + 2 * (4 + 1 + 16 + 12) + 2 * (4 + 1 + 16 + 162);
-constexpr int ENT_SOS = 10;
-
 int ent_header(const double* q, int mode, int H, int W, uint8_t* o) {
   int p = 0;
   auto put = [&](std::initializer_list<int> b) {
@@ -164,100 +150,7 @@ int ent_header(const double* q, int mode, int H, int W, uint8_t* o) {
 }
 
 // ------------------------------------------------------------ kernels --
-
-struct EntGeo {
-  int nb;          // blocks per frame (Y + Cb + Cr)
-  int first[4];    // first block of each scan within the frame, first[3] = nb
-  int sfirst[4];   // single-pass coder: first 64-block segment of each scan within the frame, sfirst[3] = per frame
-  int cap_w[3];    // packed-scan capacity in 32-bit words (worst case 1660 bits per block)
-  long long raw_w; // packed words per frame
-  long long hdr;   // header template bytes per frame
-};
-
-__device__ __forceinline__ long long raw_base(const EntGeo& e, int frame, int s) {
-  return (long long)frame * e.raw_w + (s == 0 ? 0 : (s == 1 ? e.cap_w[0] : e.cap_w[0] + e.cap_w[1]));
-}
-
-// Inclusive prefix sum over the wave (every lane active): row_shr 1, 2, 4, 8
-// within the 16-lane rows, then row_bcast 15 / 31 across them -- six DPP adds
-// (the log-step shuffle form, six ds_bpermute round trips, measured slower).
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane) {
-  (void)lane;
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-
-__device__ __forceinline__ int wave_excl_sum(int x, int lane) {
-  return (int)(wave_incl_sum((uint32_t)x, lane) - (uint32_t)x);
-}
-
-__device__ __forceinline__ uint32_t lane63(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-
-// lane l <- lane l + 1 across the whole wave (DPP wave_shl:1; lane 63 <- 0)
-__device__ __forceinline__ uint32_t wave_shl1(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true);
-}
-// lane l <- lane l - 1 (DPP wave_shr:1; lane 0 <- 0)
-__device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, true); }
-
-// wave-wide totals (every lane active), read from lane 63 of the DPP scan
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return lane63(wave_incl_sum(v, (int)__lane_id())); }
-
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  return lane63(v);
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
-  return lane63(v);
-}
-
-// One LANE per block: its 64 coefficients sit in 32 VGPRs (packed int16
-// pairs) and the zigzag walk is unrolled at compile time, so every register
-// index is a constant; the per-coefficient work is a handful of integer ops
-// under the lane's own "nonzero" mask.  (A wave per block, one lane per
-// coefficient, spent ~400 wave instructions per block on ballots, shuffles
-// and divergent branches.)
-struct BlockRegs {
-  uint32_t w[32];
-};
-
-__device__ __forceinline__ BlockRegs load_block(const int16_t* __restrict__ p) {
-  BlockRegs r;
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint4 x = q[i];
-    r.w[4 * i] = x.x; r.w[4 * i + 1] = x.y; r.w[4 * i + 2] = x.z; r.w[4 * i + 3] = x.w;
-  }
-  return r;
-}
-
-template <int IDX>
-__device__ __forceinline__ int coef_at(const BlockRegs& r) {
-  return (int)(int16_t)((IDX & 1) ? (r.w[IDX >> 1] >> 16) : (r.w[IDX >> 1] & 0xFFFFu));
-}
-
-constexpr uint8_t ZZC[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                             12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                             58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// (segment geometry, block registers, wave primitives: jds_entropy_common.hpp)
 
 // ------------------------------------------------ one pass (round 4) --
 //
@@ -279,7 +172,17 @@ constexpr uint8_t ZZC[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18,
 //    and each scan's last byte is padded with 1-bits (T.81 F.1.2.3), so the
 //    stuffing pass reads final words.
 // A segment that is not the last of its scan holds >= 256 bits (every block
-// costs >= 4), so only consecutive segments share a word.
+// costs >= 4), so only consecutive segments share a word.  (Optimised tables,
+// DESIGN.md "Optimised tables": a block costs >= 2 bits -- a one-symbol DC
+// table and a one-symbol AC table have 1-bit codes -- so >= 128 bits per such
+// segment, and the same holds.)
+//
+// OPT (template parameter of the coding kernels): the optimised route.  Its
+// code tables, header and header length are per frame (OptFrame, built on the
+// device by jds_huffopt.hip); a workgroup's waves can sit in different frames,
+// so each wave stages its own frame's table.  The standard route's
+// instantiations (OPT = false) carry none of that: one shared table per
+// workgroup, the header template's fixed length.
 constexpr int ES_WPE = 4;     // waves per SIMD the walk's registers are held to (3..6: no difference)
 constexpr int ES_DENSE = 32;  // zigzag positions coded by the unrolled walk; the rest by the nonzero loop
 // LDS staging words per lane (more go to global): 16: 0.303, 0: 0.295, 8: 0.292
@@ -287,7 +190,15 @@ constexpr int ES_DENSE = 32;  // zigzag positions coded by the unrolled walk; th
 constexpr int ES_SW = 8;
 constexpr int ES_HI = 64 - ES_DENSE;     // positions of the nonzero loop
 static_assert(ES_HI <= 32, "es_hi_stash's nonzero mask is one 32-bit word (ES_DENSE = 24 dropped positions 56-63)");
-constexpr int ES_MAXW = 53;              // words per block at most (1660 bits + the partial word): the spill area
+// words per block at most: the spill area.  1660 bits (Annex K tables) and 1665
+// (optimised tables, ENT_BLOCK_BITS_OPT) both end in word 53 (52 * 32 = 1664)
+constexpr int ES_MAXW = 53;
+static_assert(32 * ES_MAXW >= ENT_BLOCK_BITS_OPT && ENT_BLOCK_BITS_OPT >= ENT_BLOCK_BITS, "a block's staged words");
+// lanes one 32-bit word can hold whole, + 1: the reach of es_place's segmented
+// OR.  Every block costs >= 4 bits with the Annex K tables (7 whole blocks
+// between a tail bit and a head bit), >= 2 with optimised ones (15).
+template <bool OPT>
+constexpr int es_span() { return OPT ? 15 : 7; }
 #ifndef JDS_ES_WAVES  // tools: A/B builds of the walk's waves per workgroup
 #define JDS_ES_WAVES 4
 #endif
@@ -323,12 +234,6 @@ struct EsStage {
     if (k < ES_SW) st[k * 64] = w; else ov[k * 64] = w;
   }
 };
-
-// size category of |v| (clamped to 10, code_ac's clamp)
-__device__ __forceinline__ int es_size(int a) {
-  const int sz = a ? 32 - __clz(a) : 0;
-  return sz > 10 ? 10 : sz;
-}
 
 // The AC walk, software-pipelined: e is position K's table entry, loaded
 // while position K - 1 was appended; position K + 1's lookup (its run needs
@@ -430,20 +335,6 @@ __device__ __forceinline__ uint32_t es_block(const BlockRegs& r, int diff, const
   return nb;
 }
 
-struct EsSeg {
-  int f, s, seg, nseg_s, nbs;
-};
-__device__ __forceinline__ EsSeg es_seg(const EntGeo& e, int g) {
-  EsSeg q;
-  q.f = g / e.sfirst[3];
-  const int r = g - q.f * e.sfirst[3];
-  q.s = r < e.sfirst[1] ? 0 : (r < e.sfirst[2] ? 1 : 2);
-  q.seg = r - e.sfirst[q.s];
-  q.nseg_s = e.sfirst[q.s + 1] - e.sfirst[q.s];
-  q.nbs = e.first[q.s + 1] - e.first[q.s];
-  return q;
-}
-
 // the scan's final word: 1-bits from the scan's end to its byte boundary;
 // returns the number of the word's bytes that belong to the scan
 __device__ __forceinline__ int es_pad(uint32_t& v, unsigned long long W1, unsigned long long widx) {
@@ -472,7 +363,9 @@ __device__ __forceinline__ int es_ff(uint32_t v, int nbytes) {  // 0xFF bytes am
 // share this segment's final word, so that word is written whole here; Wn: the
 // scan's end bit when the next segment ends in that word.  rs: the packed words
 // the offsets count from (the scan's; a restart interval's own slot); report:
-// the scan's last segment stores the scan's length (info, scan_bits).
+// the scan's last segment stores the scan's length (info, scan_bits).  SPAN:
+// es_span().
+template <int SPAN>
 __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g, int lane, bool valid, int nvalid,
                                          bool last_seg, uint32_t nb, uint32_t excl, unsigned long long pre,
                                          unsigned long long A, const uint32_t* st, const uint32_t* ov, int k,
@@ -500,13 +393,13 @@ __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g,
   }
   // (every block costs >= 4 bits, so at most 7 lanes in a row lie inside one
   // word and share the next lane's word: spans of 8 lanes suffice; the host
-  // model fails with spans of 4)
+  // model fails with spans of 4.  Optimised tables: >= 2 bits, 15 lanes.)
   {  // X_l = own_l | (F_l ? X_{l+1} : 0), one lane further per DPP wave shift (lane 63 never chains)
     // (a mask, not a select: the shifts must run with every lane active, and
     // the compiler turns a select into a branch around them)
     const uint32_t own = X, fm = 0u - (uint32_t)F;
 #pragma unroll
-    for (int it = 0; it < 7; ++it) X = own | (wave_shl1(X) & fm);
+    for (int it = 0; it < SPAN; ++it) X = own | (wave_shl1(X) & fm);
   }
   const uint32_t X1 = wave_shl1(X);
   const uint32_t in_tail = c ? ((fuse && lane == 63) ? tailx : X1) : 0u;
@@ -560,22 +453,41 @@ __device__ __forceinline__ void es_place(const EntGeo& e, const EsSeg& q, int g,
 // k_ent_walk packs each segment's blocks and stores the staged words
 // (word-major per segment), the lanes' bit counts and the segment's total;
 // k_ent_place places the words at the segment's offset.
+//
+// The code table in LDS (es: [ES_WAVES] on the optimised route, [1] otherwise):
+// the standard route stages the one table gt for the workgroup; the optimised
+// route has every wave stage its own frame's (a workgroup's segments can span
+// frames: three segments per frame at 40 x 72 4:4:4).  Both end in the
+// workgroup's barrier, so every wave calls them before it can leave.
+__device__ __forceinline__ void es_stage_shared(EsTab* es, const EsTab* __restrict__ gt) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(gt);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(es);
+  for (int i = threadIdx.x; i < (int)(sizeof(EsTab) / 4); i += blockDim.x) dst[i] = src[i];
+  __syncthreads();
+}
+__device__ __forceinline__ void es_stage_frame(EsTab* es, const OptFrame* __restrict__ of, const EntGeo& e, int g,
+                                               int nseg, int lane) {
+  const int f = (g < nseg ? g : nseg - 1) / e.sfirst[3];
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&of[f].es);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(es);
+  for (int i = lane; i < (int)(sizeof(EsTab) / 4); i += 64) dst[i] = src[i];
+  __syncthreads();
+}
+
+template <bool OPT>
 __global__ void __launch_bounds__(64 * ES_WAVES) __attribute__((amdgpu_waves_per_eu(ES_WPE))) k_ent_walk(
     const EntGeo e, const int nseg, const int16_t* __restrict__ coeffs, const EsTab* __restrict__ gt,
     uint32_t* __restrict__ gst, uint32_t* __restrict__ nbits, unsigned long long* __restrict__ agg,
-    uint32_t* __restrict__ badseg, unsigned long long* __restrict__ ffs) {
-  __shared__ EsTab es;
+    uint32_t* __restrict__ badseg, unsigned long long* __restrict__ ffs, const OptFrame* __restrict__ of) {
+  __shared__ EsTab es_s[OPT ? ES_WAVES : 1];
   __shared__ uint32_t stage[ES_WAVES][ES_SW > 0 ? ES_SW : 1][64];
   __shared__ int16_t czs[ES_WAVES][ES_HI > 0 ? ES_HI : 1][64];
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(gt);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&es);
-    for (int i = threadIdx.x; i < (int)(sizeof(EsTab) / 4); i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
+  if constexpr (!OPT) es_stage_shared(es_s, gt);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int16_t* cz = &czs[wv][0][lane];
   const int g = blockIdx.x * ES_WAVES + wv;
+  if constexpr (OPT) es_stage_frame(&es_s[wv], of, e, g, nseg, lane);
+  const EsTab& es = es_s[OPT ? wv : 0];
   if (g >= nseg) return;  // (whole wave; no barrier follows)
   const EsSeg q = es_seg(e, g);
   const int bi = q.seg * 64 + lane;
@@ -626,6 +538,7 @@ constexpr int ES_SELF_MAX = 512;
 
 // incl[g] = the segment's end bit within its scan (k_ent_fscan / k_ent_emit3
 // read it as desc)
+template <bool OPT>
 __global__ void __launch_bounds__(256) k_ent_place(const EntGeo e, const int nseg, const uint32_t* __restrict__ gst,
                                                    const uint32_t* __restrict__ nbits,
                                                    const unsigned long long* __restrict__ agg,
@@ -681,7 +594,7 @@ __global__ void __launch_bounds__(256) k_ent_place(const EntGeo e, const int nse
     const unsigned long long An = lane63(incn);
     if (q.seg + 2 == q.nseg_s && sh && ((W1 + An - 1ull) >> 5) == ((W1 - 1ull) >> 5)) Wn = W1 + An;
   }
-  es_place(e, q, g, lane, valid, nvalid, last_seg, nb, inc - nb, pre, A, nullptr,
+  es_place<es_span<OPT>()>(e, q, g, lane, valid, nvalid, last_seg, nb, inc - nb, pre, A, nullptr,
            gst + (size_t)g * ES_MAXW * 64 + lane, (int)((nb + 31u) >> 5), raw, ffs, info, scan_bits, fuse, tailx, Wn,
            raw + raw_base(e, q.f, q.s), true);
 }
@@ -697,7 +610,8 @@ constexpr int EM_CHUNK = 1024;
 // frame-relative, tot[f] the frame's total.  OFFS: also each segment's first
 // output byte, from the frame's own prefixes, and the frame's markers.
 // (Replaced a hipCUB scan -- two launches -- and a per-segment offset launch.)
-template <bool OFFS>
+// OPT: the frame's header and its length come from its OptFrame.
+template <bool OFFS, bool OPT>
 __global__ void __launch_bounds__(1024) k_ent_fscan(const EntGeo e, const unsigned long long* __restrict__ in,
                                                     unsigned long long* __restrict__ out,
                                                     unsigned long long* __restrict__ tot,
@@ -706,7 +620,8 @@ __global__ void __launch_bounds__(1024) k_ent_fscan(const EntGeo e, const unsign
                                                     unsigned long long* __restrict__ outoff,
                                                     const uint8_t* __restrict__ hdr, uint8_t* __restrict__ file,
                                                     long long stride, unsigned long long* __restrict__ lengths,
-                                                    const uint32_t* __restrict__ badseg) {
+                                                    const uint32_t* __restrict__ badseg,
+                                                    const OptFrame* __restrict__ of) {
   __shared__ unsigned long long s_w[16];
   __shared__ int s_bad;
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -737,8 +652,10 @@ __global__ void __launch_bounds__(1024) k_ent_fscan(const EntGeo e, const unsign
   if (t == 0) tot[f] = all;
   if constexpr (OFFS) {
     __syncthreads();  // the frame's prefixes (global, this workgroup's writes) are visible
+    const long long hl = OPT ? (long long)of[f].hdr_len : e.hdr;
+    const uint8_t* hsrc = OPT ? of[f].hdr : hdr + (long long)f * e.hdr;
     long long so[3];
-    long long p = e.hdr + ENT_SOS;
+    long long p = hl + ENT_SOS;
     for (int s2 = 0; s2 < 3; ++s2) {
       so[s2] = p;
       const unsigned long long nb = (info[2 * (f * 3 + s2) + 1] + 7) >> 3;
@@ -759,7 +676,7 @@ __global__ void __launch_bounds__(1024) k_ent_fscan(const EntGeo e, const unsign
     __syncthreads();
     if (b) s_bad = 1;
     uint8_t* dst = file + (long long)f * stride;
-    for (int i = t; i < e.hdr; i += 1024) dst[i] = hdr[(long long)f * e.hdr + i];
+    for (int i = t; i < hl; i += 1024) dst[i] = hsrc[i];
     if (t < 3) {
       uint8_t* m = dst + so[t] - ENT_SOS;
       const uint8_t sos[ENT_SOS] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)(t + 1), (uint8_t)(t == 0 ? 0x00 : 0x11),
@@ -877,27 +794,31 @@ __global__ void __launch_bounds__(256) k_ent_emit3(const EntGeo e, const int nse
 // coder's worst case would put block 64 seg, and ent_sizes' areas carry over.
 constexpr int RS_INTERVAL = 64;
 constexpr int RS_SLOT = 64 * 1660 / 32;
-static_assert(RS_SLOT * 32 == 64 * 1660, "whole words");
+static_assert(RS_SLOT * 32 == 64 * ENT_BLOCK_BITS, "whole words");
+// optimised tables: 64 blocks of at most 1665 bits are exactly 3330 words, and
+// the packed areas are sized with that bound (ent_geo_opt)
+constexpr int RS_SLOT_OPT = 64 * ENT_BLOCK_BITS_OPT / 32;
+static_assert(RS_SLOT_OPT * 32 == 64 * ENT_BLOCK_BITS_OPT, "whole words");
+template <bool OPT>
+constexpr int rs_slot() { return OPT ? RS_SLOT_OPT : RS_SLOT; }
 constexpr int RS_DRI = 6;  // FF DD 00 04 Ri(2)
 
 int ent_restart_interval() { return RS_INTERVAL; }
 
+template <bool OPT>
 __global__ void __launch_bounds__(64 * ES_WAVES) __attribute__((amdgpu_waves_per_eu(ES_WPE))) k_rst_code(
     const EntGeo e, const int nseg, const int16_t* __restrict__ coeffs, const EsTab* __restrict__ gt,
     uint32_t* gst, uint32_t* __restrict__ raw, unsigned long long* __restrict__ agg, uint32_t* __restrict__ badseg,
-    unsigned long long* __restrict__ ffs) {
-  __shared__ EsTab es;
+    unsigned long long* __restrict__ ffs, const OptFrame* __restrict__ of) {
+  __shared__ EsTab es_s[OPT ? ES_WAVES : 1];
   __shared__ uint32_t stage[ES_WAVES][ES_SW > 0 ? ES_SW : 1][64];
   __shared__ int16_t czs[ES_WAVES][ES_HI > 0 ? ES_HI : 1][64];
-  {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(gt);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&es);
-    for (int i = threadIdx.x; i < (int)(sizeof(EsTab) / 4); i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
+  if constexpr (!OPT) es_stage_shared(es_s, gt);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int16_t* cz = &czs[wv][0][lane];
   const int g = blockIdx.x * ES_WAVES + wv;
+  if constexpr (OPT) es_stage_frame(&es_s[wv], of, e, g, nseg, lane);
+  const EsTab& es = es_s[OPT ? wv : 0];
   if (g >= nseg) return;  // (whole wave; no barrier follows)
   const EsSeg q = es_seg(e, g);
   const int bi = q.seg * 64 + lane;
@@ -922,27 +843,32 @@ __global__ void __launch_bounds__(64 * ES_WAVES) __attribute__((amdgpu_waves_per
   const uint32_t inc = wave_incl_sum(nb, lane);
   const unsigned long long A = lane63(inc);  // (<= 64 * 1660 bits)
   // the lane reads back its own staged words: LDS slots and, past ES_SW, its own global stores
-  es_place(e, q, g, lane, valid, nvalid, true, nb, inc - nb, 0ull, A, st, ov, k, raw, ffs, nullptr, nullptr, false, 0u,
-           0ull, raw + raw_base(e, q.f, q.s) + (long long)q.seg * RS_SLOT, false);
+  es_place<es_span<OPT>()>(e, q, g, lane, valid, nvalid, true, nb, inc - nb, 0ull, A, st, ov, k, raw, ffs, nullptr,
+                           nullptr, false, 0u, 0ull,
+                           raw + raw_base(e, q.f, q.s) + (long long)q.seg * rs_slot<OPT>(), false);
   if (lane == 0) {
     agg[g] = A;
     badseg[g] = any_bad ? 1u : 0u;
   }
 }
 
+template <bool OPT>
 __global__ void __launch_bounds__(1024) k_rst_fscan(const EntGeo e, const unsigned long long* __restrict__ agg,
                                                     const unsigned long long* __restrict__ ffs,
                                                     unsigned long long* __restrict__ outoff,
                                                     const uint8_t* __restrict__ hdr, uint8_t* __restrict__ file,
                                                     long long stride, unsigned long long* __restrict__ lengths,
                                                     unsigned long long* __restrict__ scan_bits,
-                                                    const uint32_t* __restrict__ badseg) {
+                                                    const uint32_t* __restrict__ badseg,
+                                                    const OptFrame* __restrict__ of) {
   __shared__ unsigned long long s_w[16], s_bits[3], s_first[3];
   __shared__ int s_bad;
   const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int n = e.sfirst[3];
   const long long g0 = (long long)f * n;
-  const long long hl = e.hdr + RS_DRI;
+  const long long h0 = OPT ? (long long)of[f].hdr_len : e.hdr;  // the header before DRI
+  const uint8_t* hsrc = OPT ? of[f].hdr : hdr + (long long)f * e.hdr;
+  const long long hl = h0 + RS_DRI;
   if (t < 3) s_bits[t] = 0ull;
   if (t == 0) s_bad = 0;
   __syncthreads();
@@ -983,10 +909,10 @@ __global__ void __launch_bounds__(1024) k_rst_fscan(const EntGeo e, const unsign
     run += bytes_of(i);
   }
   uint8_t* dst = file + (long long)f * stride;
-  for (int i = t; i < e.hdr; i += 1024) dst[i] = hdr[(long long)f * e.hdr + i];
+  for (int i = t; i < h0; i += 1024) dst[i] = hsrc[i];
   if (t == 0) {
     const uint8_t dri[RS_DRI] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(RS_INTERVAL >> 8), (uint8_t)(RS_INTERVAL & 255)};
-    for (int i = 0; i < RS_DRI; ++i) dst[e.hdr + i] = dri[i];
+    for (int i = 0; i < RS_DRI; ++i) dst[h0 + i] = dri[i];
   }
   __syncthreads();
   if (t < 3) {
@@ -1004,6 +930,7 @@ __global__ void __launch_bounds__(1024) k_rst_fscan(const EntGeo e, const unsign
   }
 }
 
+template <bool OPT>
 __global__ void __launch_bounds__(256) k_rst_emit(const EntGeo e, const int nseg,
                                                   const unsigned long long* __restrict__ agg,
                                                   const uint32_t* __restrict__ raw,
@@ -1022,12 +949,23 @@ __global__ void __launch_bounds__(256) k_rst_emit(const EntGeo e, const int nseg
     }
     dst += 2;
   }
-  em_copy(raw + raw_base(e, q.f, q.s) + (long long)q.seg * RS_SLOT, 0ull, (agg[g] + 7) >> 3, dst, sbuf[wv], lane);
+  em_copy(raw + raw_base(e, q.f, q.s) + (long long)q.seg * rs_slot<OPT>(), 0ull, (agg[g] + 7) >> 3, dst, sbuf[wv],
+          lane);
 }
 
 // ------------------------------------------------------------ driver --
 
-EntGeo ent_geo(const Geo& g) {
+// Capacity derivation.  A block's worst case is ENT_BLOCK_BITS (1660 >= 1658:
+// DC 9 + 11 bits, 63 x (16 + 10) AC) with the Annex K tables and
+// ENT_BLOCK_BITS_OPT (1665: DC 16 + 11, 63 x (16 + 10)) with optimised ones,
+// where any symbol may get a 16-bit code.  cap_w[s] = the scan's blocks at that
+// bound, in words, + 2; a restart interval's slot is 64 blocks at the bound
+// (RS_SLOT / RS_SLOT_OPT); a block's staged words ES_MAXW = 53 cover both.  The
+// optimised headers are never longer than the template (at most 12 DC and 162
+// AC symbols: the histogram clamps like the coder), so the file bounds differ
+// only through cap_w: ent_capacity_opt > ent_capacity, and the optimised route
+// has its own capacity call while the existing calls keep their values.
+static EntGeo ent_geo_bits(const Geo& g, int block_bits) {
   EntGeo e{};
   const int ny = g.nby * g.nbx, nc = g.ncy * g.ncx;
   e.nb = ny + 2 * nc;
@@ -1037,12 +975,15 @@ EntGeo ent_geo(const Geo& g) {
   e.first[3] = e.nb;
   e.sfirst[0] = 0;
   for (int s = 0; s < 3; ++s) e.sfirst[s + 1] = e.sfirst[s] + (e.first[s + 1] - e.first[s] + 63) / 64;
-  e.cap_w[0] = (int)(((long long)ny * 1660 + 31) / 32) + 2;
-  e.cap_w[1] = e.cap_w[2] = (int)(((long long)nc * 1660 + 31) / 32) + 2;
+  e.cap_w[0] = (int)(((long long)ny * block_bits + 31) / 32) + 2;
+  e.cap_w[1] = e.cap_w[2] = (int)(((long long)nc * block_bits + 31) / 32) + 2;
   e.raw_w = (long long)e.cap_w[0] + 2LL * e.cap_w[1];
   e.hdr = ENT_HDR;
   return e;
 }
+
+EntGeo ent_geo(const Geo& g) { return ent_geo_bits(g, ENT_BLOCK_BITS); }
+EntGeo ent_geo_opt(const Geo& g) { return ent_geo_bits(g, ENT_BLOCK_BITS_OPT); }
 
 // worst case file: header + 3 SOS + every scan at 1660 bits per block, all bytes stuffed + EOI
 long long ent_capacity(const Geo& g) {
@@ -1050,14 +991,21 @@ long long ent_capacity(const Geo& g) {
   return e.hdr + 3 * ENT_SOS + 2 * 4 * e.raw_w + 2;
 }
 
+// the same at 1665 bits per block; restart files: + DRI and 4 bytes per interval (ent_capacity_rst)
+long long ent_capacity_opt(const Geo& g, bool rst) {
+  const EntGeo e = ent_geo_opt(g);
+  return e.hdr + 3 * ENT_SOS + 2 * 4 * e.raw_w + 2 + (rst ? 6 + 4ll * e.sfirst[3] : 0);
+}
+
 // scratch sizes (bytes): [0] segment end bits (desc, from the second word),
 // segment totals (agg; reused for the output offsets once placed), their
 // per-frame prefix (segoff), per-lane bit counts, per-segment error flags; [1]
 // staged words (word-major per segment); [2] info; [3] packed scans; [4] 0xFF
 // counts per segment; [5] their prefix and the frame totals; [6] headers; [7]
-// unused.
+// the optimised route's per-frame state (OptFrame).  The packed scans are
+// sized for the optimised route's bound, which covers the standard one.
 void ent_sizes(const Geo& g, int n, size_t* sz) {
-  const EntGeo e = ent_geo(g);
+  const EntGeo e = ent_geo_opt(g);
   sz[2] = sizeof(unsigned long long) * 7 * n;  // 6 per frame (scan start / bits) + the frame's error flag
   sz[3] = sizeof(uint32_t) * e.raw_w * n;
   sz[6] = (size_t)e.hdr * n;
@@ -1067,15 +1015,28 @@ void ent_sizes(const Geo& g, int n, size_t* sz) {
   sz[1] = sizeof(uint32_t) * ES_MAXW * 64 * nseg;
   sz[4] = sizeof(unsigned long long) * (nseg + 1);
   sz[5] = sizeof(unsigned long long) * (nseg + 1 + n);  // + the frame totals (k_ent_fscan)
-  sz[7] = 0;
+  sz[7] = sizeof(OptFrame) * (size_t)n;
+}
+
+// The optimised route's front: zeroed counters, the symbol histogram, the
+// frames' tables and headers (jds_huffopt.hip) -- all on the stream, no host
+// read between the histogram and the file.
+static hipError_t launch_opt_front(const EntGeo& e, int n, int nseg, const int16_t* coeffs, bool rst,
+                                   const uint8_t* hdr_dev, const EsTab* est, OptFrame* of, hipStream_t s) {
+  hipError_t err = hipMemsetAsync(of, 0, sizeof(OptFrame) * (size_t)n, s);
+  if (err != hipSuccess) return err;
+  if ((err = launch_ent_hist(e, nseg, coeffs, rst, of, s)) != hipSuccess) return err;
+  return launch_opt_tables(n, est, hdr_dev, e.hdr, of, s);
 }
 
 // walk, (per-frame segment prefix for long scans,) placement, per-frame
 // offsets and markers, stuffing: 4 or 5 launches per batch of frames
+// (OPT: after launch_opt_front's three)
+template <bool OPT>
 static hipError_t launch_entropy_fused(const Geo& g, int n, const int16_t* coeffs, void* const* buf,
                                        const uint8_t* hdr_dev, const void* tab_dev, uint8_t* out, long long stride,
                                        unsigned long long* lengths, unsigned long long* scan_bits, hipStream_t s) {
-  const EntGeo e = ent_geo(g);
+  const EntGeo e = OPT ? ent_geo_opt(g) : ent_geo(g);
   const long long nseg_l = (long long)n * e.sfirst[3];
   if (nseg_l >= (1ll << 31)) return hipErrorInvalidValue;
   const int nseg = (int)nseg_l;
@@ -1090,31 +1051,36 @@ static hipError_t launch_entropy_fused(const Geo& g, int n, const int16_t* coeff
   auto* raw = (uint32_t*)buf[3];
   auto* ffs = (unsigned long long*)buf[4];
   auto* ffx = (unsigned long long*)buf[5];
+  OptFrame* of = OPT ? (OptFrame*)buf[7] : nullptr;
   const unsigned wg = (unsigned)((nseg + ES_WAVES - 1) / ES_WAVES);
   const unsigned wg4 = (unsigned)((nseg + 3) / 4);  // k_ent_place / k_ent_emit3: four segment waves per workgroup
   const EsTab* est = reinterpret_cast<const EsTab*>((const char*)tab_dev + sizeof(EntTab));
-  hipLaunchKernelGGL(k_ent_walk, dim3(wg), dim3(64 * ES_WAVES), 0, s, e, nseg, coeffs, est, ovf, nbits, agg, badseg,
-                     ffs);
-  kmark(s, "k_ent_walk");
-  hipError_t err = hipGetLastError();
+  hipError_t err;
+  if constexpr (OPT) {
+    if ((err = launch_opt_front(e, n, nseg, coeffs, false, hdr_dev, est, of, s)) != hipSuccess) return err;
+  }
+  hipLaunchKernelGGL(k_ent_walk<OPT>, dim3(wg), dim3(64 * ES_WAVES), 0, s, e, nseg, coeffs, est, ovf, nbits, agg,
+                     badseg, ffs, of);
+  kmark(s, OPT ? "k_ent_walk<opt>" : "k_ent_walk");
+  err = hipGetLastError();
   if (err != hipSuccess) return err;
   bool long_scan = false;
   for (int c = 0; c < 3; ++c) long_scan = long_scan || e.sfirst[c + 1] - e.sfirst[c] > ES_SELF_MAX;
   if (long_scan) {
-    hipLaunchKernelGGL(k_ent_fscan<false>, dim3(n), dim3(1024), 0, s, e, agg, segoff, ffx, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, 0ll, nullptr, nullptr);
+    hipLaunchKernelGGL((k_ent_fscan<false, false>), dim3(n), dim3(1024), 0, s, e, agg, segoff, ffx, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, 0ll, nullptr, nullptr, nullptr);
     kmark(s, "k_ent_fscan<0>");
   }
-  hipLaunchKernelGGL(k_ent_place, dim3(wg4), dim3(256), 0, s, e, nseg, ovf, nbits, agg, segoff, desc, raw, ffs, info,
-                     scan_bits);
-  kmark(s, "k_ent_place");
+  hipLaunchKernelGGL(k_ent_place<OPT>, dim3(wg4), dim3(256), 0, s, e, nseg, ovf, nbits, agg, segoff, desc, raw, ffs,
+                     info, scan_bits);
+  kmark(s, OPT ? "k_ent_place<opt>" : "k_ent_place");
   if ((err = hipGetLastError()) != hipSuccess) return err;
   // frame-relative 0xFF prefixes, each segment's output offset and the frame's
   // markers in one launch; frame totals in ffx[nseg + 1 ..]
   unsigned long long* fftot = ffx + nseg + 1;
-  hipLaunchKernelGGL(k_ent_fscan<true>, dim3(n), dim3(1024), 0, s, e, ffs, ffx, fftot, desc, info, outoff, hdr_dev,
-                     out, stride, lengths, badseg);
-  kmark(s, "k_ent_fscan<1>");
+  hipLaunchKernelGGL((k_ent_fscan<true, OPT>), dim3(n), dim3(1024), 0, s, e, ffs, ffx, fftot, desc, info, outoff,
+                     hdr_dev, out, stride, lengths, badseg, of);
+  kmark(s, OPT ? "k_ent_fscan<1,opt>" : "k_ent_fscan<1>");
   hipLaunchKernelGGL(k_ent_emit3, dim3(wg4), dim3(256), 0, s, e, nseg, desc, info, raw, outoff, out, stride);
   kmark(s, "k_ent_emit3");
   return hipGetLastError();
@@ -1123,7 +1089,13 @@ static hipError_t launch_entropy_fused(const Geo& g, int n, const int16_t* coeff
 hipError_t launch_entropy(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
                           const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
                           unsigned long long* scan_bits, hipStream_t s) {
-  return launch_entropy_fused(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
+  return launch_entropy_fused<false>(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
+}
+
+hipError_t launch_entropy_opt(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
+                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
+                              unsigned long long* scan_bits, hipStream_t s) {
+  return launch_entropy_fused<true>(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
 }
 
 // The restart header template: the plain one, then DRI.  Returns its length or -1.
@@ -1144,13 +1116,15 @@ long long ent_capacity_rst(const Geo& g) {
   const EntGeo e = ent_geo(g);
   return ent_capacity(g) + RS_DRI + 4ll * e.sfirst[3];
 }
+static_assert(RS_DRI == 6, "ent_capacity_opt's DRI bytes");
 
 // code + place, per-frame offsets and markers, stuffing: 3 launches per batch of
 // frames, scratch as launch_entropy's (ent_sizes)
-hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
-                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
-                              unsigned long long* scan_bits, hipStream_t s) {
-  const EntGeo e = ent_geo(g);
+template <bool OPT>
+static hipError_t launch_entropy_rst_t(const Geo& g, int n, const int16_t* coeffs, void* const* buf,
+                                       const uint8_t* hdr_dev, const void* tab_dev, uint8_t* out, long long stride,
+                                       unsigned long long* lengths, unsigned long long* scan_bits, hipStream_t s) {
+  const EntGeo e = OPT ? ent_geo_opt(g) : ent_geo(g);
   const long long nseg_l = (long long)n * e.sfirst[3];
   if (nseg_l >= (1ll << 31)) return hipErrorInvalidValue;
   const int nseg = (int)nseg_l;
@@ -1161,19 +1135,48 @@ hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* 
   auto* ovf = (uint32_t*)buf[1];
   auto* raw = (uint32_t*)buf[3];
   auto* ffs = (unsigned long long*)buf[4];
+  OptFrame* of = OPT ? (OptFrame*)buf[7] : nullptr;
   const unsigned wg = (unsigned)((nseg + ES_WAVES - 1) / ES_WAVES);
   const unsigned wg4 = (unsigned)((nseg + 3) / 4);
   const EsTab* est = reinterpret_cast<const EsTab*>((const char*)tab_dev + sizeof(EntTab));
-  hipLaunchKernelGGL(k_rst_code, dim3(wg), dim3(64 * ES_WAVES), 0, s, e, nseg, coeffs, est, ovf, raw, agg, badseg, ffs);
-  kmark(s, "k_rst_code");
-  hipError_t err = hipGetLastError();
+  hipError_t err;
+  if constexpr (OPT) {
+    if ((err = launch_opt_front(e, n, nseg, coeffs, true, hdr_dev, est, of, s)) != hipSuccess) return err;
+  }
+  hipLaunchKernelGGL(k_rst_code<OPT>, dim3(wg), dim3(64 * ES_WAVES), 0, s, e, nseg, coeffs, est, ovf, raw, agg,
+                     badseg, ffs, of);
+  kmark(s, OPT ? "k_rst_code<opt>" : "k_rst_code");
+  err = hipGetLastError();
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(k_rst_fscan, dim3(n), dim3(1024), 0, s, e, agg, ffs, outoff, hdr_dev, out, stride, lengths,
-                     scan_bits, badseg);
-  kmark(s, "k_rst_fscan");
-  hipLaunchKernelGGL(k_rst_emit, dim3(wg4), dim3(256), 0, s, e, nseg, agg, raw, outoff, out, stride);
-  kmark(s, "k_rst_emit");
+  hipLaunchKernelGGL(k_rst_fscan<OPT>, dim3(n), dim3(1024), 0, s, e, agg, ffs, outoff, hdr_dev, out, stride, lengths,
+                     scan_bits, badseg, of);
+  kmark(s, OPT ? "k_rst_fscan<opt>" : "k_rst_fscan");
+  hipLaunchKernelGGL(k_rst_emit<OPT>, dim3(wg4), dim3(256), 0, s, e, nseg, agg, raw, outoff, out, stride);
+  kmark(s, OPT ? "k_rst_emit<opt>" : "k_rst_emit");
   return hipGetLastError();
 }
 
+hipError_t launch_entropy_rst(const Geo& g, int n, const int16_t* coeffs, void* const* buf, const uint8_t* hdr_dev,
+                              const void* tab_dev, uint8_t* out, long long stride, unsigned long long* lengths,
+                              unsigned long long* scan_bits, hipStream_t s) {
+  return launch_entropy_rst_t<false>(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
+}
+
+hipError_t launch_entropy_rst_opt(const Geo& g, int n, const int16_t* coeffs, void* const* buf,
+                                  const uint8_t* hdr_dev, const void* tab_dev, uint8_t* out, long long stride,
+                                  unsigned long long* lengths, unsigned long long* scan_bits, hipStream_t s) {
+  return launch_entropy_rst_t<true>(g, n, coeffs, buf, hdr_dev, tab_dev, out, stride, lengths, scan_bits, s);
+}
+
+// The Annex K table idx (0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma): what
+// a table class falls back to (jds_selftest_huffopt).
+int ent_std_table(int idx, const uint8_t** bits, const uint8_t** vals) {
+  const uint8_t* b[4] = {K3_BITS, K5_BITS, K4_BITS, K6_BITS};
+  const uint8_t* v[4] = {DC_VALS, K5_VALS, DC_VALS, K6_VALS};
+  *bits = b[idx & 3];
+  *vals = v[idx & 3];
+  return (idx & 1) ? 162 : 12;
+}
+
 }  // namespace jds
+

@@ -164,6 +164,12 @@ _SIGS = {
     'jds_encode_jfif_rst': (C.c_int, [_P, C.POINTER(Params), C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64,
                                       C.POINTER(C.c_int64), _P]),
     'jds_plan_entropy_decode_rst': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
+    'jds_plan_entropy_capacity_opt': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    'jds_plan_entropy_opt': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    'jds_encode_jfif_opt': (C.c_int, [_P, C.POINTER(Params), C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64,
+                                      C.POINTER(C.c_int64), _P]),
+    'jds_selftest_huffopt': (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'jds_selftest_huffopt_dev': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'jds_jfif_parse': (C.c_int, [_P, C.c_int64, C.POINTER(JfifInfo)]),
     'jds_decode_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(JfifInfo)]),
     'jds_decompress_jfif': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(JfifInfo)]),

@@ -27,10 +27,12 @@ def restart_info() -> Tuple[int, int]:
 
 
 def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarray,
-                device: int = 0, restart_interval: int = 0) -> Tuple[bytes, List[int]]:
+                device: int = 0, restart_interval: int = 0, optimize: bool = False) -> Tuple[bytes, List[int]]:
     """One frame: all_quantized_coeffs (int16, Y/Cb/Cr blocks) -> (file bytes,
     entropy-coded bits of the Y, Cb, Cr scans).  restart_interval: 0, or restart_info()[0]
-    for a file with DRI and RSTm markers (every interval an independent stream)."""
+    for a file with DRI and RSTm markers (every interval an independent stream).  optimize:
+    the frame's own Huffman tables instead of the Annex K ones (jds_encode_jfif_opt,
+    DESIGN.md "Optimised tables")."""
     p = make_params(50, qtable, mode, False, np.zeros(3))
     geo = _abi.geometry(p, H, W)
     cf = np.ascontiguousarray(coeffs, dtype=np.int16).reshape(-1)
@@ -43,7 +45,10 @@ def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarra
     while True:
         out = np.empty(cap, np.uint8)
         with _abi.lease(device) as ctx:
-            if restart_interval:
+            if optimize:
+                rc = lib().jds_encode_jfif_opt(ctx.handle, C.byref(p), H, W, int(restart_interval), cf.ctypes.data,
+                                               out.ctypes.data, cap, C.byref(n), bits)
+            elif restart_interval:
                 rc = lib().jds_encode_jfif_rst(ctx.handle, C.byref(p), H, W, int(restart_interval), cf.ctypes.data,
                                                out.ctypes.data, cap, C.byref(n), bits)
             else:
@@ -124,6 +129,33 @@ def host_decode_jfif(data, subseq_bits: int = 1024):
     return cf, [int(r) for r in rounds]
 
 
+def optimal_table(freq):
+    """Test aid (jds_selftest_huffopt, no GPU): the optimised table of freq[0..255] by the
+    host/device core of k_ent_opt_tables -> (BITS[1..16], HUFFVAL, fell_back)."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    if f.shape != (256,):
+        raise ValueError('freq: 256 counts')
+    bits, vals = np.zeros(16, np.uint8), np.zeros(256, np.uint8)
+    n, fell = C.c_int32(0), C.c_int32(0)
+    check(lib().jds_selftest_huffopt(f.ctypes.data, bits.ctypes.data, vals.ctypes.data, C.byref(n), C.byref(fell)))
+    return [int(b) for b in bits], [int(v) for v in vals[:n.value]], bool(fell.value)
+
+
+def optimal_tables_dev(freqs, device: int = 0):
+    """Test aid (jds_selftest_huffopt_dev): k_ent_opt_tables on n histograms (n x 256 counts)
+    -> [(BITS, HUFFVAL, fell_back)]."""
+    f = np.ascontiguousarray(freqs, dtype=np.uint32)
+    if f.ndim != 2 or f.shape[1] != 256 or not len(f):
+        raise ValueError('freqs: n x 256 counts')
+    m = len(f)
+    bits, vals = np.zeros((m, 16), np.uint8), np.zeros((m, 256), np.uint8)
+    n, fell = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    with _abi.lease(device) as ctx:
+        check(lib().jds_selftest_huffopt_dev(ctx.handle, f.ctypes.data, m, bits.ctypes.data, vals.ctypes.data,
+                                             n.ctypes.data, fell.ctypes.data))
+    return [([int(b) for b in bits[i]], [int(v) for v in vals[i, :n[i]]], bool(fell[i])) for i in range(m)]
+
+
 def _jpeg_dict(info: _abi.JpegInfo) -> dict:
     names = ('dc0', 'dc1', 'ac0', 'ac1')
     huff = {nm: (list(info.huff[i].bits), list(info.huff[i].vals)[:info.huff[i].n_vals])
@@ -194,13 +226,19 @@ def bitrate_from_jfif(nbytes: int, shape) -> dict:
 
 class PlanEntropy:
     """Device-resident entropy coding for a jds_plan: out[i] holds frame i's file.
-    restart_interval (0, or restart_info()[0]): capacity, run and decode follow it."""
+    restart_interval (0, or restart_info()[0]): capacity, run and decode follow it.
+    optimize: run() writes files with per-frame optimised tables (jds_plan_entropy_opt; its own,
+    larger capacity); decode() reads only the plan's standard header and marks such files
+    JDS_DEC_HEADER."""
 
-    def __init__(self, plan: _abi.Plan, restart_interval: int = 0):
+    def __init__(self, plan: _abi.Plan, restart_interval: int = 0, optimize: bool = False):
         self.plan = plan
         self.restart_interval = int(restart_interval)
+        self.optimize = bool(optimize)
         cap = C.c_int64(0)
-        if self.restart_interval:
+        if self.optimize:
+            check(lib().jds_plan_entropy_capacity_opt(plan.handle, self.restart_interval, C.byref(cap)))
+        elif self.restart_interval:
             check(lib().jds_plan_entropy_capacity_rst(plan.handle, self.restart_interval, C.byref(cap)))
         else:
             check(lib().jds_plan_entropy_capacity(plan.handle, C.byref(cap)))
@@ -210,7 +248,10 @@ class PlanEntropy:
             stream: int | None = None):
         if stream is None:
             stream = lib().jds_ctx_stream(self.plan.ctx.handle)
-        if self.restart_interval:
+        if self.optimize:
+            check(lib().jds_plan_entropy_opt(self.plan.handle, self.restart_interval, coeffs_dev, out_dev, out_stride,
+                                             lengths_dev, scan_bits_dev or None, stream))
+        elif self.restart_interval:
             check(lib().jds_plan_entropy_rst(self.plan.handle, self.restart_interval, coeffs_dev, out_dev, out_stride,
                                              lengths_dev, scan_bits_dev or None, stream))
         else:

@@ -1,7 +1,12 @@
 """Time the JPEG entropy coder (jds_plan_entropy) on one 64 x 1080p Q50 4:2:0
 batch of codec coefficients (FRAMES / HEIGHT / WIDTH override the batch); prints one JSON line with ms per batch and a
 digest of the files (A/B builds must produce the same digest).  Run with
-JDS_LIB_PATH=... for a variant build."""
+JDS_LIB_PATH=... for a variant build.
+
+--optimize: the standard and the optimised-table routes (DESIGN.md "Optimised
+tables"), each for plain and restart files, on the same batch: ms per batch, the
+files' bytes, and per-kernel times from the plan's launch marks (a separate,
+marked run of each route); one JSON line."""
 import hashlib
 import json
 import os
@@ -15,6 +20,33 @@ import torch  # noqa: E402
 from jds import _abi, codec, entropy  # noqa: E402
 from engines.quantizer import scale_quant_matrix  # noqa: E402
 from utils.constants import JPEG_LUMA_Q50  # noqa: E402
+
+
+def time_route(plan, cf, B, s, reps, restart_interval, optimize):
+    ent = entropy.PlanEntropy(plan, restart_interval, optimize=optimize)
+    files = torch.empty((B, ent.capacity), dtype=torch.uint8, device=cf.device)
+    lengths = torch.zeros(B, dtype=torch.int64, device=cf.device)
+    args = (cf.data_ptr(), files.data_ptr(), ent.capacity, lengths.data_ptr(), 0, s.cuda_stream)
+    for _ in range(3):
+        ent.run(*args)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(s)
+    for _ in range(reps):
+        ent.run(*args)
+    e1.record(s)
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    plan.profile(True)
+    plan.profile_read()
+    for _ in range(reps):
+        ent.run(*args)
+    torch.cuda.synchronize()
+    kern, span = plan.profile_read()
+    plan.profile(False)
+    ln = lengths.cpu().tolist()
+    assert all(v > 0 for v in ln)
+    return {'ms_per_batch': ms, 'bytes': int(sum(ln)), 'capacity': ent.capacity,
+            'kernels_ms': {k: v[0] / reps for k, v in kern.items()}, 'marked_ms_per_batch': span / reps}
 
 
 def main():
@@ -32,6 +64,19 @@ def main():
     torch.cuda.synchronize()
     plan.run(rgb.data_ptr(), out.data_ptr(), cf.data_ptr(), st.data_ptr(), 0, s.cuda_stream)
     torch.cuda.synchronize()
+    if '--optimize' in sys.argv[1:]:
+        reps = int(os.environ.get('REPS', '20'))
+        r = {'frames': B, 'H': H, 'W': W, 'quality': 50, 'mode': '4:2:0', 'reps': reps}
+        for name, ri, opt in (('standard_plain', 0, False), ('standard_restart', 64, False),
+                              ('optimised_plain', 0, True), ('optimised_restart', 64, True)):
+            r[name] = time_route(plan, cf, B, s, reps, ri, opt)
+        for form in ('plain', 'restart'):
+            a, b = r['standard_' + form], r['optimised_' + form]
+            r['saved_' + form] = {'bytes': a['bytes'] - b['bytes'], 'fraction': 1.0 - b['bytes'] / a['bytes'],
+                                  'extra_ms_per_batch': b['ms_per_batch'] - a['ms_per_batch']}
+        print(json.dumps(r))
+        plan.close()
+        return
     ent = entropy.PlanEntropy(plan)
     files = torch.empty((B, ent.capacity), dtype=torch.uint8, device=dev)
     lengths = torch.zeros(B, dtype=torch.int64, device=dev)
