@@ -615,6 +615,89 @@ int jds_jpeg_batch_to_rgb(jds_ctx* ctx, const uint8_t* const* data, const int64_
 int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
                             uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items);
 
+/* Lossless transcode (DESIGN.md "Transcode"; byte-for-byte definition:
+ * tests/transcode_ref.py): the coefficients of jds_decode_jpeg written back as
+ * the file form everybody else writes -- ONE interleaved scan (Ns = 3,
+ * components 1, 2, 3; Y with Huffman tables 0/0, Cb and Cr with 1/1, whatever
+ * the input assigned; no DRI) -- by the interleaved instantiation of the
+ * one-pass coder (csrc/jds_entropy_mcu.hip).  No pixel and no coefficient
+ * changes.  The output is
+ *     SOI | prefix | DHT 0x00, 0x10, 0x01, 0x11 | SOS | scan | EOI
+ *   prefix: every marker segment of the input before its first SOS, verbatim
+ *     and in order, except DHT and DRI (APPn, COM, DQT, SOF0 untouched); what
+ *     follows the first SOS other than scan data is dropped;
+ *   tables: optimize == 0 the T.81 Annex K tables; otherwise the K.2 / K.3
+ *     tables of jds_encode_jfif_opt built on the device from the symbol counts
+ *     of THIS scan (luma from the Y blocks, chroma from Cb and Cr together,
+ *     padding blocks included; the > 32-bit fallback per table as there);
+ *   padding: the blocks that pad the image to whole MCUs are libjpeg's dummy
+ *     blocks: AC zero, DC = the DC of the preceding block of the component in
+ *     scan order, so each codes as a zero DC difference and EOB and the next
+ *     real block predicts from the last real one;
+ *   a restart file is written without intervals, its DC differences taken
+ *     across the former boundaries.
+ * A block baseline Huffman coding cannot express (DC difference category above
+ * 11 -- joining a hostile restart file's intervals can make one -- or AC
+ * category above 10) is an error of that file: JDS_EINVAL "not
+ * baseline-codable", nothing written.
+ *
+ * jds_encode_jpeg: one file from host coefficients in jds_decode_jpeg's layout.
+ *   Reads H, W, subsampling, grid_cols / grid_rows (they must be T.81's grids of
+ *   H x W: JDS_EINVAL otherwise; with reference_grid set a plan's coefficients
+ *   are that layout as they are) and, without a prefix, tq and qtable of info.
+ *   coeffs: 64 * the grids' blocks entries.  prefix: prefix_len header bytes
+ *   to place after SOI (DQT and SOF0 among them: the caller answers for their
+ *   agreement with info), or NULL: APP0 (JFIF 1.01), one DQT per table id in
+ *   use, SOF0.  *out_len = the file's bytes, also when out_cap is too small
+ *   (JDS_EINVAL, nothing written).  Synchronous.
+ * jds_jpeg_transcode: parse, decode and write on the context's stream; the
+ *   coefficients never leave the device.  The error contract of
+ *   jds_decode_jpeg; nothing is written on a defective scan.  info: as
+ *   jds_decode_jpeg fills it.  out_cap too small: as above.
+ * jds_jpeg_batch_transcode: the batch decode's launches (jds_jpeg_batch_to_rgb
+ *   without the inverse), then one set of writer launches over all files.
+ *   Items by that call's contract: a file the parser rejects is an item error
+ *   (rc), a defective scan sets status, a file that is not baseline-codable
+ *   gets rc JDS_EINVAL; the call goes on and returns JDS_OK, jds_last_error
+ *   naming the first such file.  Such a file gets out_len 0 and out_off -1 and
+ *   no other file's bytes depend on it.  The files are packed in batch order,
+ *   each at a multiple of 256; the bytes between a file's end and the next
+ *   multiple of 256 are never written; *out_bytes = the last file's end rounded
+ *   up to 256.  Synchronous: the per-file lengths are read back once between
+ *   the placement and the emit, so no worst-case buffer is needed; out_cap <
+ *   *out_bytes: JDS_EINVAL with the need in *out_bytes, items filled, nothing
+ *   written.  out: host memory, or with out_on_device != 0 memory of the
+ *   context's device.  n == 0 is valid.
+ * jds_selftest_jpeg_transcode: test-only, host only: the host decode model
+ *   (jds_selftest_jpegdec), then the writer on the host through the kernels'
+ *   shared lookup, predecessor rule, splicer and table builder
+ *   (csrc/jds_entropy_mcu.hpp, csrc/jds_huffopt.hpp), a serial bit writer
+ *   standing in for the lanes.  jds_selftest_jpeg_encode: jds_encode_jpeg's
+ *   model likewise.  No GPU. */
+typedef struct {
+  int32_t rc;        /* JDS_OK, or the code this file alone would get */
+  uint32_t status;   /* JDS_DEC_* bits of its scan data; 0: decoded */
+  int64_t H, W;
+  int32_t subsampling, interleaved;
+  int64_t out_off;   /* its first byte in the output, a multiple of 256; -1: not written */
+  int64_t out_len;   /* its bytes; 0: not written */
+} jds_jpeg_transcode_item;
+int jds_encode_jpeg(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize,
+                    const uint8_t* prefix, int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len);
+int jds_jpeg_transcode(jds_ctx* ctx, const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                       int64_t* out_len, jds_jpeg_info* info);
+int jds_jpeg_batch_transcode(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                             jds_jpeg_transcode_item* items, int64_t* out_bytes);
+int jds_selftest_jpeg_transcode(const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                                int64_t* out_len);
+int jds_selftest_jpeg_encode(const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize, const uint8_t* prefix,
+                             int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len);
+/* Test-only: the writer's symbol histogram on the device (k_mcu_hist) for host
+ * coefficients in jds_decode_jpeg's layout: counts[2][272] = luma, chroma x
+ * (16 DC categories, 256 AC symbols). */
+int jds_selftest_jpeg_hist_dev(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, uint32_t* counts);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

@@ -19,6 +19,7 @@
 
 #include "jds_dct16.hpp"
 #include "jds_dct8.hpp"
+#include "jds_entropy_mcu_dev.hpp"
 #include "jds_huffdec.hpp"
 #include "jds_huffopt.hpp"
 #include "jds_internal.hpp"
@@ -218,6 +219,7 @@ struct jds_ctx {
   // jds_jpeg_batch_to_rgb: everything a batch uploads (file bytes, table sets, MCU and inverse records, tile maps,
   // interval lists, initial status words) is gathered in one pinned host buffer and copied once to bat
   DevBuf bat;
+  DevBuf mcu_up, mcu_scr;  // interleaved-scan writer (jds_jpeg_transcode): its uploads (records, segment table, prefixes), scratch
   void* bat_host = nullptr;
   size_t bat_host_cap = 0;
   // jds_ctx_profile: launch marks of the batch calls on this context
@@ -682,6 +684,8 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->dec_iv.release();
   c->dec_mcu.release();
   c->bat.release();
+  c->mcu_up.release();
+  c->mcu_scr.release();
   if (c->bat_host) (void)hipHostFree(c->bat_host);
   marks_release(c->marks);
   c->gen_tab.release();
@@ -2359,21 +2363,15 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
   return JDS_OK;
 }
 
-int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
-                          int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
-                          uint32_t* rounds_out) {
-  if (!c) return fail(JDS_EINVAL, "null argument");
-  BatchPlan bp;
-  int rc = batch_layout(data, lens, n, items, bp);
-  if (rc) return rc;
-  if (rounds_out) *rounds_out = 0;
-  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
-    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+// The launches of a laid-out batch with at least one record: upload, entropy
+// decode into c->ent_cf (file k's coefficients at bp.recs[k].coef_off), then
+// with `inverse` the batch inverse into rgb; the status words into items.
+// Synchronous.  Without `inverse` (jds_jpeg_batch_transcode) rgb is not used.
+static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
+                     int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, uint32_t* rounds_out,
+                     bool inverse) {
+  int rc;
   const int nv = (int)bp.recs.size();
-  if (nv == 0) {
-    batch_note(bp);
-    return JDS_OK;
-  }
   hipStream_t s = c->stream;
   HIP_TRY(hipSetDevice(c->device));
   int lane_max;
@@ -2474,7 +2472,7 @@ int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t*
   HIP_TRY(c->dec_mcu.ensure(sizeof(int16_t) * (size_t)dcs_n));
   HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)bp.coef_entries));
   uint8_t* dst = rgb;
-  if (!rgb_on_device) {
+  if (inverse && !rgb_on_device) {
     HIP_TRY(c->out.ensure((size_t)bp.rgb_bytes));
     dst = (uint8_t*)c->out.p;
   }
@@ -2498,9 +2496,10 @@ int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t*
     return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
   HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivil), (long long)iv_il.size(), tabs_d, cf_d, st_d, s, mcu_d));
   HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivpl), (long long)iv_pl.size(), tabs_d, cf_d, st_d, s, nullptr));
-  HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles, st_d,
-                                cf_d, dst, s));
-  if (!rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
+  if (inverse)
+    HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
+                                  st_d, cf_d, dst, s));
+  if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
     for (int k = 0; k < nv; ++k) {
       const JInvRec& r = bp.recs[(size_t)k];
       HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)r.a.H * (size_t)r.a.W * 3, hipMemcpyDeviceToHost,
@@ -2513,7 +2512,370 @@ int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t*
   HIP_TRY(hipStreamSynchronize(s));
   for (int k = 0; k < nv; ++k) items[bp.file_of[(size_t)k]].status = st0[(size_t)k];
   if (rounds_out) *rounds_out = rounds;
+  return JDS_OK;
+}
+
+int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                          int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                          uint32_t* rounds_out) {
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  BatchPlan bp;
+  int rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  if (rounds_out) *rounds_out = 0;
+  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
+    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+  if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true)))
+    return rc;
   batch_note(bp);
+  return JDS_OK;
+}
+
+// ------------------------------------------------- lossless transcode --
+// (DESIGN.md "Transcode"; kernels: jds_entropy_mcu.hip)
+
+// One file of a writer batch: its geometry record (the planes' offsets count
+// from the start of c->ent_cf) and its header prefix.
+struct McuJob {
+  McuFile f;
+  std::vector<uint8_t> pfx;
+};
+
+static int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j) {
+  if (mcu_file_of(info, &j->f))
+    return fail(JDS_EINVAL,
+                "%lldx%lld with block grids %lldx%lld, %lldx%lld, %lldx%lld is not a T.81 geometry of subsampling %d",
+                (long long)info->H, (long long)info->W, (long long)info->grid_rows[0], (long long)info->grid_cols[0],
+                (long long)info->grid_rows[1], (long long)info->grid_cols[1], (long long)info->grid_rows[2],
+                (long long)info->grid_cols[2], info->subsampling);
+  for (int cc = 0; cc < 3; ++cc) j->f.off[cc] += coef_off;
+  return JDS_OK;
+}
+
+static int mcu_job_splice(const uint8_t* data, int64_t len, McuJob* j) {
+  const int64_t n = mcu_splice(data, len, nullptr, 0);
+  if (n < 0 || n > 0x7fffffffll) return fail(JDS_EINVAL, "header splice: no marker sequence from SOI to an SOS");
+  j->pfx.resize((size_t)n);
+  if (mcu_splice(data, len, j->pfx.data(), n) != n) return fail(JDS_EINVAL, "header splice: length mismatch");
+  return JDS_OK;
+}
+
+static int mcu_job_prefix(const jds_jpeg_info* info, const uint8_t* prefix, int64_t prefix_len, McuJob* j) {
+  if (prefix) {
+    if (prefix_len < 0 || prefix_len > 0x7fffffffll) return fail(JDS_EINVAL, "prefix_len %lld", (long long)prefix_len);
+    j->pfx.assign(prefix, prefix + prefix_len);
+    return JDS_OK;
+  }
+  j->pfx.resize(MCU_PFX_DEFAULT_MAX);
+  const int n = mcu_default_prefix(info, j->pfx.data());
+  if (n == -1000) return fail(JDS_EINVAL, "quantisation table id outside 0..3");
+  if (n < 0) {
+    const int cc = (-n - 1) / 64, i = (-n - 1) % 64;
+    return fail(JDS_EINVAL, "qtable[%d][%d] = %g is not an integer in [1, 255]", cc, i, info->qtable[cc][i]);
+  }
+  j->pfx.resize((size_t)n);
+  return JDS_OK;
+}
+
+static const char* const MCU_NOT_CODABLE =
+    "not baseline-codable: a DC difference category above 11 or an AC category above 10";
+
+// The Annex K table object on this thread's host side (and, with a context, on its device).
+static int mcu_tables(jds_ctx* c, const char** host) {
+  alignas(16) static thread_local char t[16384];
+  static thread_local bool built = false;
+  if (ent_tab_size() > sizeof t) return fail(JDS_EINVAL, "entropy tables exceed the staging buffer");
+  if (!built) {
+    ent_build_tables((EntTab*)t);
+    built = true;
+  }
+  if (c && !c->ent_tab.p) {
+    HIP_TRY(c->ent_tab.ensure(ent_tab_size()));
+    HIP_TRY(hipMemcpy(c->ent_tab.p, t, ent_tab_size(), hipMemcpyHostToDevice));
+  }
+  *host = t;
+  return JDS_OK;
+}
+
+static void mcu_std_tabs(McuStdTabs* t) {
+  for (int i = 0; i < 4; ++i) t->n_vals[i] = ent_std_table(i, &t->bits[i], &t->vals[i]);
+}
+
+struct McuRun {
+  McuDev d;
+  int nf = 0, nseg = 0;
+  std::vector<int64_t> len;  // per job: the file's bytes, 0: not baseline-codable
+};
+
+// The writer's launches up to the files' lengths, over the coefficients in
+// c->ent_cf; the lengths and flags come back (the call's one read between the
+// placement and the emit).
+static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun* r) {
+  hipStream_t s = c->stream;
+  const int nf = (int)jobs.size();
+  long long nseg = 0, raw_words = 0, pfx_bytes = 0;
+  bool any_long = false;
+  for (int k = 0; k < nf; ++k) {
+    McuFile& f = jobs[(size_t)k].f;
+    f.seg0 = (int32_t)nseg;
+    f.frame = optimize ? k : 0;
+    f.raw_w0 = raw_words;
+    f.raw_words = mcu_raw_words(f.nblk);
+    f.pfx_off = pfx_bytes;
+    f.pfx_len = (int32_t)jobs[(size_t)k].pfx.size();
+    nseg += f.nseg;
+    raw_words += f.raw_words;
+    pfx_bytes += f.pfx_len;
+    any_long = any_long || f.nseg > mcu_self_max();
+    if (nseg > 0x1fffffffll || raw_words > 0x7fffffffll * 16)
+      return fail(JDS_ENOTSUP, "batch of %d files: too many blocks for one set of writer launches", nf);
+  }
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_seg = up(sizeof(McuFile) * (size_t)nf), o_pfx = up(o_seg + 4 * (size_t)nseg),
+               total = up(o_pfx + (size_t)pfx_bytes);
+  std::vector<char> h(total, 0);
+  for (int k = 0; k < nf; ++k) {
+    const McuJob& j = jobs[(size_t)k];
+    memcpy(h.data() + sizeof(McuFile) * (size_t)k, &j.f, sizeof(McuFile));
+    int32_t* sf = (int32_t*)(h.data() + o_seg) + j.f.seg0;
+    for (int i = 0; i < j.f.nseg; ++i) sf[i] = k;
+    if (!j.pfx.empty()) memcpy(h.data() + o_pfx + j.f.pfx_off, j.pfx.data(), j.pfx.size());
+  }
+  const char* tab_host;
+  int rc = mcu_tables(c, &tab_host);
+  if (rc) return rc;
+  HIP_TRY(c->mcu_up.ensure(total));
+  HIP_TRY(c->mcu_scr.ensure(mcu_scratch_bytes(nf, nseg, raw_words)));
+  McuDev& d = r->d;
+  (void)mcu_carve(c->mcu_scr.p, nf, nseg, raw_words, &d);
+  d.files = (const McuFile*)c->mcu_up.p;
+  d.segfile = (const int32_t*)((const char*)c->mcu_up.p + o_seg);
+  d.pfx = (const uint8_t*)c->mcu_up.p + o_pfx;
+  // a header template: the DHT segments a table class falls back to (its other bytes are not used)
+  uint8_t hdr[ENT_HDR];
+  double ones[64];
+  for (double& v : ones) v = 1.0;
+  if (ent_header(ones, M444, 8, 8, hdr) != ENT_HDR) return fail(JDS_EINVAL, "header template");
+  std::vector<char> frame(mcu_optframe_bytes());
+  mcu_std_frame(ent_es_tab(tab_host), hdr, frame.data());
+  HIP_TRY(hipMemcpyAsync(c->mcu_up.p, h.data(), total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d.hdr_std, hdr, ENT_HDR, hipMemcpyHostToDevice, s));
+  if (!optimize) HIP_TRY(hipMemcpyAsync(d.of, frame.data(), frame.size(), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_mcu_code(d, nf, (int)nseg, any_long, (const int16_t*)c->ent_cf.p, optimize != 0,
+                          ent_es_tab(c->ent_tab.p), s));
+  std::vector<unsigned long long> fl((size_t)nf);
+  std::vector<uint32_t> fb((size_t)nf);
+  HIP_TRY(hipMemcpyAsync(fl.data(), d.flen, 8 * (size_t)nf, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(fb.data(), d.fbad, 4 * (size_t)nf, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (h, hdr and frame are this call's objects)
+  r->nf = nf;
+  r->nseg = (int)nseg;
+  r->len.assign((size_t)nf, 0);
+  for (int k = 0; k < nf; ++k) {
+    if ((long long)fl[(size_t)k] > mcu_capacity(jobs[(size_t)k].f) || fl[(size_t)k] < 4)
+      return fail(JDS_EHIP, "writer: file %d reports %llu bytes, outside its bound", k, fl[(size_t)k]);
+    r->len[(size_t)k] = fb[(size_t)k] ? 0 : (int64_t)fl[(size_t)k];
+  }
+  return JDS_OK;
+}
+
+// The files at fout (per job; < 0: not written) into out_dev; asynchronous on the context's stream.
+static int mcu_emit(jds_ctx* c, const McuRun& r, const std::vector<long long>& fout, uint8_t* out_dev) {
+  HIP_TRY(hipMemcpyAsync(r.d.fout, fout.data(), 8 * (size_t)r.nf, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_mcu_emit(r.d, r.nf, r.nseg, out_dev, c->stream));
+  return JDS_OK;
+}
+
+// One job whose coefficients are in c->ent_cf, to host memory.
+static int mcu_single(jds_ctx* c, McuJob& job, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  std::vector<McuJob> jobs(1);
+  jobs[0] = std::move(job);
+  McuRun r;
+  const CtxMarkScope marks_(c, c->stream);
+  int rc = mcu_code(c, jobs, optimize, &r);
+  if (rc) return rc;
+  if (r.len[0] == 0) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+  *out_len = r.len[0];
+  if (r.len[0] > out_cap || !out)
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)r.len[0]);
+  HIP_TRY(c->ent_out.ensure((size_t)r.len[0]));
+  const std::vector<long long> fout(1, 0ll);
+  if ((rc = mcu_emit(c, r, fout, (uint8_t*)c->ent_out.p))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->ent_out.p, (size_t)r.len[0], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return JDS_OK;
+}
+
+int jds_encode_jpeg(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize,
+                    const uint8_t* prefix, int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  if (!c || !info || !coeffs || !out_len) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_prefix(info, prefix, prefix_len, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nbytes = (size_t)mcu_coeffs(job.f) * sizeof(int16_t);
+  HIP_TRY(c->ent_cf.ensure(nbytes));
+  HIP_TRY(hipMemcpyAsync(c->ent_cf.p, coeffs, nbytes, hipMemcpyHostToDevice, c->stream));
+  return mcu_single(c, job, optimize, out, out_cap, out_len);
+}
+
+int jds_jpeg_transcode(jds_ctx* c, const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                       int64_t* out_len, jds_jpeg_info* info) {
+  if (!c || !data || !info || !out_len) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_splice(data, len, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  return mcu_single(c, job, optimize, out, out_cap, out_len);
+}
+
+int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                             jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  if (!c || !out_bytes || (n > 0 && !items)) return fail(JDS_EINVAL, "null argument");
+  *out_bytes = 0;
+  std::vector<jds_jpeg_batch_item> bi((size_t)(n > 0 ? n : 0));
+  BatchPlan bp;
+  int rc = batch_layout(data, lens, n, bi.data(), bp);
+  if (rc) return rc;
+  if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, nullptr, 0, nullptr, bi.data(), nullptr, false)))
+    return rc;
+  for (int i = 0; i < n; ++i) {
+    jds_jpeg_transcode_item& it = items[i];
+    memset(&it, 0, sizeof it);
+    it.rc = bi[(size_t)i].rc;
+    it.status = bi[(size_t)i].status;
+    it.H = bi[(size_t)i].H;
+    it.W = bi[(size_t)i].W;
+    it.subsampling = bi[(size_t)i].subsampling;
+    it.interleaved = bi[(size_t)i].interleaved;
+    it.out_off = -1;
+  }
+  // the files that decoded take part in the writer's launches
+  std::vector<McuJob> jobs;
+  std::vector<int> job_file;
+  for (size_t k = 0; k < bp.recs.size(); ++k) {
+    const int i = bp.file_of[k];
+    if (items[i].status) continue;
+    McuJob j;
+    if ((rc = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, &j))) return rc;
+    if ((rc = mcu_job_splice(data[i], lens[i], &j))) return rc;
+    jobs.push_back(std::move(j));
+    job_file.push_back(i);
+  }
+  if (jobs.empty()) {
+    batch_note(bp);
+    return JDS_OK;
+  }
+  hipStream_t s = c->stream;
+  const CtxMarkScope marks_(c, s);
+  McuRun r;
+  if ((rc = mcu_code(c, jobs, optimize, &r))) return rc;
+  std::vector<long long> fout(jobs.size(), -1ll);
+  int64_t cur = 0;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const int i = job_file[k];
+    if (r.len[k] == 0) {
+      items[i].rc = fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+      if (bp.first_bad < 0 || i < bp.first_bad) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", MCU_NOT_CODABLE);
+      }
+      continue;
+    }
+    fout[k] = cur;
+    items[i].out_off = cur;
+    items[i].out_len = r.len[k];
+    cur = (cur + r.len[k] + 255) & ~(int64_t)255;
+  }
+  *out_bytes = cur;
+  if (cur > 0 && (!out || out_cap < cur))
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)cur);
+  if (cur > 0) {
+    uint8_t* dst = out;
+    if (!out_on_device) {
+      HIP_TRY(c->ent_out.ensure((size_t)cur));
+      dst = (uint8_t*)c->ent_out.p;
+    }
+    if ((rc = mcu_emit(c, r, fout, dst))) return rc;
+    if (!out_on_device)  // file by file: the gaps of the caller's buffer stay as they are
+      for (size_t k = 0; k < jobs.size(); ++k)
+        if (fout[k] >= 0)
+          HIP_TRY(hipMemcpyAsync(out + fout[k], dst + fout[k], (size_t)r.len[k], hipMemcpyDeviceToHost, s));
+    kmark(s, "(transcode download)");
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  batch_note(bp);
+  return JDS_OK;
+}
+
+// the host model's result into the caller's buffer
+static int mcu_host_result(int wrc, const std::vector<uint8_t>& file, uint8_t* out, int64_t out_cap,
+                           int64_t* out_len) {
+  if (wrc) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+  *out_len = (int64_t)file.size();
+  if (!out || out_cap < (int64_t)file.size())
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)file.size());
+  memcpy(out, file.data(), file.size());
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_transcode(const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                                int64_t* out_len) {
+  if (!data || !out_len) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(&info, 0, &job))) return rc;
+  if ((rc = mcu_job_splice(data, len, &job))) return rc;
+  int lane_max, sb, spg;
+  rst_constants(&lane_max);
+  dec_constants(&sb, &spg);
+  std::vector<int16_t> cf((size_t)info.coeffs_needed);
+  int32_t rounds[3];
+  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, cf.data(), optimize, job.pfx.data(), (int64_t)job.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_encode(const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize, const uint8_t* prefix,
+                             int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  if (!info || !coeffs || !out_len) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_prefix(info, prefix, prefix_len, &job))) return rc;
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, coeffs, optimize, job.pfx.data(), (int64_t)job.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_hist_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint32_t* counts) {
+  if (!c || !info || !coeffs || !counts) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nbytes = (size_t)mcu_coeffs(job.f) * sizeof(int16_t);
+  HIP_TRY(c->ent_cf.ensure(nbytes));
+  HIP_TRY(hipMemcpyAsync(c->ent_cf.p, coeffs, nbytes, hipMemcpyHostToDevice, c->stream));
+  std::vector<McuJob> jobs(1);
+  jobs[0] = std::move(job);
+  McuRun r;
+  if ((rc = mcu_code(c, jobs, 1, &r))) return rc;
+  // (the counters open the file's frame)
+  HIP_TRY(hipMemcpy(counts, r.d.of, sizeof(uint32_t) * 2 * OPT_BINS, hipMemcpyDeviceToHost));
   return JDS_OK;
 }
 

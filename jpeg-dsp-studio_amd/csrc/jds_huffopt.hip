@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "jds_entropy_common.hpp"
+#include "jds_entropy_core.hpp"
 #include "jds_huffopt.hpp"
 #include "jds_internal.hpp"
 
@@ -27,34 +28,12 @@ namespace jds {
 // ---------------------------------------------------------- histogram --
 
 constexpr int EH_WAVES = 4;
-constexpr int EH_ZRL = 16 + 0xF0, EH_EOB = 16 + 0x00;
 // Copies of a wave's bins, lane l counting into copy l % EH_COPIES (bin i's
 // copies side by side, on neighbouring banks): the lanes of a wave mostly count
 // the same few symbols, and LDS atomics on one address take their turns
 // (1 copy: 0.187, 8 copies: 0.143 ms per 64 x 1080p Q50).
 constexpr int EH_COPIES = 8;
 static_assert(EH_COPIES >= 1 && (EH_COPIES & (EH_COPIES - 1)) == 0 && EH_COPIES <= 64, "a power of two");
-
-// zigzag positions K..63 of the lane's block: one count per non-zero
-// coefficient ((run & 15) << 4 | size, size clamped like the coder's), one ZRL
-// count per 16 zeros before it
-template <int K>
-__device__ __forceinline__ void eh_ac(const BlockRegs& r, int last, int& aor, uint32_t* bins, int& lastK) {
-  if constexpr (K < 64) {
-    const int v = coef_at<ZZC[K]>(r);
-    const int a = v < 0 ? -v : v;
-    if (a) {
-      const int run = K - 1 - last;
-      if (run >= 16) atomicAdd(&bins[EH_ZRL * EH_COPIES], (uint32_t)(run >> 4));
-      atomicAdd(&bins[(16 + (((run & 15) << 4) | es_size(a))) * EH_COPIES], 1u);
-      aor |= a;
-      last = K;
-    }
-    eh_ac<K + 1>(r, last, aor, bins, lastK);
-  } else {
-    lastK = last;
-  }
-}
 
 // RST: every segment is a restart interval (its first block predicts from 0).
 // A block baseline JPEG cannot code (DC category > 11, AC category > 10) counts
@@ -86,7 +65,7 @@ __global__ void __launch_bounds__(64 * EH_WAVES) k_ent_hist(const EntGeo e, cons
       ds = ds > 11 ? 11 : ds;
       atomicAdd(&bins[ds * EH_COPIES], 1u);
       int aor = 0, last = 0;
-      eh_ac<1>(rg, 0, aor, bins, last);
+      eh_ac<1, EH_COPIES>(rg, 0, aor, bins, last);
       if (last < 63) atomicAdd(&bins[EH_EOB * EH_COPIES], 1u);
     }
   }

@@ -105,6 +105,12 @@ class JpegBatchItem(C.Structure):
                 ('coef_off', C.c_int64), ('coeffs_needed', C.c_int64)]
 
 
+class JpegTranscodeItem(C.Structure):
+    _fields_ = [('rc', C.c_int32), ('status', C.c_uint32), ('H', C.c_int64), ('W', C.c_int64),
+                ('subsampling', C.c_int32), ('interleaved', C.c_int32), ('out_off', C.c_int64),
+                ('out_len', C.c_int64)]
+
+
 # frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
 DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE, DEC_RESTART = 1, 2, 4, 8, 16, 32, 64
 
@@ -190,6 +196,16 @@ _SIGS = {
     'jds_jpeg_batch_to_rgb': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegBatchItem),
                                         C.POINTER(C.c_uint32)]),
     'jds_selftest_jpeg_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.POINTER(JpegBatchItem)]),
+    'jds_encode_jpeg': (C.c_int, [_P, C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
+                                  C.POINTER(C.c_int64)]),
+    'jds_jpeg_transcode': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),
+                                     C.POINTER(JpegInfo)]),
+    'jds_jpeg_batch_transcode': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32,
+                                           C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
+    'jds_selftest_jpeg_transcode': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    'jds_selftest_jpeg_encode': (C.c_int, [C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
+                                           C.POINTER(C.c_int64)]),
+    'jds_selftest_jpeg_hist_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P]),
     'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),

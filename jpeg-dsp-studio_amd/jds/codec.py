@@ -334,6 +334,103 @@ def host_jpeg_batch(files, subseq_bits: int = 1024):
     return rgb[:int(rb.value)], cf[:int(ce.value)], [_batch_item_dict(items[i]) for i in range(n)]
 
 
+def jpeg_transcode(data, optimize: bool = True, device: int = 0, with_info: bool = False):
+    """jds_jpeg_transcode: any baseline JPEG parse_jpeg accepts -> the same coefficients as one
+    interleaved scan behind the file's own header segments (APPn, COM, DQT, SOF0 verbatim), with
+    the file's own optimised Huffman tables (optimize=True: what `jpegtran -optimize` writes) or
+    the Annex K ones.  Decode and write run on the device; no pixel and no coefficient changes
+    (DESIGN.md "Transcode").  ValueError for a file the parser rejects, defective scan data, or a
+    block baseline JPEG cannot code ("not baseline-codable").  with_info: (bytes, parse_jpeg's
+    dict of the input plus 'rounds')."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.JpegInfo()
+    with lease(device) as ctx:
+        out = entropy._grown(lambda o, cap, m: lib().jds_jpeg_transcode(
+            ctx.handle, p, n, int(bool(optimize)), o.ctypes.data, cap, C.byref(m), C.byref(info)),
+            n + n // 4 + 4096)
+    if not with_info:
+        return out
+    d = entropy._jpeg_dict(info)
+    d['rounds'] = int(info.rounds)
+    return out, d
+
+
+def _transcode_item_dict(it) -> dict:
+    from . import entropy
+    return {'rc': int(it.rc), 'status': int(it.status), 'H': int(it.H), 'W': int(it.W),
+            'mode': entropy._MODE_NAMES.get(int(it.subsampling)) if it.H > 0 else None,
+            'interleaved': bool(it.interleaved), 'out_off': int(it.out_off), 'out_len': int(it.out_len)}
+
+
+def jpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = 'raise', device: int = 0, ctx=None):
+    """jds_jpeg_batch_transcode: a sequence of baseline JPEGs (any mix of sizes, modes, tables,
+    restart intervals and scan forms) -> each one's jpeg_transcode output, by the batch decode's
+    launches and one set of writer launches.  out=None: a list of bytes; out='device': torch.uint8
+    tensors, views into one allocation on `device` (file i at a multiple of 256); out a 1-D uint8
+    device tensor: views into that (ValueError naming the need when it is too small).  A file that
+    does not parse, whose scan data are defective or that is not baseline-codable does not stop the
+    others and no other file's bytes depend on it: errors='raise' raises ValueError naming the
+    first such index after the batch has run; errors='items' returns (outputs with None in its
+    place, per-file dicts: 'rc', 'status', 'out_off', 'out_len', ...).  ctx: a caller-owned Context
+    (e.g. a profiled one) instead of a pooled one."""
+    if errors not in ('raise', 'items'):
+        raise ValueError("errors must be 'raise' or 'items'")
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    items = (_abi.JpegTranscodeItem * max(n, 1))()
+    need = C.c_int64(0)
+    own = out is None or isinstance(out, str)
+    if isinstance(out, str) and out != 'device':
+        raise ValueError("out must be None, 'device' or a 1-D uint8 device tensor")
+    if not own and (out.dim() != 1 or out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError('out must be a contiguous 1-D uint8 device tensor')
+    # a first guess from the inputs' sizes; the call reports the exact need when it is short
+    cap = sum(-(-(int(k[0].size) * 5 // 4 + 4096) // 256) * 256 for k in keep) if own else int(out.numel())
+
+    def run(c, buf, cap):
+        dst, on_dev = (buf.ctypes.data, 0) if out is None else (int(buf.data_ptr()), 1)
+        return lib().jds_jpeg_batch_transcode(c.handle, ptrs, lens, n, int(bool(optimize)), C.c_void_p(dst), cap,
+                                              on_dev, items, C.byref(need))
+
+    def alloc(cap):
+        if out is None:
+            return np.empty(max(cap, 1), np.uint8)
+        if isinstance(out, str):
+            import torch
+            return torch.empty(max(cap, 1), dtype=torch.uint8, device=f'cuda:{device}')
+        return out
+
+    def attempt(c):
+        nonlocal cap
+        buf = alloc(cap)
+        rc = run(c, buf, cap)
+        if rc == _abi.JDS_EINVAL and own and need.value > cap:
+            cap = int(need.value)
+            buf = alloc(cap)
+            rc = run(c, buf, cap)
+        check(rc)
+        return buf
+
+    if ctx is not None:
+        buf = attempt(ctx)
+    else:
+        with lease(device) as c:
+            buf = attempt(c)
+    info = [_transcode_item_dict(items[i]) for i in range(n)]
+    first = _batch_first_error(info)
+    if first and errors == 'raise':
+        raise ValueError(first)
+    outs = []
+    for it in info:
+        if it['rc'] != 0 or it['status'] != 0:
+            outs.append(None)
+            continue
+        v = buf[it['out_off']:it['out_off'] + it['out_len']]
+        outs.append(v.tobytes() if out is None else v)
+    return outs if errors == 'raise' else (outs, info)
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

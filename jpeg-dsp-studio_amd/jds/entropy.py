@@ -215,6 +215,91 @@ def host_decode_jpeg(data, subseq_bits: int = 1024):
     return cf, [int(r) for r in rounds][:int(info.n_scans)]
 
 
+def _grown(call, cap: int) -> bytes:
+    """call(out array, cap, length) -> rc, repeated once with the size the C side reports."""
+    n = C.c_int64(0)
+    while True:
+        out = np.empty(max(cap, 1), np.uint8)
+        rc = call(out, cap, n)
+        if rc == _abi.JDS_EINVAL and n.value > cap:
+            cap = int(n.value)
+            continue
+        check(rc)
+        return out[:n.value].tobytes()
+
+
+def _encode_info(info: dict) -> _abi.JpegInfo:
+    """The fields jds_encode_jpeg reads, from parse_jpeg's / decode_jpeg's terms."""
+    st = _abi.JpegInfo()
+    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.MODE_CODES[info['mode']]
+    q = np.ascontiguousarray(info['qtables'], np.float64).reshape(3, 64)
+    tq = info.get('tq', (0, 1, 1) if not info.get('single_table') else (0, 0, 0))
+    for c, (gr, gc) in enumerate(info['grids']):
+        st.grid_rows[c], st.grid_cols[c], st.tq[c] = int(gr), int(gc), int(tq[c])
+        for i in range(64):
+            st.qtable[c][i] = q[c, i]
+    st.coeffs_needed = 64 * sum(int(gr) * int(gc) for gr, gc in info['grids'])
+    return st
+
+
+def _encode_args(coeffs, info: dict, prefix):
+    st = _encode_info(info)
+    cf = np.ascontiguousarray(coeffs, dtype=np.int16).reshape(-1)
+    if cf.size != int(st.coeffs_needed):
+        raise ValueError(f'expected {int(st.coeffs_needed)} coefficients for these block grids, got {cf.size}')
+    if prefix is None:
+        return st, cf, (None, None, 0)
+    a = np.frombuffer(bytes(prefix), np.uint8)
+    keep = a if a.size else np.zeros(1, np.uint8)   # (an empty prefix is still "a prefix": a non-null pointer)
+    return st, cf, (keep, keep.ctypes.data, int(a.size))
+
+
+def encode_jpeg(coeffs: np.ndarray, info: dict, optimize: bool = False, prefix=None, device: int = 0) -> bytes:
+    """jds_encode_jpeg: coefficients in decode_jpeg's layout (Y, Cb, Cr planar on their T.81 grids)
+    -> a baseline JPEG with ONE interleaved scan (DESIGN.md "Transcode").  info: 'H', 'W', 'mode',
+    'grids', 'qtables' and 'tq' as parse_jpeg / decode_jpeg give them.  prefix: the header bytes to
+    place after SOI (DQT and SOF0 among them); None: APP0, the DQTs of qtables / tq, SOF0.
+    optimize: the scan's own Huffman tables instead of the Annex K ones.  ValueError for a wrong
+    coefficient count, grids other than T.81's, or a block baseline JPEG cannot code."""
+    st, cf, pf = _encode_args(coeffs, info, prefix)
+    with _abi.lease(device) as ctx:
+        return _grown(lambda out, cap, n: lib().jds_encode_jpeg(
+            ctx.handle, C.byref(st), cf.ctypes.data, int(bool(optimize)), pf[1], pf[2], out.ctypes.data, cap,
+            C.byref(n)), max(1 << 16, 4 * cf.size))
+
+
+def host_encode_jpeg(coeffs: np.ndarray, info: dict, optimize: bool = False, prefix=None) -> bytes:
+    """Test aid (jds_selftest_jpeg_encode): encode_jpeg's host model.  No GPU."""
+    st, cf, pf = _encode_args(coeffs, info, prefix)
+    return _grown(lambda out, cap, n: lib().jds_selftest_jpeg_encode(
+        C.byref(st), cf.ctypes.data, int(bool(optimize)), pf[1], pf[2], out.ctypes.data, cap, C.byref(n)),
+        max(1 << 16, 4 * cf.size))
+
+
+def host_transcode_jpeg(data, optimize: bool = True) -> bytes:
+    """Test aid (jds_selftest_jpeg_transcode): codec.jpeg_transcode's host model -- the host decode
+    model, then the writer through the kernels' shared lookup, predecessor rule, splicer and
+    table builder.  No GPU."""
+    a, p, n = _bytes_arg(data)
+    return _grown(lambda out, cap, m: lib().jds_selftest_jpeg_transcode(p, n, int(bool(optimize)), out.ctypes.data, cap,
+                                                                        C.byref(m)), max(1 << 16, 2 * n))
+
+
+def transcode_histogram_dev(coeffs: np.ndarray, info: dict, device: int = 0) -> dict:
+    """Test aid (jds_selftest_jpeg_hist_dev): the interleaved scan's symbol counts by k_mcu_hist
+    -> {'dc0', 'ac0', 'dc1', 'ac1'}: counts[256]."""
+    st, cf, _ = _encode_args(coeffs, info, None)
+    cnt = np.zeros((2, 16 + 256), np.uint32)
+    with _abi.lease(device) as ctx:
+        check(lib().jds_selftest_jpeg_hist_dev(ctx.handle, C.byref(st), cf.ctypes.data, cnt.ctypes.data))
+    out = {}
+    for c in range(2):
+        dc = np.zeros(256, np.int64)
+        dc[:16] = cnt[c, :16]
+        out[f'dc{c}'], out[f'ac{c}'] = dc, cnt[c, 16:].astype(np.int64)
+    return out
+
+
 def bitrate_from_jfif(nbytes: int, shape) -> dict:
     """bpp / compression ratio of a real file, in estimate_bitrate_no_entropy's
     terms (utils/metrics.py:62-92: 24-bit originals)."""

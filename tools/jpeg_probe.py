@@ -18,7 +18,14 @@ through jpeg_batch_to_rgb(out='device') against N sequential jpeg_to_rgb(out=ten
 the same process (median of 10 after 2 warm-ups each), the rounds of the batch and the
 per-kernel times from the context's launch marks; then a mixed leg: the same N split over Q50 /
 Q95 / optimize=True / restart_marker_rows=1 and the three subsampling modes, at two sizes.
-Writes profiles/jpeg_batch_probe.json (or --out FILE)."""
+Writes profiles/jpeg_batch_probe.json (or --out FILE).
+--transcode N (default 64) instead: the same two sets of files through jpeg_batch_transcode with
+optimize False and True (to a device buffer and to host memory) against N sequential
+jpeg_transcode calls in the same process, every batch output compared with its single call; the
+per-kernel times of the batch from the context's launch marks, split into the decode's and the
+writer's (k_mcu_*, k_ent_opt_tables); input and output bytes; and beside them, in the same run,
+jpeg_batch_to_rgb(out=tensor) on the same files (the batch decode with its inverse).  Writes
+profiles/transcode_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -205,9 +212,74 @@ def batch_main():
     return 0 if all(r['batch_equals_sequence'] for r in rows) else 1
 
 
+def transcode_leg(name, files):
+    """One set of files: the batch call against the sequence of single calls, both table kinds."""
+    import torch
+    from jds import _abi
+    n = len(files)
+    ctx = _abi.Context(0)
+    row = {'leg': name, 'n': n, 'input_bytes': int(sum(len(f) for f in files))}
+    items, rgb_bytes, _ = codec.jpeg_batch_layout(files)
+    rgb = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    row['batch_to_rgb'] = timed(lambda: codec.jpeg_batch_to_rgb(files, out=rgb, ctx=ctx))
+    for opt in (False, True):
+        outs = codec.jpeg_batch_transcode(files, optimize=opt, ctx=ctx)
+        singles = [codec.jpeg_transcode(f, optimize=opt) for f in files]
+        buf = torch.empty(sum(-(-len(o) // 256) * 256 for o in outs), dtype=torch.uint8, device='cuda')
+        views = codec.jpeg_batch_transcode(files, optimize=opt, out=buf, ctx=ctx)
+        equal = outs == singles and all(v.cpu().numpy().tobytes() == o for v, o in zip(views, outs))
+        tb = timed(lambda: codec.jpeg_batch_transcode(files, optimize=opt, out=buf, ctx=ctx))
+        th = timed(lambda: codec.jpeg_batch_transcode(files, optimize=opt, ctx=ctx))
+        ts = timed(lambda: [codec.jpeg_transcode(f, optimize=opt) for f in files], reps=5, warm=1)
+        ctx.profile(True)
+        reps = 5
+        for _ in range(reps):
+            codec.jpeg_batch_transcode(files, optimize=opt, out=buf, ctx=ctx)
+        kern, span = ctx.profile_read()
+        ctx.profile(False)
+        writer = {k: v[0] / reps for k, v in kern.items() if k.startswith('k_mcu') or k.startswith('k_ent_opt')}
+        decode = {k: v[0] / reps for k, v in kern.items() if k not in writer and not k.startswith('(')}
+        row['optimize' if opt else 'annex_k'] = {
+            'output_bytes': int(sum(len(o) for o in outs)), 'batch_equals_singles': bool(equal),
+            'batch_to_device': tb, 'batch_to_host': th, 'single_calls': ts,
+            'single_over_batch': ts['median_ms'] / tb['median_ms'],
+            'batch_minus_batch_to_rgb_ms': tb['median_ms'] - row['batch_to_rgb']['median_ms'],
+            'writer_kernels_ms_per_batch': writer, 'writer_kernels_ms_total': sum(writer.values()),
+            'decode_kernels_ms_per_batch': decode, 'decode_kernels_ms_total': sum(decode.values()),
+            'other_marks_ms_per_batch': {k: v[0] / reps for k, v in kern.items() if k.startswith('(')},
+            'marks_span_ms_per_batch': span / reps}
+    ctx.close()
+    return row
+
+
+def transcode_main():
+    i = sys.argv.index('--transcode')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    plain = [pillow_file(np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8)) for k in range(n)]
+    rows = [transcode_leg('pillow_q50_420_1080p', plain)]
+    print(json.dumps(rows[-1]), flush=True)
+    kinds = [{'quality': 50}, {'quality': 95}, {'quality': 50, 'optimize': True}, {'quality': 50, 'restart_marker_rows': 1}]
+    sizes = [(H, W), (2 * H // 3, 2 * W // 3)]
+    mixed = []
+    for k in range(n):
+        h, w = sizes[(k // 12) % 2]
+        img = np.random.default_rng(500 + k).integers(0, 256, (h, w, 3), dtype=np.uint8)
+        mixed.append(pillow_file(img, subsampling=(2, 0, 1)[k % 3], **kinds[(k // 3) % 4]))
+    rows.append(transcode_leg('pillow_mixed', mixed))
+    print(json.dumps(rows[-1]), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'transcode_probe.json')
+    with open(out, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r[k]['batch_equals_singles'] for r in rows for k in ('annex_k', 'optimize')) else 1
+
+
 def main():
     if '--batch' in sys.argv:
         return batch_main()
+    if '--transcode' in sys.argv:
+        return transcode_main()
     H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
     reps = 1 if '--once' in sys.argv else int(os.environ.get('REPS', '30'))
     want_rgb = '--rgb' in sys.argv
