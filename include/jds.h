@@ -698,6 +698,77 @@ int jds_selftest_jpeg_encode(const jds_jpeg_info* info, const int16_t* coeffs, i
  * (16 DC categories, 256 AC symbols). */
 int jds_selftest_jpeg_hist_dev(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, uint32_t* counts);
 
+/* Lossless transforms (DESIGN.md "Lossless transforms"; byte-for-byte
+ * definition: tests/transform_ref.py): the transcode above with the decoded
+ * coefficient planes rewritten into a mirrored, transposed or rotated
+ * geometry between the decode and the writer (k_coef_xform,
+ * csrc/jds_xform.hip) -- what `jpegtran -flip / -transpose / -rotate` does.
+ * No coefficient changes except in sign, so the ideal IDCT of the output is
+ * exactly the transformed image.  Per component, with block grid B[r][c]
+ * (R x C) and row-major coefficients k[v][u] (v vertical frequency):
+ *   hflip      B'[r][C-1-c] = B[r][c],  k'[v][u] = (-1)^u k[v][u]
+ *   vflip      B'[R-1-r][c] = B[r][c],  k'[v][u] = (-1)^v k[v][u]
+ *   transpose  B'[c][r]     = B[r][c],  k'[u][v] = k[v][u]
+ *   rot90 = transpose, then hflip (clockwise, `jpegtran -rotate 90`);
+ *   rot270 = hflip, then transpose; rot180 = hflip and vflip;
+ *   transverse = transpose, then rot180.
+ * Geometry: a mirrored source axis must be whole MCUs (hflip, rot180,
+ *   transverse, rot270: W % (8 hs) == 0; vflip, rot180, transverse, rot90:
+ *   H % (8 vs) == 0).  Otherwise JDS_ENOTSUP naming the axis (`jpegtran
+ *   -perfect`), or with JDS_XF_TRIM or-ed into the operation the source is
+ *   first cropped on that axis to whole MCUs (`jpegtran -trim`; JDS_EINVAL when
+ *   nothing is left).  Transposition alone has no size constraint.  4:2:2
+ *   takes only hflip, vflip and rot180 (a transposed file would be 4:4:0):
+ *   JDS_ENOTSUP.  JDS_XF_NONE gives the bytes of jds_jpeg_transcode.
+ * Header: the prefix of the transcode with, for transposing operations, every
+ *   8-bit table of every DQT segment transposed and SOF0's Y and X swapped;
+ *   SOF0 gets the cropped size under trim.  Everything else verbatim.
+ * JDS_XF_AUTO: the operation the EXIF Orientation tag asks for (IFD0 tag
+ *   0x0112 of the first APP1 "Exif" segment; 1 none, 2 hflip, 3 rot180,
+ *   4 vflip, 5 transpose, 6 rot90, 7 transverse, 8 rot270), and the tag is set
+ *   to 1 in the output.  No or malformed EXIF, no tag or a value outside 1..8:
+ *   the plain transcode, not an error.  No other EXIF field is touched (pixel
+ *   dimension tags, the thumbnail).  Explicit operations never touch EXIF.
+ *
+ * jds_jpeg_transform_info: host only: parse, resolve JDS_XF_AUTO and trim;
+ *   *op_out = the operation 0..7, *H_out x *W_out = the output's size; the
+ *   geometry errors above.
+ * jds_jpeg_transform / jds_jpeg_batch_transform: jds_jpeg_transcode /
+ *   jds_jpeg_batch_transcode in every respect (items, packing at multiples of
+ *   256, one read of the lengths, the out_cap contract), with an operation per
+ *   file (ops == NULL: JDS_XF_AUTO for all).  An item's H and W are the
+ *   OUTPUT's size; a file whose operation is refused is an item error with the
+ *   code it would get alone.  info (single call): the input's, as
+ *   jds_jpeg_transcode fills it.
+ * jds_selftest_jpeg_transform: test-only, host only: the host decode model,
+ *   the host coefficient transform and prefix editor (csrc/jds_xform.hpp), the
+ *   writer's host model.
+ * jds_selftest_coef_transform_dev: test-only: k_coef_xform alone on host
+ *   coefficients in jds_decode_jpeg's layout of `info` (H, W, subsampling,
+ *   grids); op: an explicit operation, JDS_XF_TRIM allowed; coeffs_out: the
+ *   destination layout (jds_jpeg_transform_info's size, its T.81 grids). */
+#define JDS_XF_NONE 0
+#define JDS_XF_HFLIP 1
+#define JDS_XF_VFLIP 2
+#define JDS_XF_TRANSPOSE 3
+#define JDS_XF_TRANSVERSE 4
+#define JDS_XF_ROT90 5
+#define JDS_XF_ROT180 6
+#define JDS_XF_ROT270 7
+#define JDS_XF_AUTO 8
+#define JDS_XF_TRIM 0x100
+int jds_jpeg_transform_info(const uint8_t* data, int64_t len, int32_t op, int32_t* op_out, int64_t* H_out,
+                            int64_t* W_out);
+int jds_jpeg_transform(jds_ctx* ctx, const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                       int64_t out_cap, int64_t* out_len, jds_jpeg_info* info);
+int jds_jpeg_batch_transform(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             const int32_t* ops, int32_t optimize, uint8_t* out, int64_t out_cap,
+                             int32_t out_on_device, jds_jpeg_transcode_item* items, int64_t* out_bytes);
+int jds_selftest_jpeg_transform(const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                                int64_t out_cap, int64_t* out_len);
+int jds_selftest_coef_transform_dev(jds_ctx* ctx, const jds_jpeg_info* info, int32_t op, const int16_t* coeffs,
+                                    int16_t* coeffs_out);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

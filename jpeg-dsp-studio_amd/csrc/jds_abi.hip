@@ -24,6 +24,7 @@
 #include "jds_huffopt.hpp"
 #include "jds_internal.hpp"
 #include "jds_jpeg_inv.hpp"
+#include "jds_xform_dev.hpp"
 
 #ifdef JDS_INV6
 #define JDS_INV6_LIST 1  // the transpose-free variant's tile list (A/B builds: tools/build_variant.py)
@@ -2601,6 +2602,18 @@ static void mcu_std_tabs(McuStdTabs* t) {
   for (int i = 0; i < 4; ++i) t->n_vals[i] = ent_std_table(i, &t->bits[i], &t->vals[i]);
 }
 
+// The transformed files of a writer batch (DESIGN.md "Lossless transforms"):
+// their records, tiles assigned, travel in the writer's upload and
+// k_coef_xform runs in front of the writer's first kernel.
+struct XfSet {
+  std::vector<XfFile> files;
+  int64_t tiles = 0;
+  void add(XfFile f) {
+    tiles += xf_set_tiles(&f, tiles);
+    files.push_back(f);
+  }
+};
+
 struct McuRun {
   McuDev d;
   int nf = 0, nseg = 0;
@@ -2610,7 +2623,7 @@ struct McuRun {
 // The writer's launches up to the files' lengths, over the coefficients in
 // c->ent_cf; the lengths and flags come back (the call's one read between the
 // placement and the emit).
-static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun* r) {
+static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun* r, const XfSet* xf = nullptr) {
   hipStream_t s = c->stream;
   const int nf = (int)jobs.size();
   long long nseg = 0, raw_words = 0, pfx_bytes = 0;
@@ -2631,9 +2644,19 @@ static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun*
       return fail(JDS_ENOTSUP, "batch of %d files: too many blocks for one set of writer launches", nf);
   }
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t nxf = xf ? xf->files.size() : 0, nxt = xf ? (size_t)xf->tiles : 0;
+  if (nxt > 0x7fffffffull) return fail(JDS_ENOTSUP, "batch of %d files: too many blocks for one transform launch", nf);
   const size_t o_seg = up(sizeof(McuFile) * (size_t)nf), o_pfx = up(o_seg + 4 * (size_t)nseg),
-               total = up(o_pfx + (size_t)pfx_bytes);
+               o_xf = up(o_pfx + (size_t)pfx_bytes), o_xt = nxf ? up(o_xf + sizeof(XfFile) * nxf) : o_xf,
+               total = nxf ? up(o_xt + 4 * nxt) : o_xf;
   std::vector<char> h(total, 0);
+  for (size_t k = 0; k < nxf; ++k) {
+    const XfFile& x = xf->files[k];
+    memcpy(h.data() + o_xf + sizeof(XfFile) * k, &x, sizeof(XfFile));
+    int32_t* tf = (int32_t*)(h.data() + o_xt) + x.tile0;
+    const int64_t nt = (k + 1 < nxf ? (int64_t)xf->files[k + 1].tile0 : xf->tiles) - x.tile0;
+    for (int64_t i = 0; i < nt; ++i) tf[i] = (int32_t)k;
+  }
   for (int k = 0; k < nf; ++k) {
     const McuJob& j = jobs[(size_t)k];
     memcpy(h.data() + sizeof(McuFile) * (size_t)k, &j.f, sizeof(McuFile));
@@ -2661,6 +2684,10 @@ static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun*
   HIP_TRY(hipMemcpyAsync(c->mcu_up.p, h.data(), total, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d.hdr_std, hdr, ENT_HDR, hipMemcpyHostToDevice, s));
   if (!optimize) HIP_TRY(hipMemcpyAsync(d.of, frame.data(), frame.size(), hipMemcpyHostToDevice, s));
+  if (nxf)  // the transformed files' planes into the second coefficient region, where their McuFile points
+    HIP_TRY(launch_coef_xform((const XfFile*)((const char*)c->mcu_up.p + o_xf),
+                              (const int32_t*)((const char*)c->mcu_up.p + o_xt), (long long)nxt,
+                              (const int16_t*)c->ent_cf.p, (int16_t*)c->ent_cf.p, s));
   HIP_TRY(launch_mcu_code(d, nf, (int)nseg, any_long, (const int16_t*)c->ent_cf.p, optimize != 0,
                           ent_es_tab(c->ent_tab.p), s));
   std::vector<unsigned long long> fl((size_t)nf);
@@ -2687,12 +2714,13 @@ static int mcu_emit(jds_ctx* c, const McuRun& r, const std::vector<long long>& f
 }
 
 // One job whose coefficients are in c->ent_cf, to host memory.
-static int mcu_single(jds_ctx* c, McuJob& job, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+static int mcu_single(jds_ctx* c, McuJob& job, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len,
+                      const XfSet* xf = nullptr) {
   std::vector<McuJob> jobs(1);
   jobs[0] = std::move(job);
   McuRun r;
   const CtxMarkScope marks_(c, c->stream);
-  int rc = mcu_code(c, jobs, optimize, &r);
+  int rc = mcu_code(c, jobs, optimize, &r, xf);
   if (rc) return rc;
   if (r.len[0] == 0) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
   *out_len = r.len[0];
@@ -2733,15 +2761,75 @@ int jds_jpeg_transcode(jds_ctx* c, const uint8_t* data, int64_t len, int32_t opt
   return mcu_single(c, job, optimize, out, out_cap, out_len);
 }
 
-int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
-                             int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
-                             jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+// One file's transform, settled on the host before anything runs: the
+// operation (JDS_XF_AUTO resolved from the spliced prefix), its geometry and
+// the prefix, edited unless the operation is none.
+struct XfJob {
+  int op = JDS_XF_NONE;
+  XfPlan plan;
+  std::vector<uint8_t> pfx;
+};
+
+static inline int64_t xf_align(int64_t entries) { return (entries + 127) & ~(int64_t)127; }
+
+static int xf_prepare(const uint8_t* data, int64_t len, const jds_jpeg_info* info, int32_t op_in, XfJob* x) {
+  const int base = op_in & 0xFF;
+  if (op_in < 0 || (op_in & ~(0xFF | JDS_XF_TRIM)) || base > JDS_XF_AUTO)
+    return fail(JDS_EINVAL, "unknown transform operation 0x%x", (unsigned)op_in);
+  McuJob sp;
+  int rc = mcu_job_splice(data, len, &sp);
+  if (rc) return rc;
+  x->pfx = std::move(sp.pfx);
+  int64_t pos = -1;
+  int big = 0, op = base;
+  if (base == JDS_XF_AUTO)
+    op = xf_op_of_orientation(xf_exif_orientation(x->pfx.data(), (int64_t)x->pfx.size(), &pos, &big));
+  char msg[320];
+  if ((rc = xf_plan(info, op, (op_in & JDS_XF_TRIM) != 0, &x->plan, msg, sizeof msg))) return fail(rc, "%s", msg);
+  x->op = op;
+  if (op == JDS_XF_NONE) return JDS_OK;
+  const int e = xf_edit_prefix(x->pfx.data(), (int64_t)x->pfx.size(), x->plan.flags, x->plan.dst.H, x->plan.dst.W);
+  if (e == -2) return fail(JDS_ENOTSUP, "DQT: a 16-bit or incomplete table cannot be transposed");
+  if (e) return fail(JDS_EINVAL, "header prefix: %s", e == -3 ? "no SOF0 segment" : "not a sequence of marker segments");
+  if (pos >= 0) xf_exif_reset(x->pfx.data(), pos, big);
+  return JDS_OK;
+}
+
+// jds_jpeg_batch_transcode, and with `xform` jds_jpeg_batch_transform: the same
+// launches with per-file transformed records handed to the writer's driver.
+static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, bool xform,
+                           const int32_t* ops, int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                           jds_jpeg_transcode_item* items, int64_t* out_bytes) {
   if (!c || !out_bytes || (n > 0 && !items)) return fail(JDS_EINVAL, "null argument");
   *out_bytes = 0;
   std::vector<jds_jpeg_batch_item> bi((size_t)(n > 0 ? n : 0));
   BatchPlan bp;
   int rc = batch_layout(data, lens, n, bi.data(), bp);
   if (rc) return rc;
+  // the transformed planes follow the decoder's in c->ent_cf: sized before the decode fills it
+  std::vector<XfJob> xj((size_t)(xform && n > 0 ? n : 0));
+  const int64_t xbase = xf_align(bp.coef_entries);
+  int64_t xtotal = 0;
+  for (int i = 0; xform && i < n; ++i) {
+    if (bp.rec_of[(size_t)i] < 0) continue;
+    XfJob& x = xj[(size_t)i];
+    const int rc1 = xf_prepare(data[i], lens[i], &bp.info[(size_t)i], ops ? ops[i] : JDS_XF_AUTO, &x);
+    if (rc1) {  // refused: an item error with the code the file would get alone
+      bi[(size_t)i].rc = rc1;
+      if (bp.first_bad < 0 || i < bp.first_bad) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", g_err);
+      }
+      continue;
+    }
+    bi[(size_t)i].H = x.plan.dst.H;
+    bi[(size_t)i].W = x.plan.dst.W;
+    if (x.op != JDS_XF_NONE) xtotal += xf_align(x.plan.dst.coeffs_needed);
+  }
+  if (xtotal) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(xbase + xtotal)));
+  }
   if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, nullptr, 0, nullptr, bi.data(), nullptr, false)))
     return rc;
   for (int i = 0; i < n; ++i) {
@@ -2758,12 +2846,27 @@ int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64
   // the files that decoded take part in the writer's launches
   std::vector<McuJob> jobs;
   std::vector<int> job_file;
+  XfSet xs;
+  int64_t xcur = xbase;
   for (size_t k = 0; k < bp.recs.size(); ++k) {
     const int i = bp.file_of[k];
-    if (items[i].status) continue;
+    if (items[i].status || items[i].rc) continue;
     McuJob j;
-    if ((rc = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, &j))) return rc;
-    if ((rc = mcu_job_splice(data[i], lens[i], &j))) return rc;
+    if (xform && xj[(size_t)i].op != JDS_XF_NONE) {  // the writer sees the destination planes
+      XfJob& x = xj[(size_t)i];
+      if ((rc = mcu_job_geo(&x.plan.dst, xcur, &j))) return rc;
+      XfFile rec = x.plan.rec;
+      for (int cc = 0; cc < 3; ++cc) {
+        rec.soff[cc] += bp.recs[k].coef_off;
+        rec.doff[cc] += xcur;
+      }
+      xs.add(rec);
+      xcur += xf_align(x.plan.dst.coeffs_needed);
+      j.pfx = std::move(x.pfx);
+    } else {
+      if ((rc = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, &j))) return rc;
+      if ((rc = mcu_job_splice(data[i], lens[i], &j))) return rc;
+    }
     jobs.push_back(std::move(j));
     job_file.push_back(i);
   }
@@ -2774,7 +2877,7 @@ int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64
   hipStream_t s = c->stream;
   const CtxMarkScope marks_(c, s);
   McuRun r;
-  if ((rc = mcu_code(c, jobs, optimize, &r))) return rc;
+  if ((rc = mcu_code(c, jobs, optimize, &r, xs.files.empty() ? nullptr : &xs))) return rc;
   std::vector<long long> fout(jobs.size(), -1ll);
   int64_t cur = 0;
   for (size_t k = 0; k < jobs.size(); ++k) {
@@ -2813,6 +2916,96 @@ int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64
   return JDS_OK;
 }
 
+int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                             jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  return batch_transcode(c, data, lens, n, false, nullptr, optimize, out, out_cap, out_on_device, items, out_bytes);
+}
+
+// ------------------------------------------------ lossless transforms --
+// (DESIGN.md "Lossless transforms"; kernel: jds_xform.hip; host side: jds_xform.hpp)
+
+int jds_jpeg_batch_transform(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             const int32_t* ops, int32_t optimize, uint8_t* out, int64_t out_cap,
+                             int32_t out_on_device, jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  return batch_transcode(c, data, lens, n, true, ops, optimize, out, out_cap, out_on_device, items, out_bytes);
+}
+
+int jds_jpeg_transform_info(const uint8_t* data, int64_t len, int32_t op, int32_t* op_out, int64_t* H_out,
+                            int64_t* W_out) {
+  if (!data || !op_out || !H_out || !W_out) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, &info, op, &x))) return rc;
+  *op_out = x.op;
+  *H_out = x.plan.dst.H;
+  *W_out = x.plan.dst.W;
+  return JDS_OK;
+}
+
+int jds_jpeg_transform(jds_ctx* c, const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                       int64_t out_cap, int64_t* out_len, jds_jpeg_info* info) {
+  if (!c || !data || !info || !out_len) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, info, op, &x))) return rc;
+  McuJob job;
+  if (x.op == JDS_XF_NONE) {  // jds_jpeg_transcode
+    if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+    job.pfx = std::move(x.pfx);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+    return mcu_single(c, job, optimize, out, out_cap, out_len);
+  }
+  const int64_t base = xf_align(info->coeffs_needed);
+  if ((rc = mcu_job_geo(&x.plan.dst, base, &job))) return rc;
+  job.pfx = std::move(x.pfx);
+  XfFile rec = x.plan.rec;
+  for (int cc = 0; cc < 3; ++cc) rec.doff[cc] += base;
+  XfSet xs;
+  xs.add(rec);
+  HIP_TRY(hipSetDevice(c->device));
+  // the transformed planes follow the decoder's: sized before the decode fills the buffer
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(base + x.plan.dst.coeffs_needed)));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  return mcu_single(c, job, optimize, out, out_cap, out_len, &xs);
+}
+
+int jds_selftest_coef_transform_dev(jds_ctx* c, const jds_jpeg_info* info, int32_t op, const int16_t* coeffs,
+                                    int16_t* coeffs_out) {
+  if (!c || !info || !coeffs || !coeffs_out) return fail(JDS_EINVAL, "null argument");
+  const int base_op = op & 0xFF;
+  if (op < 0 || (op & ~(0xFF | JDS_XF_TRIM)) || base_op >= JDS_XF_AUTO)
+    return fail(JDS_EINVAL, "unknown transform operation 0x%x (an explicit operation is needed)", (unsigned)op);
+  XfPlan p;
+  char msg[320];
+  int rc = xf_plan(info, base_op, (op & JDS_XF_TRIM) != 0, &p, msg, sizeof msg);
+  if (rc) return fail(rc, "%s", msg);
+  McuFile sf;
+  (void)mcu_file_of(info, &sf);  // (xf_plan has checked it)
+  const int64_t nsrc = mcu_coeffs(sf), base = xf_align(nsrc), ndst = p.dst.coeffs_needed;
+  XfFile rec = p.rec;
+  for (int cc = 0; cc < 3; ++cc) rec.doff[cc] += base;
+  const size_t o_t = (sizeof(XfFile) + 255) & ~(size_t)255, total = o_t + 4 * (size_t)p.tiles;
+  std::vector<char> h(total, 0);  // (the tile table: every tile is record 0's)
+  memcpy(h.data(), &rec, sizeof rec);
+  hipStream_t s = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(c->mcu_up.ensure(total));
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(base + ndst)));
+  int16_t* cf = (int16_t*)c->ent_cf.p;
+  HIP_TRY(hipMemcpyAsync(c->mcu_up.p, h.data(), total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(cf, coeffs, sizeof(int16_t) * (size_t)nsrc, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_coef_xform((const XfFile*)c->mcu_up.p, (const int32_t*)((const char*)c->mcu_up.p + o_t),
+                            (long long)p.tiles, cf, cf, s));
+  HIP_TRY(hipMemcpyAsync(coeffs_out, cf + base, sizeof(int16_t) * (size_t)ndst, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return JDS_OK;
+}
+
 // the host model's result into the caller's buffer
 static int mcu_host_result(int wrc, const std::vector<uint8_t>& file, uint8_t* out, int64_t out_cap,
                            int64_t* out_len) {
@@ -2844,6 +3037,35 @@ int jds_selftest_jpeg_transcode(const uint8_t* data, int64_t len, int32_t optimi
   mcu_std_tabs(&std_tabs);
   std::vector<uint8_t> file;
   const int wrc = mcu_host_write(job.f, cf.data(), optimize, job.pfx.data(), (int64_t)job.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_transform(const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                                int64_t out_cap, int64_t* out_len) {
+  if (!data || !out_len) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, &info, op, &x))) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(x.op == JDS_XF_NONE ? &info : &x.plan.dst, 0, &job))) return rc;
+  int lane_max, sb, spg;
+  rst_constants(&lane_max);
+  dec_constants(&sb, &spg);
+  std::vector<int16_t> cf((size_t)info.coeffs_needed);
+  int32_t rounds[3];
+  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  if (x.op != JDS_XF_NONE) {
+    std::vector<int16_t> dst((size_t)x.plan.dst.coeffs_needed);
+    xf_host(x.plan.rec, cf.data(), dst.data());
+    cf.swap(dst);
+  }
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, cf.data(), optimize, x.pfx.data(), (int64_t)x.pfx.size(), std_tabs, &file);
   return mcu_host_result(wrc, file, out, out_cap, out_len);
 }
 

@@ -111,6 +111,19 @@ class JpegTranscodeItem(C.Structure):
                 ('out_len', C.c_int64)]
 
 
+# lossless transform operations (include/jds.h JDS_XF_*)
+XF_OPS = {'none': 0, 'hflip': 1, 'vflip': 2, 'transpose': 3, 'transverse': 4, 'rot90': 5, 'rot180': 6, 'rot270': 7,
+          'auto': 8}
+XF_NAMES = {v: k for k, v in XF_OPS.items()}
+XF_TRIM = 0x100
+
+
+def xf_code(op: str, trim: bool = False) -> int:
+    if op not in XF_OPS:
+        raise ValueError(f'unknown transform operation {op!r}: one of {", ".join(XF_OPS)}')
+    return XF_OPS[op] | (XF_TRIM if trim else 0)
+
+
 # frame status bits of the entropy decoder (include/jds.h JDS_DEC_*)
 DEC_HEADER, DEC_CODE, DEC_K63, DEC_OVERRUN, DEC_COUNT, DEC_DC_RANGE, DEC_RESTART = 1, 2, 4, 8, 16, 32, 64
 
@@ -206,6 +219,15 @@ _SIGS = {
     'jds_selftest_jpeg_encode': (C.c_int, [C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
                                            C.POINTER(C.c_int64)]),
     'jds_selftest_jpeg_hist_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P]),
+    'jds_jpeg_transform_info': (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64)]),
+    'jds_jpeg_transform': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),
+                                     C.POINTER(JpegInfo)]),
+    'jds_jpeg_batch_transform': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int32,
+                                           C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
+    'jds_selftest_jpeg_transform': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64,
+                                              C.POINTER(C.c_int64)]),
+    'jds_selftest_coef_transform_dev': (C.c_int, [_P, C.POINTER(JpegInfo), C.c_int32, _P, _P]),
     'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),

@@ -374,10 +374,19 @@ def jpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = '
     first such index after the batch has run; errors='items' returns (outputs with None in its
     place, per-file dicts: 'rc', 'status', 'out_off', 'out_len', ...).  ctx: a caller-owned Context
     (e.g. a profiled one) instead of a pooled one."""
+    return _batch_transcode(files, optimize, out, errors, device, ctx, None)
+
+
+def _batch_transcode(files, optimize, out, errors, device, ctx, ops):
+    """jpeg_batch_transcode (ops None) and jpeg_batch_transform (ops: one JDS_XF_* code per file)."""
     if errors not in ('raise', 'items'):
         raise ValueError("errors must be 'raise' or 'items'")
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
+    if ops is not None:
+        if len(ops) != n:
+            raise ValueError(f'{len(ops)} operations for {n} files')
+        ops_arr = (C.c_int32 * max(n, 1))(*ops)
     items = (_abi.JpegTranscodeItem * max(n, 1))()
     need = C.c_int64(0)
     own = out is None or isinstance(out, str)
@@ -390,6 +399,9 @@ def jpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = '
 
     def run(c, buf, cap):
         dst, on_dev = (buf.ctypes.data, 0) if out is None else (int(buf.data_ptr()), 1)
+        if ops is not None:
+            return lib().jds_jpeg_batch_transform(c.handle, ptrs, lens, n, ops_arr, int(bool(optimize)),
+                                                  C.c_void_p(dst), cap, on_dev, items, C.byref(need))
         return lib().jds_jpeg_batch_transcode(c.handle, ptrs, lens, n, int(bool(optimize)), C.c_void_p(dst), cap,
                                               on_dev, items, C.byref(need))
 
@@ -429,6 +441,59 @@ def jpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = '
         v = buf[it['out_off']:it['out_off'] + it['out_len']]
         outs.append(v.tobytes() if out is None else v)
     return outs if errors == 'raise' else (outs, info)
+
+
+def jpeg_transform_info(data, op: str = 'auto', trim: bool = False) -> dict:
+    """jds_jpeg_transform_info (host only): what jpeg_transform would do to this file ->
+    {'op': the operation, 'auto' resolved from the EXIF Orientation, 'H', 'W': the output's size}.
+    ValueError for a file the parser rejects, a mirrored axis that is not whole MCUs without trim
+    (it names the axis and the multiple), a transposing operation at 4:2:2, a trim that leaves
+    nothing."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    op_out, H, W = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    check(lib().jds_jpeg_transform_info(p, n, _abi.xf_code(op, trim), C.byref(op_out), C.byref(H), C.byref(W)))
+    return {'op': _abi.XF_NAMES[int(op_out.value)], 'H': int(H.value), 'W': int(W.value)}
+
+
+def jpeg_transform(data, op: str = 'auto', trim: bool = False, optimize: bool = True, device: int = 0,
+                   with_info: bool = False):
+    """jds_jpeg_transform: jpeg_transcode with the image mirrored, transposed or rotated without
+    re-compression (what `jpegtran -flip / -transpose / -rotate` does; DESIGN.md "Lossless
+    transforms").  op: 'none', 'hflip', 'vflip', 'transpose', 'transverse', 'rot90' (clockwise),
+    'rot180', 'rot270', or 'auto': the operation the EXIF Orientation tag asks for, the tag reset to 1
+    (no usable tag: the plain transcode).  A mirrored axis must be whole MCUs: ValueError otherwise
+    (`jpegtran -perfect`), or with trim=True the partial MCU column / row is dropped first
+    (`jpegtran -trim`).  4:2:2 takes only 'hflip', 'vflip' and 'rot180'.  The coefficients never
+    leave the device and change in sign only.  with_info: (bytes, parse_jpeg's dict of the input
+    plus 'rounds' and 'transform': jpeg_transform_info's dict)."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    code = _abi.xf_code(op, trim)
+    info = _abi.JpegInfo()
+    with lease(device) as ctx:
+        out = entropy._grown(lambda o, cap, m: lib().jds_jpeg_transform(
+            ctx.handle, p, n, code, int(bool(optimize)), o.ctypes.data, cap, C.byref(m), C.byref(info)),
+            n + n // 4 + 4096)
+    if not with_info:
+        return out
+    d = entropy._jpeg_dict(info)
+    d['rounds'] = int(info.rounds)
+    d['transform'] = jpeg_transform_info(data, op, trim)
+    return out, d
+
+
+def jpeg_batch_transform(files, ops='auto', trim: bool = False, optimize: bool = True, out=None, errors: str = 'raise',
+                         device: int = 0, ctx=None):
+    """jds_jpeg_batch_transform: jpeg_batch_transcode with an operation per file -- each good
+    file's bytes are jpeg_transform's.  ops: one name for all files or a list with one name per file
+    (jpeg_transform's names); trim applies to all.  out, errors, ctx and the return shape as
+    jpeg_batch_transcode; an item's 'H' and 'W' are the output's size, and a file whose operation is
+    refused (a partial MCU on a mirrored axis without trim, a transposition at 4:2:2) is an item
+    error that does not stop the others."""
+    files = list(files)
+    names = [ops] * len(files) if isinstance(ops, str) else list(ops)
+    return _batch_transcode(files, optimize, out, errors, device, ctx, [_abi.xf_code(o, trim) for o in names])
 
 
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:

@@ -285,6 +285,44 @@ def host_transcode_jpeg(data, optimize: bool = True) -> bytes:
                                                                         C.byref(m)), max(1 << 16, 2 * n))
 
 
+def host_transform_jpeg(data, op: str = 'auto', trim: bool = False, optimize: bool = True) -> bytes:
+    """Test aid (jds_selftest_jpeg_transform): codec.jpeg_transform's host model -- the host decode
+    model, the host coefficient transform through the kernel's block map, the prefix editor and the
+    EXIF reader (csrc/jds_xform.hpp), then the writer's host model.  No GPU."""
+    a, p, n = _bytes_arg(data)
+    code = _abi.xf_code(op, trim)
+    return _grown(lambda out, cap, m: lib().jds_selftest_jpeg_transform(p, n, code, int(bool(optimize)), out.ctypes.data,
+                                                                        cap, C.byref(m)), max(1 << 16, 2 * n))
+
+
+def coef_transform_dev(coeffs: np.ndarray, info: dict, op: str, trim: bool = False, device: int = 0) -> np.ndarray:
+    """Test aid (jds_selftest_coef_transform_dev): k_coef_xform alone on host coefficients in
+    decode_jpeg's layout (info: 'H', 'W', 'mode', 'grids' of the source) -> the coefficients in the
+    destination's layout.  op: an explicit operation."""
+    st = _abi.JpegInfo()
+    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.MODE_CODES[info['mode']]
+    for c, (gr, gc) in enumerate(info['grids']):
+        st.grid_rows[c], st.grid_cols[c] = int(gr), int(gc)
+    cf = np.ascontiguousarray(coeffs, dtype=np.int16).reshape(-1)
+    need = 64 * sum(int(gr) * int(gc) for gr, gc in info['grids'])
+    if cf.size != need:
+        raise ValueError(f'expected {need} coefficients for these block grids, got {cf.size}')
+    # the destination's entries: the T.81 grids of the size after trim (a transposition keeps the count)
+    hs, vs = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}[info['mode']]
+    H, W = int(info['H']), int(info['W'])
+    if trim:
+        if op in ('hflip', 'rot180', 'transverse', 'rot270'):
+            W -= W % (8 * hs)
+        if op in ('vflip', 'rot180', 'transverse', 'rot90'):
+            H -= H % (8 * vs)
+    n_out = 64 * (-(-H // 8) * -(-W // 8) + 2 * (-(-(-(-H // vs)) // 8) * -(-(-(-W // hs)) // 8)))
+    out = np.empty(need, np.int16)          # (never more blocks than the source has)
+    with _abi.lease(device) as ctx:
+        check(lib().jds_selftest_coef_transform_dev(ctx.handle, C.byref(st), _abi.xf_code(op, trim), cf.ctypes.data,
+                                                    out.ctypes.data))
+    return out[:n_out]
+
+
 def transcode_histogram_dev(coeffs: np.ndarray, info: dict, device: int = 0) -> dict:
     """Test aid (jds_selftest_jpeg_hist_dev): the interleaved scan's symbol counts by k_mcu_hist
     -> {'dc0', 'ac0', 'dc1', 'ac1'}: counts[256]."""

@@ -25,7 +25,12 @@ jpeg_transcode calls in the same process, every batch output compared with its s
 per-kernel times of the batch from the context's launch marks, split into the decode's and the
 writer's (k_mcu_*, k_ent_opt_tables); input and output bytes; and beside them, in the same run,
 jpeg_batch_to_rgb(out=tensor) on the same files (the batch decode with its inverse).  Writes
-profiles/transcode_probe.json (or --out FILE)."""
+profiles/transcode_probe.json (or --out FILE).
+--transform N (default 64) instead: the N 1080p files through jpeg_batch_transform(out=tensor,
+optimize=True) with 'rot90' for all (1080 is not a multiple of 16: with trim), 'hflip' for all and
+'auto' on these files without EXIF (the plain transcode), and jpeg_batch_transcode beside them in
+the same run; k_coef_xform on its own from the context's launch marks; four outputs of each leg
+compared with the single call.  Writes profiles/transform_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -275,7 +280,64 @@ def transcode_main():
     return 0 if all(r[k]['batch_equals_singles'] for r in rows for k in ('annex_k', 'optimize')) else 1
 
 
+def transform_main():
+    import torch
+    from jds import _abi
+    i = sys.argv.index('--transform')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    files = [pillow_file(np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8)) for k in range(n)]
+    ctx = _abi.Context(0)
+    legs = [('transcode', None, False), ('rot90_trim', 'rot90', True), ('hflip', 'hflip', False),
+            ('auto_no_exif', 'auto', False)]
+
+    def call(op, trim, **kw):
+        if op is None:
+            return codec.jpeg_batch_transcode(files, optimize=True, ctx=ctx, **kw)
+        return codec.jpeg_batch_transform(files, op, trim=trim, optimize=True, ctx=ctx, **kw)
+
+    row = {'n': n, 'H': H, 'W': W, 'input_bytes': int(sum(len(f) for f in files)), 'legs': {}}
+    ok = True
+    for name, op, trim in legs:
+        outs = call(op, trim)
+        buf = torch.empty(sum(-(-len(o) // 256) * 256 for o in outs), dtype=torch.uint8, device='cuda')
+        some = range(0, n, max(1, n // 4))
+        singles = [codec.jpeg_transcode(files[k]) if op is None else codec.jpeg_transform(files[k], op, trim=trim)
+                   for k in some]
+        equal = singles == [outs[k] for k in some]
+        if name == 'auto_no_exif':
+            equal = equal and outs == call(None, False)
+        ok = ok and equal
+        tb = timed(lambda: call(op, trim, out=buf))
+        ctx.profile(True)
+        reps = 5
+        for _ in range(reps):
+            call(op, trim, out=buf)
+        kern, span = ctx.profile_read()
+        ctx.profile(False)
+        writer = {k: v[0] / reps for k, v in kern.items() if k.startswith('k_mcu') or k.startswith('k_ent_opt')}
+        row['legs'][name] = {'batch_to_device': tb, 'output_bytes': int(sum(len(o) for o in outs)),
+                             'equals_single_calls': bool(equal),
+                             'out_size': list(codec.jpeg_transform_info(outs[0], 'none').values())[1:],
+                             'k_coef_xform_ms_per_batch': kern.get('k_coef_xform', (0.0, 0))[0] / reps,
+                             'k_coef_xform_launches_per_batch': kern.get('k_coef_xform', (0.0, 0))[1] / reps,
+                             'writer_kernels_ms_total': sum(writer.values()),
+                             'marks_span_ms_per_batch': span / reps}
+    ctx.close()
+    base = row['legs']['transcode']['batch_to_device']['median_ms']
+    for name in ('rot90_trim', 'hflip', 'auto_no_exif'):
+        row['legs'][name]['minus_transcode_ms'] = row['legs'][name]['batch_to_device']['median_ms'] - base
+    print(json.dumps(row), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'transform_probe.json')
+    with open(out, 'w') as f:
+        json.dump([row], f, indent=1)
+        f.write('\n')
+    return 0 if ok else 1
+
+
 def main():
+    if '--transform' in sys.argv:
+        return transform_main()
     if '--batch' in sys.argv:
         return batch_main()
     if '--transcode' in sys.argv:
