@@ -33,6 +33,7 @@ extern "C" {
 #define JDS_SS_444 0
 #define JDS_SS_422 1
 #define JDS_SS_420 2
+#define JDS_SS_GRAY 3 /* one-component (grayscale) files: jds_jpeg_parse and the calls on foreign files only */
 
 /* jds_plan_run flags */
 #define JDS_RUN_SSE 1u  /* fill sse_rgb / sse_y (PSNR); the inverse kernel re-reads the input */
@@ -461,20 +462,37 @@ int jds_selftest_huffopt_dev(jds_ctx* ctx, const uint32_t* freqs, int32_t n, uin
  *     ceil(ceil(W * Hc / Hmax) / 8) columns (rows alike); reference_grid says
  *     whether they equal the floor-sized grids of the calls above;
  *   - with an interleaved scan DRI counts MCUs: ceil(nMCU / Ri) - 1 markers,
- *     RST0, RST1, .. in order.
- * Still rejected by name: progressive, arithmetic, 12-bit, grayscale, 16-bit
- * DQT, Huffman ids above 1, DHT redefined between scans, component ids other
- * than 1, 2, 3, luma sampling other than 1x1, 2x1, 2x2, subsampled chroma.
+ *     RST0, RST1, .. in order;
+ *   - grayscale files (DESIGN.md "Grayscale files"): SOF0 with Nf = 1, any
+ *     component id 0..255 (the SOS must name the same one), sampling factors
+ *     1..4 each -- which are then IGNORED: a one-component scan is never
+ *     interleaved (T.81 A.2.2), so the block grid is ceil(W/8) x ceil(H/8)
+ *     whatever the byte says (Pillow writes 0x22 with subsampling=2; libjpeg
+ *     reads such files as 1x1) -- and exactly one scan with Ns = 1, whose DRI
+ *     counts blocks.  subsampling = JDS_SS_GRAY, n_scans = 1, interleaved = 0,
+ *     blocks_per_mcu = 1, hs[0] = vs[0] = 1, mcu_cols / mcu_rows = the grid,
+ *     single_table = 1, reference_grid = 0; hs, vs, tq, grid_cols, grid_rows and
+ *     qtable of components 1 and 2 are zero; scan[0].component[0] is 1 (the
+ *     file's own id stays in its header).  A scan with Ns != 1, a scan naming
+ *     another id, or a second scan in such a frame is an error naming
+ *     "grayscale".
+ * Still rejected by name: progressive, arithmetic, 12-bit, two- and
+ * four-component frames (CMYK / YCCK), 16-bit DQT, Huffman ids above 1, DHT
+ * redefined between scans, component ids other than 1, 2, 3 in a
+ * three-component frame, luma sampling other than 1x1, 2x1, 2x2, subsampled
+ * chroma.  jds_jfif_parse keeps this library's own profile and rejects
+ * grayscale files.
  *
  * Coefficient layout of every decode: Y, Cb, Cr planar, each component's
- * blocks in raster order of its T.81 grid, each block row-major;
+ * blocks in raster order of its T.81 grid, each block row-major (a grayscale
+ * file: the one plane);
  * coeffs_needed = 64 * sum of the grid sizes (with reference_grid set: exactly
  * the layout of jds_decode_jfif).  The blocks an interleaved scan carries
  * beyond the grids (padding to whole MCUs) are decoded, count in their
  * component's DC prediction and are dropped. */
 typedef struct {
   int32_t n_components;       /* Ns: 3 (interleaved) or 1 */
-  int32_t component[3];       /* 1 Y, 2 Cb, 3 Cr, in scan order */
+  int32_t component[3];       /* 1 Y, 2 Cb, 3 Cr, in scan order (a grayscale file's component: 1) */
   int32_t dc_table[3], ac_table[3]; /* Huffman table ids (0 / 1) per scan component */
   int32_t restart_interval;   /* DRI in effect at SOS, in MCUs of this scan (Ns = 1: blocks); 0: none */
   int64_t offset, length;     /* the entropy-coded segment, RSTm markers included */
@@ -482,17 +500,17 @@ typedef struct {
 
 typedef struct {
   int64_t H, W;
-  int32_t subsampling;        /* JDS_SS_* */
-  int32_t n_scans;            /* 1 (interleaved) or 3 */
+  int32_t subsampling;        /* JDS_SS_*; JDS_SS_GRAY: one component */
+  int32_t n_scans;            /* 1 (interleaved, or grayscale) or 3 */
   int32_t interleaved;        /* 1: one scan with Ns = 3 */
   int32_t reference_grid;     /* 1: the T.81 grids are the ones jds_jfif_parse accepts */
   int32_t single_table;       /* 1: one quantisation table serves all three components */
-  int32_t blocks_per_mcu;     /* of the interleaved MCU: 6 (4:2:0), 4 (4:2:2), 3 (4:4:4) */
-  int32_t hs[3], vs[3];       /* sampling factors per component */
+  int32_t blocks_per_mcu;     /* of the interleaved MCU: 6 (4:2:0), 4 (4:2:2), 3 (4:4:4); grayscale: 1 */
+  int32_t hs[3], vs[3];       /* sampling factors per component (grayscale: 1 x 1, zero for the absent ones) */
   int32_t tq[3];              /* quantisation table id per component */
   int64_t mcu_cols, mcu_rows; /* ceil(W / (8 Hmax)), ceil(H / (8 Vmax)) */
-  int64_t grid_cols[3], grid_rows[3]; /* T.81 block grid per component */
-  double qtable[3][64];       /* per component, row-major (de-zigzagged) */
+  int64_t grid_cols[3], grid_rows[3]; /* T.81 block grid per component (zero for an absent one) */
+  double qtable[3][64];       /* per component, row-major (de-zigzagged; zero for an absent one) */
   jds_jpeg_scan scan[3];      /* in file order */
   jds_jfif_huff huff[4];      /* [0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1 */
   int64_t coeffs_needed;      /* 64 * sum of grid_cols[c] * grid_rows[c] */
@@ -514,7 +532,7 @@ int jds_decode_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coe
 /* jds_decompress_jfif for a file of either scan form that the plan's inverse can
  * take: one quantisation table for all components (single_table) and the
  * reference's block grids (reference_grid); anything else is JDS_ENOTSUP.  Such
- * files -- a table per component, other grids -- are reconstructed stage by
+ * files -- a table per component, other grids, grayscale -- are reconstructed stage by
  * stage with the file's own tables (jds.codec.decompress_jpeg: jds_stage_quantize_n,
  * jds_stage_block_dct_n, jds_stage_upsample, jds_stage_ycbcr_to_rgb), not a
  * throughput path.  coeffs: NULL, or info->coeffs_needed entries. */
@@ -527,7 +545,12 @@ int jds_decompress_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t*
  * (jds.codec.staged_inverse) reconstructs: dequantise with the component's
  * table, the exact fp64 IDCT, +128, clip, crop chroma to its T.81 plane
  * ceil(H Vc / Vmax) x ceil(W Hc / Hmax), cv2 INTER_LINEAR with its general taps
- * to H x W, NumPy's colour expressions, clip, truncate.
+ * to H x W, NumPy's colour expressions, clip, truncate.  A grayscale file
+ * (JDS_SS_GRAY) gives (Y, Y, Y) per pixel -- the same definition at neutral
+ * chroma, where the colour expressions are Y + c * 0.0 = Y -- through an
+ * instantiation of its own that reads the one plane and the one table only:
+ * qtable, grid_rows / grid_cols of component 0 and coeffs_needed = one plane are
+ * checked, the rest of info is not read.
  *
  * jds_jpeg_inverse_info: the tile of output pixels one workgroup produces
  *   (compile-time constants, multiples of 16).
@@ -567,7 +590,9 @@ int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, 
  * any mix of sizes, subsampling modes, tables, restart intervals and scan forms
  * through ONE set of launches -- the entropy decode over the descriptors of
  * every file (as many propagation rounds as the slowest file needs), then
- * k_jpeg_inv_batch once per subsampling mode present -- into one output buffer.
+ * k_jpeg_inv_batch once per mode present (4:4:4, 4:2:2, 4:2:0, grayscale; a
+ * grayscale item's subsampling is JDS_SS_GRAY and its image H x W x 3 like the
+ * others') -- into one output buffer.
  *
  * Layout: file i's image starts at items[i].rgb_off, a multiple of 256, and the
  *   images follow one another in batch order; rgb_bytes is the sum of the
@@ -619,7 +644,11 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
  * tests/transcode_ref.py): the coefficients of jds_decode_jpeg written back as
  * the file form everybody else writes -- ONE interleaved scan (Ns = 3,
  * components 1, 2, 3; Y with Huffman tables 0/0, Cb and Cr with 1/1, whatever
- * the input assigned; no DRI) -- by the interleaved instantiation of the
+ * the input assigned; no DRI; a grayscale file: SOI | prefix | DHT 0x00 | DHT
+ * 0x10 | SOS of Ns = 1 naming the frame's component id | scan | EOI, what
+ * libjpeg writes, with optimised tables from the luma counts alone; without a
+ * prefix jds_encode_jpeg writes APP0, one DQT and SOF0 with Nf = 1, id 1,
+ * sampling 0x11) -- by the interleaved instantiation of the
  * one-pass coder (csrc/jds_entropy_mcu.hip).  No pixel and no coefficient
  * changes.  The output is
  *     SOI | prefix | DHT 0x00, 0x10, 0x01, 0x11 | SOS | scan | EOI
@@ -719,7 +748,9 @@ int jds_selftest_jpeg_hist_dev(jds_ctx* ctx, const jds_jpeg_info* info, const in
  *   first cropped on that axis to whole MCUs (`jpegtran -trim`; JDS_EINVAL when
  *   nothing is left).  Transposition alone has no size constraint.  4:2:2
  *   takes only hflip, vflip and rot180 (a transposed file would be 4:4:0):
- *   JDS_ENOTSUP.  JDS_XF_NONE gives the bytes of jds_jpeg_transcode.
+ *   JDS_ENOTSUP.  A grayscale file's MCU is 8 x 8 whatever its sampling byte
+ *   says (jpegtran's rule for one-component files) and it takes every
+ *   operation.  JDS_XF_NONE gives the bytes of jds_jpeg_transcode.
  * Header: the prefix of the transcode with, for transposing operations, every
  *   8-bit table of every DQT segment transposed and SOF0's Y and X swapped;
  *   SOF0 gets the cropped size under trim.  Everything else verbatim.

@@ -143,9 +143,9 @@ void jpeg_inv_constants(int* th, int* tw);
 bool jpeg_inv_fits(const JInvArgs& a);
 hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb);
-hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[3], const int nmap[3],
-                                 const int tiles[3], const uint32_t* status, const int16_t* coeffs, uint8_t* rgb,
-                                 hipStream_t s);
+hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
+                                 const int nmap[JI_MODES], const int tiles[JI_MODES], const uint32_t* status,
+                                 const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 }
 
 // skimage: C1 = (K1 * R) ** 2, C2 = (K2 * R) ** 2 with R = data_range = 255
@@ -1823,7 +1823,7 @@ static long long next_rst(const uint8_t* d, long long a, long long n) {
 // sum is the interval's.
 static int plain_descriptors(const uint8_t* data, const jds_jfif_info* info, const FilePlace& pl, int lane_max,
                              std::vector<DecScan>& sc, std::vector<RstIv>& ivs) {
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < info->n_scans; ++i) {  // (three; one for a grayscale file)
     const jds_jfif_scan& f = info->scan[i];
     const int comp = f.component - 1;
     if (f.length >= (int64_t)1 << 40) return fail(JDS_ENOTSUP, "scan of %lld bytes", (long long)f.length);
@@ -2074,14 +2074,15 @@ static int decode_il_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_
   return JDS_OK;
 }
 
-// A file of three non-interleaved scans in the terms of the first decoder.
+// A file of three non-interleaved scans (a grayscale file: of one) in the terms
+// of the first decoder.
 static void jfif_view(const jds_jpeg_info* info, jds_jfif_info* fi) {
   memset(fi, 0, sizeof *fi);
   fi->H = info->H;
   fi->W = info->W;
   fi->subsampling = info->subsampling;
-  fi->n_scans = 3;
-  for (int i = 0; i < 3; ++i) {
+  fi->n_scans = info->n_scans;
+  for (int i = 0; i < info->n_scans; ++i) {
     const jds_jpeg_scan& f = info->scan[i];
     fi->scan[i].component = f.component[0];
     fi->scan[i].dc_table = f.dc_table[0];
@@ -2134,6 +2135,9 @@ int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* r
   if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
   int rc = jds_jpeg_parse(data, len, info);
   if (rc) return rc;
+  if (info->subsampling == JDS_SS_GRAY)
+    return fail(JDS_ENOTSUP, "the plan's inverse takes three components: this is a grayscale file "
+                             "(jds_jpeg_to_rgb reconstructs it)");
   if (!info->single_table || !info->reference_grid)
     return fail(JDS_ENOTSUP, "the plan's inverse takes one quantisation table and the reference's block grids: "
                              "%s (the per-stage calls reconstruct such a file)",
@@ -2237,13 +2241,13 @@ int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_
 // (DESIGN.md "Batches of foreign files")
 
 // What the layout keeps per batch: the parsed files, the inverse records of the
-// ones that take part (in batch order) and the tile maps of the three launches.
+// ones that take part (in batch order) and the tile maps of the four launches.
 struct BatchPlan {
   std::vector<jds_jpeg_info> info;  // per file
   std::vector<int> rec_of;          // per file: its record, or -1
   std::vector<int> file_of;         // per record: its file
   std::vector<JInvRec> recs;
-  std::vector<JInvMap> map[3];
+  std::vector<JInvMap> map[JI_MODES];
   int64_t rgb_bytes = 0, coef_entries = 0;
   int first_bad = -1;
   char first_msg[400] = "";
@@ -2357,8 +2361,12 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
     st[k] = hd_jpeg_host_decode(data[i], &bp.info[(size_t)i], subseq_bits, lane_max, coeffs + bp.recs[k].coef_off, rounds);
     items[i].status = st[k];
   }
-  const JInvMap* maps[3] = {bp.map[0].data(), bp.map[1].data(), bp.map[2].data()};
-  const int nmap[3] = {(int)bp.map[0].size() - 1, (int)bp.map[1].size() - 1, (int)bp.map[2].size() - 1};
+  const JInvMap* maps[JI_MODES];
+  int nmap[JI_MODES];
+  for (int m = 0; m < JI_MODES; ++m) {
+    maps[m] = bp.map[m].data();
+    nmap[m] = (int)bp.map[m].size() - 1;
+  }
   jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
   batch_note(bp);
   return JDS_OK;
@@ -2436,8 +2444,8 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
   const long long ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
   const long long ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
   if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
-  int map_off[3], nmap[3], tiles[3], nm = 0;
-  for (int m = 0; m < 3; ++m) {
+  int map_off[JI_MODES], nmap[JI_MODES], tiles[JI_MODES], nm = 0;
+  for (int m = 0; m < JI_MODES; ++m) {
     map_off[m] = nm;
     nmap[m] = (int)bp.map[m].size() - 1;
     tiles[m] = bp.map[m].back().tile0;
@@ -2462,7 +2470,7 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
   memcpy(h + o_tabs, tabs.data(), sizeof(HuffDecTab) * tabs.size());
   memcpy(h + o_mcu, mcus.data(), sizeof(HdMcu) * mcus.size());
   memcpy(h + o_rec, bp.recs.data(), sizeof(JInvRec) * (size_t)nv);
-  for (int m = 0; m < 3; ++m)
+  for (int m = 0; m < JI_MODES; ++m)
     memcpy(h + o_map + sizeof(JInvMap) * (size_t)map_off[m], bp.map[m].data(), sizeof(JInvMap) * bp.map[m].size());
   if (!iv_il.empty()) memcpy(h + o_ivil, iv_il.data(), sizeof(RstIv) * iv_il.size());
   if (!iv_pl.empty()) memcpy(h + o_ivpl, iv_pl.data(), sizeof(RstIv) * iv_pl.size());
@@ -2636,6 +2644,7 @@ static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun*
     f.raw_words = mcu_raw_words(f.nblk);
     f.pfx_off = pfx_bytes;
     f.pfx_len = (int32_t)jobs[(size_t)k].pfx.size();
+    if (f.gray) f.comp_id = mcu_gray_id(jobs[(size_t)k].pfx.data(), f.pfx_len);
     nseg += f.nseg;
     raw_words += f.raw_words;
     pfx_bytes += f.pfx_len;

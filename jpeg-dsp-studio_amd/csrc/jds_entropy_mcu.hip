@@ -230,9 +230,19 @@ __global__ void __launch_bounds__(256) k_mcu_place(const McuFile* __restrict__ f
 
 // ------------------------------------------------- per-file prefixes --
 
-// the file's bytes before its scan: SOI, prefix, the four DHT segments, SOS
+// the bytes of a frame's DHT segments that a file carries: all four, or for a
+// grayscale file the first two (DC 0x00, AC 0x10: the luma class leads the
+// frame's header), found by the segments' own length fields
+__device__ __forceinline__ int mcu_dht_len(const McuFile& F, const OptFrame& o) {
+  if (!F.gray) return (int)o.hdr_len - ENT_HDR_FIXED;
+  const uint8_t* h = o.hdr + ENT_HDR_FIXED;
+  const int l0 = 2 + ((h[2] << 8) | h[3]);
+  return l0 + 2 + ((h[l0 + 2] << 8) | h[l0 + 3]);
+}
+
+// the file's bytes before its scan: SOI, prefix, its DHT segments, SOS
 __device__ __forceinline__ long long mcu_head_len(const McuFile& F, const OptFrame* __restrict__ of) {
-  return 2ll + F.pfx_len + ((long long)of[F.frame].hdr_len - ENT_HDR_FIXED) + MCU_SOS;
+  return 2ll + F.pfx_len + mcu_dht_len(F, of[F.frame]) + (F.gray ? MCU_SOS1 : MCU_SOS);
 }
 
 // k_ent_fscan per file (one 1024-thread workgroup each): out[g] = the
@@ -310,7 +320,7 @@ __global__ void __launch_bounds__(256) k_mcu_head(const McuFile* __restrict__ fi
   const McuFile F = files[f];
   uint8_t* dst = out + fout[f];
   const OptFrame& o = of[F.frame];
-  const int nd = (int)o.hdr_len - ENT_HDR_FIXED;
+  const int nd = mcu_dht_len(F, o);
   if (t == 0) {
     dst[0] = 0xFF;
     dst[1] = 0xD8;
@@ -319,7 +329,12 @@ __global__ void __launch_bounds__(256) k_mcu_head(const McuFile* __restrict__ fi
   for (int i = t; i < F.pfx_len; i += 256) dst[2 + i] = ps[i];
   uint8_t* d2 = dst + 2 + F.pfx_len;
   for (int i = t; i < nd; i += 256) d2[i] = o.hdr[ENT_HDR_FIXED + i];
-  if (t < MCU_SOS) {
+  if (F.gray) {  // (uniform: a field of the file's record)
+    if (t < MCU_SOS1) {
+      const uint8_t sos[MCU_SOS1] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)F.comp_id, 0x00, 0x00, 0x3F, 0x00};
+      d2[nd + t] = sos[t];
+    }
+  } else if (t < MCU_SOS) {
     const uint8_t sos[MCU_SOS] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 1, 0x00, 2, 0x11, 3, 0x11, 0x00, 0x3F, 0x00};
     d2[nd + t] = sos[t];
   }

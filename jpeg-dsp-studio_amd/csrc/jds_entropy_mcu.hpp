@@ -27,7 +27,7 @@ namespace jds {
 // raster order, then Cb, then Cr (T.81 A.2.3).  Segment g of the batch's
 // segment table is blocks [64 (g - seg0), 64 (g - seg0) + 64) of that scan.
 struct McuFile {
-  int32_t bpm;                 // blocks per MCU: hs * vs + 2
+  int32_t bpm;                 // blocks per MCU: hs * vs + 2; a grayscale file: 1 (the MCU is one block)
   int32_t mcu_cols, mcu_rows;
   int32_t nblk;                // bpm * mcu_cols * mcu_rows, padding blocks included
   int32_t hs, vs;              // luma sampling factors (chroma: 1 x 1)
@@ -35,6 +35,8 @@ struct McuFile {
   int32_t seg0, nseg;          // its segments in the batch's table
   int32_t frame;               // its code tables (OptFrame): its own when optimised, the shared Annex K one otherwise
   int32_t pfx_len;             // header prefix: the bytes between SOI and the first DHT
+  int32_t gray;                // 1: one component -- two DHT segments (0x00, 0x10) and the SOS of Ns = 1
+  int32_t comp_id;             // gray: the frame's component id, which the SOS names (mcu_gray_id)
   int64_t off[3];              // a plane's first coefficient, from the coefficient base (jds_decode_jpeg's layout)
   int64_t raw_w0;              // the packed scan's first word
   int64_t raw_words;           // its capacity
@@ -42,14 +44,15 @@ struct McuFile {
 };
 
 constexpr int MCU_SOS = 14;    // FF DA 00 0C 03 | 1 00 2 11 3 11 | 00 3F 00
+constexpr int MCU_SOS1 = 10;   // grayscale: FF DA 00 08 01 | id 00 | 00 3F 00
 
 // A scan position as (MCU column, MCU row, slot): two divisions, done once per
-// block (bpm is 3, 4 or 6, so the first is by a constant on every path).
+// block (bpm is 1, 3, 4 or 6, so the first is by a constant on every path).
 struct McuPos {
   int mx, my, slot;
 };
 JDS_MCU McuPos mcu_pos(const McuFile& f, int n) {
-  const int mcu = f.bpm == 6 ? n / 6 : (f.bpm == 4 ? n >> 2 : n / 3);
+  const int mcu = f.bpm == 6 ? n / 6 : (f.bpm == 4 ? n >> 2 : (f.bpm == 1 ? n : n / 3));
   McuPos p;
   p.slot = n - mcu * f.bpm;
   p.my = mcu / f.mcu_cols;
@@ -84,7 +87,8 @@ JDS_MCU int mcu_locate(const McuFile& f, int n, long long& addr) { return mcu_lo
 // DC before it, the nearest real block back from there: at most 2 hs vs - 1
 // steps.  -1: the scan's first block of the component (prediction 0).  On T.81
 // grids slot 0 of every component is real, so the walk always ends in this MCU
-// or the previous one.
+// or the previous one.  With one block per MCU (grayscale) that is the previous
+// block in raster order.
 JDS_MCU long long mcu_pred(const McuFile& f, const McuPos& p) {
   const int ny = f.hs * f.vs;
   const int lo = p.slot < ny ? 0 : p.slot, hi = p.slot < ny ? ny - 1 : p.slot;
@@ -109,9 +113,19 @@ JDS_MCU long long mcu_pred(const McuFile& f, int n) { return mcu_pred(f, mcu_pos
 inline int mcu_file_of(const jds_jpeg_info* info, McuFile* f) {
   memset(f, 0, sizeof *f);
   const int ss = info->subsampling;
-  if (ss != JDS_SS_444 && ss != JDS_SS_422 && ss != JDS_SS_420) return -1;
+  if (ss != JDS_SS_444 && ss != JDS_SS_422 && ss != JDS_SS_420 && ss != JDS_SS_GRAY) return -1;
   const int64_t H = info->H, W = info->W;
   if (H < 1 || W < 1 || H > 65535 || W > 65535 || H * W > (int64_t)1 << 28) return -1;
+  if (ss == JDS_SS_GRAY) {  // one plane, no padding blocks; components 1 and 2 are empty and start at its end
+    f->hs = f->vs = f->bpm = f->gray = f->comp_id = 1;
+    f->gw[0] = f->mcu_cols = (int32_t)((W + 7) / 8);
+    f->gh[0] = f->mcu_rows = (int32_t)((H + 7) / 8);
+    if (info->grid_cols[0] != f->gw[0] || info->grid_rows[0] != f->gh[0]) return -1;
+    f->nblk = f->gw[0] * f->gh[0];
+    f->off[1] = f->off[2] = 64ll * f->nblk;
+    f->nseg = (f->nblk + 63) / 64;
+    return 0;
+  }
   f->hs = ss == JDS_SS_444 ? 1 : 2;
   f->vs = ss == JDS_SS_420 ? 2 : 1;
   f->bpm = f->hs * f->vs + 2;
@@ -138,6 +152,8 @@ inline int64_t mcu_coeffs(const McuFile& f) { return f.off[2] + 64ll * f.gw[2] *
 // The header prefix of a transcoded file: every marker segment of the input
 // between SOI and its first SOS, verbatim and in order, except DHT and DRI
 // (fill bytes between segments are dropped).  out == nullptr: only the length.
+// A grayscale file's prefix needs nothing else: its SOF0 (Nf = 1, the
+// component id and sampling byte as written) travels verbatim.
 // Returns the prefix's length, or -1 when the bytes are not a marker sequence
 // that reaches an SOS inside [data, data + len) -- what jds_jpeg_parse rejects
 // as well.  Never reads outside [data, data + len) nor writes outside
@@ -176,6 +192,24 @@ constexpr uint8_t MCU_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 
 
 constexpr int MCU_PFX_DEFAULT_MAX = 18 + 3 * 69 + 19;
 
+// The component id in the SOF0 of a grayscale file's prefix (1 where the
+// prefix holds no one-component SOF0: the caller's business).  Never reads
+// outside [pfx, pfx + len).
+inline int mcu_gray_id(const uint8_t* pfx, int64_t len) {
+  int64_t p = 0;
+  while (pfx && p + 4 <= len && pfx[p] == 0xFF) {
+    if (pfx[p + 1] == 0xFF) {
+      ++p;
+      continue;
+    }
+    const int64_t ln = ((int64_t)pfx[p + 2] << 8) | pfx[p + 3];
+    if (ln < 2 || p + 2 + ln > len) break;
+    if (pfx[p + 1] == 0xC0) return ln >= 11 && pfx[p + 9] == 1 ? pfx[p + 10] : 1;
+    p += 2 + ln;
+  }
+  return 1;
+}
+
 // What jds_encode_jpeg writes when the caller gives no prefix: APP0 (JFIF
 // 1.01), one DQT per table id in use (in component order), SOF0.  out:
 // MCU_PFX_DEFAULT_MAX bytes.  Returns the length, or -(1 + 64 c + i) when
@@ -186,7 +220,8 @@ inline int mcu_default_prefix(const jds_jpeg_info* info, uint8_t* out) {
   memcpy(out, app0, 18);
   p = 18;
   bool done[4] = {false, false, false, false};
-  for (int c = 0; c < 3; ++c) {
+  const int ncomp = info->subsampling == JDS_SS_GRAY ? 1 : 3;  // (a grayscale info's tq[1..2] are not read)
+  for (int c = 0; c < ncomp; ++c) {
     const int id = info->tq[c];
     if (id < 0 || id > 3) return -1000;
     if (done[id]) continue;
@@ -201,6 +236,12 @@ inline int mcu_default_prefix(const jds_jpeg_info* info, uint8_t* out) {
     }
   }
   const int H = (int)info->H, W = (int)info->W;
+  if (ncomp == 1) {  // Nf = 1, id 1, sampling 0x11
+    const uint8_t sof[13] = {0xFF, 0xC0, 0x00, 0x0B, 0x08, (uint8_t)(H >> 8), (uint8_t)(H & 255), (uint8_t)(W >> 8),
+                             (uint8_t)(W & 255), 1, 1, 0x11, (uint8_t)info->tq[0]};
+    memcpy(out + p, sof, 13);
+    return p + 13;
+  }
   const int smp = info->subsampling == JDS_SS_420 ? 0x22 : (info->subsampling == JDS_SS_422 ? 0x21 : 0x11);
   const uint8_t sof[19] = {0xFF, 0xC0, 0x00, 0x11, 0x08, (uint8_t)(H >> 8), (uint8_t)(H & 255), (uint8_t)(W >> 8),
                            (uint8_t)(W & 255), 3, 1, (uint8_t)smp, (uint8_t)info->tq[0], 2, 0x11, (uint8_t)info->tq[1],
@@ -304,10 +345,11 @@ inline int mcu_host_write(const McuFile& f, const int16_t* coeffs, int optimize,
            }) && ok;
     }
   };
+  const int ntab = f.gray ? 2 : 4;  // a grayscale file: the luma class alone
   if (optimize) {
     std::vector<uint32_t> freq(4 * 256, 0u);
     each_block([&](int cls, bool dc, int s, uint32_t, int) { freq[(size_t)(2 * cls + (dc ? 0 : 1)) * 256 + s]++; });
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < ntab; ++t) {
       HoTable ht;
       ho_build_host(&freq[(size_t)t * 256], &ht);
       if (ht.fell_back) continue;
@@ -322,7 +364,7 @@ inline int mcu_host_write(const McuFile& f, const int16_t* coeffs, int optimize,
   o.push_back(0xD8);
   o.insert(o.end(), pfx, pfx + pfx_len);
   const int tc_th[4] = {0x00, 0x10, 0x01, 0x11};
-  for (int t = 0; t < 4; ++t) {
+  for (int t = 0; t < ntab; ++t) {
     const int len = 3 + 16 + tab[t].n_vals;
     const uint8_t h[5] = {0xFF, 0xC4, (uint8_t)(len >> 8), (uint8_t)(len & 255), (uint8_t)tc_th[t]};
     o.insert(o.end(), h, h + 5);
@@ -330,7 +372,11 @@ inline int mcu_host_write(const McuFile& f, const int16_t* coeffs, int optimize,
     o.insert(o.end(), tab[t].vals, tab[t].vals + tab[t].n_vals);
   }
   const uint8_t sos[MCU_SOS] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 1, 0x00, 2, 0x11, 3, 0x11, 0x00, 0x3F, 0x00};
-  o.insert(o.end(), sos, sos + MCU_SOS);
+  const uint8_t sos1[MCU_SOS1] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)mcu_gray_id(pfx, pfx_len), 0x00, 0x00, 0x3F, 0x00};
+  if (f.gray)
+    o.insert(o.end(), sos1, sos1 + MCU_SOS1);
+  else
+    o.insert(o.end(), sos, sos + MCU_SOS);
   uint64_t acc = 0;
   int nacc = 0;
   auto put = [&](uint32_t v, int n) {

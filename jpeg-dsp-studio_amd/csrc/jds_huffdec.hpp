@@ -836,6 +836,7 @@ inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, c
   bool qdef[4] = {false, false, false, false};
   bool sof = false, seen[4] = {false, false, false, false};
   int ri = 0;
+  int ncomp = 3, gray_id = 0;  // a one-component frame: its component id as written (the SOS must name it)
   int64_t p = 2;
   for (;;) {
     if (p + 2 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated file: EOI missing");
@@ -864,10 +865,30 @@ inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, c
       out->H = (s[1] << 8) | s[2];
       out->W = (s[3] << 8) | s[4];
       const int nf = s[5];
-      if (nf == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "grayscale files (one component) are not supported");
-      if (nf != 3) return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (three are supported)", nf);
+      if (nf != 1 && nf != 3) return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (one or three are supported)", nf);
       if (sl != 6 + 3 * nf) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 length does not match its component count");
       if (out->H < 1 || out->W < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
+      if (nf == 1) {
+        // grayscale: any component id; the sampling byte is checked and then ignored, since a
+        // one-component scan is never interleaved and holds ceil(W/8) x ceil(H/8) blocks (T.81 A.2.2)
+        const int h1 = s[7] >> 4, v1 = s[7] & 15;
+        if (h1 < 1 || h1 > 4 || v1 < 1 || v1 > 4)
+          return hd_fail(msg, cap, JDS_EINVAL, "sampling factors %dx%d (1..4 each)", h1, v1);
+        if (s[8] > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", s[8]);
+        ncomp = 1;
+        gray_id = s[6];
+        out->subsampling = JDS_SS_GRAY;
+        out->tq[0] = s[8];
+        out->hs[0] = out->vs[0] = 1;
+        out->grid_cols[0] = out->mcu_cols = (out->W + 7) / 8;
+        out->grid_rows[0] = out->mcu_rows = (out->H + 7) / 8;
+        out->coeffs_needed = 64 * out->grid_cols[0] * out->grid_rows[0];
+        out->single_table = 1;
+        out->blocks_per_mcu = 1;
+        sof = true;
+        p += 2 + ln;
+        continue;
+      }
       for (int c = 0; c < 3; ++c)
         if (s[6 + 3 * c] != c + 1) return hd_fail(msg, cap, JDS_ENOTSUP, "component ids other than 1, 2, 3");
       const int ys = s[7];
@@ -938,6 +959,10 @@ inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, c
       if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
       if (sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
       const int ns = s[0];
+      if (ncomp == 1 && ns != 1)
+        return hd_fail(msg, cap, JDS_EINVAL, "scan of %d components in a grayscale (one-component) frame", ns);
+      if (ncomp == 1 && out->n_scans)
+        return hd_fail(msg, cap, JDS_ENOTSUP, "a second scan in a grayscale (one-component) file");
       if (ns == 2)
         return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan of two components (Ns = 2): one scan of three or three of one only");
       if (ns != 1 && ns != 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS with %d components", ns);
@@ -948,7 +973,13 @@ inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, c
       jds_jpeg_scan* sc = &out->scan[out->n_scans];
       memset(sc, 0, sizeof *sc);
       for (int i = 0; i < ns; ++i) {
-        const int comp = s[1 + 2 * i], td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
+        int comp = s[1 + 2 * i];
+        const int td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
+        if (ncomp == 1) {
+          if (comp != gray_id)
+            return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d, the grayscale frame's component is %d", comp, gray_id);
+          comp = 1;  // (the info counts components from 1; the file's own id stays in its header)
+        }
         if (comp < 1 || comp > 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d", comp);
         if (ns == 3 && comp != i + 1)
           return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan whose components are not 1, 2, 3 in that order");
@@ -1009,9 +1040,9 @@ inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, c
     p += 2 + ln;
   }
   if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
-  if (out->n_scans != (out->interleaved ? 1 : 3))
+  if (out->n_scans != (out->interleaved || ncomp == 1 ? 1 : 3))
     return hd_fail(msg, cap, JDS_EINVAL, "%d scans (one interleaved scan or one per component expected)", out->n_scans);
-  for (int c = 0; c < 3; ++c)
+  for (int c = 0; c < ncomp; ++c)
     for (int k = 0; k < 64; ++k) out->qtable[c][HD_ZZ[k]] = (double)qt[out->tq[c]][k];
   return JDS_OK;
 }

@@ -17,6 +17,8 @@ namespace jds {
 static_assert(sizeof(JShared<JDS_SS_422>) <= 80 * 1024 && sizeof(JShared<JDS_SS_420>) <= 80 * 1024 &&
                   sizeof(JShared<JDS_SS_444>) <= 80 * 1024,
               "two workgroups per CU");
+// grayscale: the transpose buffer and one table, four workgroups per CU
+static_assert(sizeof(JShared<JDS_SS_GRAY>) <= 40 * 1024, "four workgroups per CU");
 
 // One workgroup per tile, eight lanes per block (lane v: column v, then row v).
 // A block's two passes run on 8 lanes of one wave, whose LDS operations execute
@@ -73,6 +75,38 @@ __device__ __forceinline__ void jinv_tile_dev(JShared<SS>& sh, const JInvArgs& a
   jinv_colour_store(Yv, Cb, Cr, rgb + ((size_t)y * a.W + x0) * 3, nx);
 }
 
+// Grayscale: the tile's luma blocks and nothing else -- no window, no taps, no
+// workgroup barrier beyond the one behind the table load.  Planes 1 and 2 do
+// not exist and are never indexed (a.off[1..2], a.gr/gc[1..2] are zero and
+// unread; component 0's plane starts at the coefficient base).  LDS: 37120 B
+// (transpose buffer + 64 table entries), so four workgroups of 512 lanes share
+// a CU's 160 KB.  The compiler reports 36 VGPRs for k_jpeg_inv<JDS_SS_GRAY> and
+// 50 for k_jpeg_inv_batch<JDS_SS_GRAY> on gfx950: 8 waves per SIMD either way,
+// i.e. the same four workgroups (a workgroup is 8 waves, two per SIMD).  LDS is
+// the limit, not registers; no register cap is set.
+template <>
+__device__ __forceinline__ void jinv_tile_dev<JDS_SS_GRAY>(JShared<JDS_SS_GRAY>& sh, const JInvArgs& a, const int tile,
+                                                           const int16_t* __restrict__ coeffs,
+                                                           uint8_t* __restrict__ rgb) {
+  const int tid = threadIdx.x, v = tid & 7, lb = tid >> 3;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const JWin w = jinv_tile_window<JDS_SS_GRAY>(a, ty, tx);
+  if (tid < 64) sh.q[tid] = a.q[0][tid];
+  __syncthreads();
+  int by, bx;
+  if (!jinv_luma_block(a, w, lb, &by, &bx)) return;  // (no barrier follows)
+  double* mid = sh.mid + lb * JI_MS;
+  const long long boff = ((long long)by * a.gc[0] + bx) * 64;
+  const int y = by * 8 + v, x0 = bx * 8;
+  double Yv[8];
+  jinv_col(coeffs + boff, sh.q, v, mid);
+  __builtin_amdgcn_wave_barrier();
+  jinv_row(mid, v, Yv);
+  if (y > w.y1) return;
+  const int nx = w.x1 + 1 - x0 < 8 ? w.x1 + 1 - x0 : 8;
+  jinv_gray_store(Yv, rgb + ((size_t)y * a.W + x0) * 3, nx);
+}
+
 template <int SS>
 __global__ void __launch_bounds__(JI_NT)
 k_jpeg_inv(const JInvArgs a, const int16_t* __restrict__ coeffs, uint8_t* __restrict__ rgb) {
@@ -116,7 +150,8 @@ void jpeg_inv_constants(int* th, int* tw) {
 }
 
 bool jpeg_inv_fits(const JInvArgs& a) {
-  return a.ss == JDS_SS_420 ? jinv_windows_fit<JDS_SS_420>(a)
+  return a.ss == JDS_SS_GRAY  ? true  // (no window)
+         : a.ss == JDS_SS_420 ? jinv_windows_fit<JDS_SS_420>(a)
          : a.ss == JDS_SS_422 ? jinv_windows_fit<JDS_SS_422>(a)
                               : jinv_windows_fit<JDS_SS_444>(a);
 }
@@ -124,7 +159,9 @@ bool jpeg_inv_fits(const JInvArgs& a) {
 // One launch on s; nothing is uploaded or read back.
 hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s) {
   const dim3 grid((unsigned)(a.tiles_y * a.tiles_x)), block(JI_NT);
-  if (a.ss == JDS_SS_420)
+  if (a.ss == JDS_SS_GRAY)
+    k_jpeg_inv<JDS_SS_GRAY><<<grid, block, 0, s>>>(a, coeffs, rgb);
+  else if (a.ss == JDS_SS_420)
     k_jpeg_inv<JDS_SS_420><<<grid, block, 0, s>>>(a, coeffs, rgb);
   else if (a.ss == JDS_SS_422)
     k_jpeg_inv<JDS_SS_422><<<grid, block, 0, s>>>(a, coeffs, rgb);
@@ -134,18 +171,20 @@ hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rg
   return hipGetLastError();
 }
 
-// The batch: one launch per mode present.  maps: the three modes' maps one
+// The batch: one launch per mode present.  maps: the four modes' maps one
 // after another in device memory (map_off[m]: a mode's first entry; nmap[m]
 // images, tiles[m] tiles).
-hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[3], const int nmap[3],
-                                 const int tiles[3], const uint32_t* status, const int16_t* coeffs, uint8_t* rgb,
-                                 hipStream_t s) {
+hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
+                                 const int nmap[JI_MODES], const int tiles[JI_MODES], const uint32_t* status,
+                                 const int16_t* coeffs, uint8_t* rgb, hipStream_t s) {
   const dim3 block(JI_NT);
-  for (int m = 0; m < 3; ++m) {
+  for (int m = 0; m < JI_MODES; ++m) {
     if (nmap[m] < 1) continue;
     const dim3 grid((unsigned)tiles[m]);
     const JInvMap* mp = maps + map_off[m];
-    if (m == JDS_SS_420)
+    if (m == JDS_SS_GRAY)
+      k_jpeg_inv_batch<JDS_SS_GRAY><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
+    else if (m == JDS_SS_420)
       k_jpeg_inv_batch<JDS_SS_420><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
     else if (m == JDS_SS_422)
       k_jpeg_inv_batch<JDS_SS_422><<<grid, block, 0, s>>>(recs, mp, nmap[m], status, coeffs, rgb);
@@ -159,7 +198,9 @@ hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const
 }
 
 void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb) {
-  if (a.ss == JDS_SS_420)
+  if (a.ss == JDS_SS_GRAY)
+    jinv_host_image<JDS_SS_GRAY>(a, coeffs, rgb);
+  else if (a.ss == JDS_SS_420)
     jinv_host_image<JDS_SS_420>(a, coeffs, rgb);
   else if (a.ss == JDS_SS_422)
     jinv_host_image<JDS_SS_422>(a, coeffs, rgb);

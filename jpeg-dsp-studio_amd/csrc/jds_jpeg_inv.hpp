@@ -62,11 +62,21 @@ struct JInvCfg {
   static constexpr int CWN = SX == 2 ? CWR * CWS : 1;  // 4:4:4 has no window
 };
 
+// Grayscale (one component, DESIGN.md "Grayscale files"): no chroma at all, so
+// no window on either axis; the tile core below has a path of its own
+// (jinv_gray_*), which never touches planes 1 and 2.
+template <>
+struct JInvCfg<JDS_SS_GRAY> {
+  static constexpr int SY = 1, SX = 1;
+  static constexpr int CWR = JI_TH, CWC = JI_CAP_COLS2, CWS = CWC + 3, CWN = 0;
+};
+constexpr int JI_MODES = 4;  // JDS_SS_444, _422, _420, _GRAY: one batch launch per mode present
+
 // What a launch needs: passed by value as the kernel argument (no upload).
 struct JInvArgs {
   int H, W, ss;
-  int gr[3], gc[3];     // T.81 block grid per component (rows, columns)
-  int ph, pw;           // chroma plane: ceil(H * Vc / Vmax) x ceil(W * Hc / Hmax)
+  int gr[3], gc[3];     // T.81 block grid per component (rows, columns); grayscale: zero for 1 and 2
+  int ph, pw;           // chroma plane: ceil(H * Vc / Vmax) x ceil(W * Hc / Hmax); grayscale: 0 x 0
   int tiles_y, tiles_x;
   long long off[3];     // component offsets in the coefficient array
   double sy, sx;        // cv2's scale 1.0 / (dst / src) per axis
@@ -165,8 +175,26 @@ inline int jinv_args(const jds_jpeg_info* info, JInvArgs* a) {
   memset(a, 0, sizeof *a);
   const int ss = info->subsampling;
   if (info->H < 1 || info->W < 1 || info->H * info->W > (int64_t)1 << 28 || info->H > 0x7fffffff ||
-      info->W > 0x7fffffff || (ss != JDS_SS_444 && ss != JDS_SS_422 && ss != JDS_SS_420))
+      info->W > 0x7fffffff || (ss != JDS_SS_444 && ss != JDS_SS_422 && ss != JDS_SS_420 && ss != JDS_SS_GRAY))
     return -1000;
+  if (ss == JDS_SS_GRAY) {  // component 0 alone: the rest of the info is not read and the record keeps zeros
+    a->H = (int)info->H;
+    a->W = (int)info->W;
+    a->ss = ss;
+    a->gr[0] = (a->H + 7) / 8;
+    a->gc[0] = (a->W + 7) / 8;
+    if (info->grid_rows[0] != a->gr[0] || info->grid_cols[0] != a->gc[0]) return -1000;
+    for (int i = 0; i < 64; ++i) {
+      const double q = info->qtable[0][i];
+      if (!(q >= 1.0 && q <= 255.0) || q != (double)(int)q) return -(1 + i);
+      a->q[0][i] = (int)q;
+    }
+    if (info->coeffs_needed != 64ll * a->gr[0] * a->gc[0]) return -1000;
+    a->sy = a->sx = 1.0;
+    a->tiles_y = (a->H + JI_TH - 1) / JI_TH;
+    a->tiles_x = (a->W + JI_TW - 1) / JI_TW;
+    return 0;
+  }
   const int vmax = ss == JDS_SS_420 ? 2 : 1, hmax = ss == JDS_SS_444 ? 1 : 2;
   a->H = (int)info->H;
   a->W = (int)info->W;
@@ -203,6 +231,13 @@ struct JShared {
   int q[3 * 64];
   int xi0[JI_TW], xi1[JI_TW];  // column taps of the tile's pixels, relative to the window
   float xf[JI_TW];
+};
+
+// Grayscale: the transpose buffer and one table (36.25 KB).
+template <>
+struct JShared<JDS_SS_GRAY> {
+  double mid[JI_NB * JI_MS];
+  int q[64];
 };
 
 // jds_inv_common.hpp's tslot: the 16-B pair c/2 of row r sits at pair
@@ -358,6 +393,48 @@ JDS_HDI void jinv_colour_store(const double (&Yv)[8], const double (&Cb)[8], con
   }
 }
 
+// Grayscale: (Y, Y, Y) per pixel in jinv_colour_store's packing.  With
+// Cb = Cr = 128 its expressions are Y + c * 0.0 = Y exactly and Y is already
+// clipped (jinv_row), so the byte is the truncated sample in all three channels.
+JDS_HDI void jinv_gray_store(const double (&Yv)[8], uint8_t* o, int nx) {
+  uint32_t pk[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t y = (uint32_t)(int)Yv[k];
+    for (int b = 3 * k; b < 3 * k + 3; ++b) pk[b >> 2] |= y << (8 * (b & 3));
+  }
+  if (nx == 8 && (((uintptr_t)o) & 7u) == 0) {
+    uint8_t* o8 = (uint8_t*)__builtin_assume_aligned(o, 8);
+    for (int i = 0; i < 3; ++i) {
+      const uint64_t v = (uint64_t)pk[2 * i] | ((uint64_t)pk[2 * i + 1] << 32);
+      __builtin_memcpy(o8 + 8 * i, &v, 8);
+    }
+  } else {
+    for (int b = 0; b < 24; ++b)
+      if (b < 3 * nx) o[b] = (uint8_t)(pk[b >> 2] >> (8 * (b & 3)));
+  }
+}
+
+// A grayscale tile on the host: its luma blocks and nothing else.
+inline void jinv_host_tile_gray(JShared<JDS_SS_GRAY>& sh, const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, int ty,
+                                int tx) {
+  const JWin w = jinv_tile_window<JDS_SS_GRAY>(a, ty, tx);
+  for (int lb = 0; lb < JI_NB; ++lb) {
+    int by, bx;
+    if (!jinv_luma_block(a, w, lb, &by, &bx)) continue;
+    double* mid = sh.mid + lb * JI_MS;
+    const long long boff = ((long long)by * a.gc[0] + bx) * 64;
+    double Yv[8];
+    for (int v = 0; v < 8; ++v) jinv_col(coeffs + boff, sh.q, v, mid);
+    for (int u = 0; u < 8; ++u) {
+      const int y = by * 8 + u, x0 = bx * 8;
+      if (y > w.y1) continue;
+      jinv_row(mid, u, Yv);
+      const int nx = w.x1 + 1 - x0 < 8 ? w.x1 + 1 - x0 : 8;
+      jinv_gray_store(Yv, rgb + ((size_t)y * a.W + x0) * 3, nx);
+    }
+  }
+}
+
 // One tile on the host: the kernel's steps with loops in place of lanes and of
 // the barriers between them.  sh.q holds the image's tables.  No GPU.
 template <int SS>
@@ -407,6 +484,15 @@ inline void jinv_host_image(const JInvArgs& a, const int16_t* coeffs, uint8_t* r
     for (int i = 0; i < 64; ++i) shp->q[64 * c + i] = a.q[c][i];
   for (int ty = 0; ty < a.tiles_y; ++ty)
     for (int tx = 0; tx < a.tiles_x; ++tx) jinv_host_tile<SS>(*shp, a, coeffs, rgb, ty, tx);
+  delete shp;
+}
+
+template <>
+inline void jinv_host_image<JDS_SS_GRAY>(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb) {
+  JShared<JDS_SS_GRAY>* shp = new JShared<JDS_SS_GRAY>();
+  for (int i = 0; i < 64; ++i) shp->q[i] = a.q[0][i];
+  for (int ty = 0; ty < a.tiles_y; ++ty)
+    for (int tx = 0; tx < a.tiles_x; ++tx) jinv_host_tile_gray(*shp, a, coeffs, rgb, ty, tx);
   delete shp;
 }
 
@@ -480,33 +566,39 @@ inline void jinv_host_batch_mode(const JInvRec* recs, const JInvMap* map, int nm
       for (int y = w.Y0; y <= w.y1; ++y) memset(o + ((size_t)y * a.W + w.X0) * 3, 0, 3 * (size_t)(w.x1 - w.X0 + 1));
       continue;
     }
-    for (int c = 0; c < 3; ++c)
-      for (int i = 0; i < 64; ++i) shp->q[64 * c + i] = a.q[c][i];
-    jinv_host_tile<SS>(*shp, a, coeffs + r.coef_off, o, ty, tx);
+    if constexpr (SS == JDS_SS_GRAY) {
+      for (int i = 0; i < 64; ++i) shp->q[i] = a.q[0][i];
+      jinv_host_tile_gray(*shp, a, coeffs + r.coef_off, o, ty, tx);
+    } else {
+      for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < 64; ++i) shp->q[64 * c + i] = a.q[c][i];
+      jinv_host_tile<SS>(*shp, a, coeffs + r.coef_off, o, ty, tx);
+    }
   }
   delete shp;
 }
 
-// map[m] / nmap[m]: the launch of subsampling code m (JDS_SS_444, _422, _420 = 0, 1, 2).
-inline void jpeg_inv_batch_host(const JInvRec* recs, const JInvMap* const map[3], const int nmap[3],
+// map[m] / nmap[m]: the launch of subsampling code m (JDS_SS_444, _422, _420, _GRAY = 0, 1, 2, 3).
+inline void jpeg_inv_batch_host(const JInvRec* recs, const JInvMap* const map[JI_MODES], const int nmap[JI_MODES],
                                 const uint32_t* status, const int16_t* coeffs, uint8_t* rgb) {
   jinv_host_batch_mode<JDS_SS_444>(recs, map[JDS_SS_444], nmap[JDS_SS_444], status, coeffs, rgb);
   jinv_host_batch_mode<JDS_SS_422>(recs, map[JDS_SS_422], nmap[JDS_SS_422], status, coeffs, rgb);
   jinv_host_batch_mode<JDS_SS_420>(recs, map[JDS_SS_420], nmap[JDS_SS_420], status, coeffs, rgb);
+  jinv_host_batch_mode<JDS_SS_GRAY>(recs, map[JDS_SS_GRAY], nmap[JDS_SS_GRAY], status, coeffs, rgb);
 }
 
 // The maps of a batch from its records (in batch order).  false: a mode's tiles
 // exceed what a grid and a 32-bit tile index take.
-inline bool jinv_batch_maps(const JInvRec* recs, int nrec, std::vector<JInvMap> (&map)[3]) {
-  long long tiles[3] = {0, 0, 0};
-  for (int m = 0; m < 3; ++m) map[m].clear();
+inline bool jinv_batch_maps(const JInvRec* recs, int nrec, std::vector<JInvMap> (&map)[JI_MODES]) {
+  long long tiles[JI_MODES] = {0, 0, 0, 0};
+  for (int m = 0; m < JI_MODES; ++m) map[m].clear();
   for (int i = 0; i < nrec; ++i) {
     const int m = recs[i].a.ss;
     map[m].push_back(JInvMap{(int)tiles[m], i});
     tiles[m] += (long long)recs[i].a.tiles_y * recs[i].a.tiles_x;
     if (tiles[m] > 0x7fffffffll) return false;
   }
-  for (int m = 0; m < 3; ++m) map[m].push_back(JInvMap{(int)tiles[m], -1});
+  for (int m = 0; m < JI_MODES; ++m) map[m].push_back(JInvMap{(int)tiles[m], -1});
   return true;
 }
 

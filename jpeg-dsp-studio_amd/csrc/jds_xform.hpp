@@ -169,7 +169,10 @@ inline int xf_plan(const jds_jpeg_info* info, int op, bool trim, XfPlan* p, char
   d.W = (flags & XF_T) ? cH : cW;
   McuFile cf, df;
   d.coeffs_needed = 0;
-  for (int c = 0; c < 3; ++c) {  // the T.81 grids of both sizes
+  // a grayscale file: the MCU is one block whatever its sampling byte says (sf.hs = sf.vs = 1), every
+  // operation is allowed, and components 1 and 2 keep empty grids on both sides (no tiles)
+  const int ncomp = info->subsampling == JDS_SS_GRAY ? 1 : 3;
+  for (int c = 0; c < ncomp; ++c) {  // the T.81 grids of both sizes
     const int64_t xcw = c ? (cW + sf.hs - 1) / sf.hs : cW, ych = c ? (cH + sf.vs - 1) / sf.vs : cH;
     const int64_t xdw = c ? (d.W + sf.hs - 1) / sf.hs : d.W, ydh = c ? (d.H + sf.vs - 1) / sf.vs : d.H;
     crop.grid_cols[c] = (xcw + 7) / 8;

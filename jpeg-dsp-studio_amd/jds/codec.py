@@ -96,9 +96,11 @@ def staged_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids
     in raster order of its (rows, cols) grid) with one table per component, through the
     per-stage calls only: dequantise, decode_block, merge and crop to the component's T.81
     plane size, bilinear chroma upsampling unless 4:4:4, YCbCr -> RGB, clip, truncate."""
-    hmax, vmax = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}[mode]
+    hmax, vmax = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2), 'gray': (1, 1)}[mode]
     cf = np.asarray(coeffs, np.int16).reshape(-1, 8, 8)
     planes, b0 = [], 0
+    if mode == 'gray':   # one plane; each channel is its byte (the colour expressions at Cb = Cr = 128 give Y)
+        grids = list(grids)[:1]
     for c, (gr, gc) in enumerate(grids):
         hs, vs = (hmax, vmax) if c == 0 else (1, 1)
         ph, pw = -(-H * vs // vmax), -(-W * hs // hmax)
@@ -106,6 +108,8 @@ def staged_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids
         b0 += gr * gc
         plane = blk.reshape(gr, gc, 8, 8).transpose(0, 2, 1, 3).reshape(8 * gr, 8 * gc)[:ph, :pw]
         planes.append(plane if (ph, pw) == (H, W) else stage_resize(plane, H, W, nearest=False))
+    if mode == 'gray':
+        return np.repeat(np.clip(planes[0], 0, 255).astype(np.uint8)[:, :, None], 3, axis=2)
     rgb = stage_rgb_ycbcr(np.stack(planes, axis=-1), inverse=True)
     return np.clip(rgb, 0, 255).astype(np.uint8)
 
@@ -113,7 +117,8 @@ def staged_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids
 def decompress_jpeg(data, device: int = 0, with_info: bool = False, staged: bool | None = None):
     """A baseline JPEG with one interleaved scan or three non-interleaved ones -> the HxWx3
     uint8 image.  Plan route (jds_decompress_jpeg, as decompress_jfif) when one quantisation
-    table serves all components and the block grids are the reference's; otherwise, or with
+    table serves all components and the block grids are the reference's; otherwise (a grayscale
+    file always), or with
     staged=True, the staged route: entropy.decode_jpeg, then staged_inverse with the file's own
     tables (not a throughput path).  with_info: (image, decode_jpeg's dict plus 'route')."""
     from . import entropy
@@ -149,7 +154,7 @@ def jpeg_inverse_info() -> Tuple[int, int]:
 def _jpeg_info_struct(H: int, W: int, mode: str, qtables, grids) -> _abi.JpegInfo:
     """The fields the fused inverse reads, from parse_jpeg's / decode_jpeg's terms."""
     info = _abi.JpegInfo()
-    info.H, info.W, info.subsampling = int(H), int(W), _abi.MODE_CODES[mode]
+    info.H, info.W, info.subsampling = int(H), int(W), _abi.JPEG_MODE_CODES[mode]
     q = np.ascontiguousarray(qtables, np.float64).reshape(3, 64)
     for c, (gr, gc) in enumerate(grids):
         info.grid_rows[c], info.grid_cols[c] = int(gr), int(gc)

@@ -61,7 +61,7 @@ def encode_jfif(coeffs: np.ndarray, H: int, W: int, mode: str, qtable: np.ndarra
         return out[:n.value].tobytes(), [int(b) for b in bits]
 
 
-_MODE_NAMES = {v: k for k, v in _abi.MODE_CODES.items()}
+_MODE_NAMES = {v: k for k, v in _abi.JPEG_MODE_CODES.items()}
 
 
 def _bytes_arg(data):
@@ -167,6 +167,7 @@ def _jpeg_dict(info: _abi.JpegInfo) -> dict:
                       'ac_tables': list(s.ac_table)[:n], 'restart_interval': int(s.restart_interval),
                       'offset': int(s.offset), 'length': int(s.length)})
     return {'H': int(info.H), 'W': int(info.W), 'mode': _MODE_NAMES[info.subsampling],
+            'components': 1 if info.subsampling == _abi.SS_GRAY else 3,
             'interleaved': bool(info.interleaved), 'reference_grid': bool(info.reference_grid),
             'single_table': bool(info.single_table),
             'qtables': np.ctypeslib.as_array(info.qtable).astype(np.float64).reshape(3, 8, 8),
@@ -178,7 +179,9 @@ def _jpeg_dict(info: _abi.JpegInfo) -> dict:
 
 def parse_jpeg(data) -> dict:
     """jds_jpeg_parse (host only, no GPU): a baseline JPEG with one interleaved scan or three
-    non-interleaved ones, up to three quantisation tables, T.81 block grids.  'grids': (rows,
+    non-interleaved ones, up to three quantisation tables, T.81 block grids; or a grayscale
+    file ('mode': 'gray', 'components': 1: one scan of one component, whose sampling byte is
+    ignored; 'qtables' and 'grids' keep three entries, zero for the absent components).  'grids': (rows,
     columns) of each component's block grid; 'mcu': the MCU grid and the blocks of an
     interleaved MCU; 'reference_grid': the grids are the ones parse_jfif accepts.  ValueError
     naming the feature for anything else."""
@@ -231,7 +234,7 @@ def _grown(call, cap: int) -> bytes:
 def _encode_info(info: dict) -> _abi.JpegInfo:
     """The fields jds_encode_jpeg reads, from parse_jpeg's / decode_jpeg's terms."""
     st = _abi.JpegInfo()
-    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.MODE_CODES[info['mode']]
+    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.JPEG_MODE_CODES[info['mode']]
     q = np.ascontiguousarray(info['qtables'], np.float64).reshape(3, 64)
     tq = info.get('tq', (0, 1, 1) if not info.get('single_table') else (0, 0, 0))
     for c, (gr, gc) in enumerate(info['grids']):
@@ -300,7 +303,7 @@ def coef_transform_dev(coeffs: np.ndarray, info: dict, op: str, trim: bool = Fal
     decode_jpeg's layout (info: 'H', 'W', 'mode', 'grids' of the source) -> the coefficients in the
     destination's layout.  op: an explicit operation."""
     st = _abi.JpegInfo()
-    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.MODE_CODES[info['mode']]
+    st.H, st.W, st.subsampling = int(info['H']), int(info['W']), _abi.JPEG_MODE_CODES[info['mode']]
     for c, (gr, gc) in enumerate(info['grids']):
         st.grid_rows[c], st.grid_cols[c] = int(gr), int(gc)
     cf = np.ascontiguousarray(coeffs, dtype=np.int16).reshape(-1)
@@ -308,14 +311,14 @@ def coef_transform_dev(coeffs: np.ndarray, info: dict, op: str, trim: bool = Fal
     if cf.size != need:
         raise ValueError(f'expected {need} coefficients for these block grids, got {cf.size}')
     # the destination's entries: the T.81 grids of the size after trim (a transposition keeps the count)
-    hs, vs = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}[info['mode']]
+    hs, vs = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2), 'gray': (1, 1)}[info['mode']]
     H, W = int(info['H']), int(info['W'])
     if trim:
         if op in ('hflip', 'rot180', 'transverse', 'rot270'):
             W -= W % (8 * hs)
         if op in ('vflip', 'rot180', 'transverse', 'rot90'):
             H -= H % (8 * vs)
-    n_out = 64 * (-(-H // 8) * -(-W // 8) + 2 * (-(-(-(-H // vs)) // 8) * -(-(-(-W // hs)) // 8)))
+    n_out = 64 * (-(-H // 8) * -(-W // 8) + (0 if info['mode'] == 'gray' else 2) * (-(-(-(-H // vs)) // 8) * -(-(-(-W // hs)) // 8)))
     out = np.empty(need, np.int16)          # (never more blocks than the source has)
     with _abi.lease(device) as ctx:
         check(lib().jds_selftest_coef_transform_dev(ctx.handle, C.byref(st), _abi.xf_code(op, trim), cf.ctypes.data,

@@ -81,7 +81,7 @@ static int run_batch() {
     need[(size_t)k] = info.coeffs_needed;
     jds::jinv_batch_place(recs[(size_t)k], k, info.coeffs_needed, &rgb_bytes, &coef_entries);
   }
-  std::vector<jds::JInvMap> map[3];
+  std::vector<jds::JInvMap> map[jds::JI_MODES];
   if (!jds::jinv_batch_maps(recs.data(), n, map)) return 1;
   int16_t* cf = (int16_t*)malloc(sizeof(int16_t) * (size_t)coef_entries);
   uint8_t* rgb = (uint8_t*)malloc((size_t)rgb_bytes);
@@ -94,8 +94,9 @@ static int run_batch() {
   // two runs over differently pre-filled outputs: they agree where a byte is written, differ where not
   memset(rgb, 0x00, (size_t)rgb_bytes);
   memset(again, 0xFF, (size_t)rgb_bytes);
-  const jds::JInvMap* maps[3] = {map[0].data(), map[1].data(), map[2].data()};
-  const int nmap[3] = {(int)map[0].size() - 1, (int)map[1].size() - 1, (int)map[2].size() - 1};
+  const jds::JInvMap* maps[jds::JI_MODES] = {map[0].data(), map[1].data(), map[2].data(), map[3].data()};
+  const int nmap[jds::JI_MODES] = {(int)map[0].size() - 1, (int)map[1].size() - 1, (int)map[2].size() - 1,
+                                   (int)map[3].size() - 1};
   for (uint8_t* o : {rgb, again}) jds::jpeg_inv_batch_host(recs.data(), maps, nmap, st.data(), cf, o);
   int bad = 0;
   for (int k = 0; k < n && !bad; ++k) {

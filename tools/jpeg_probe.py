@@ -30,7 +30,14 @@ profiles/transcode_probe.json (or --out FILE).
 optimize=True) with 'rot90' for all (1080 is not a multiple of 16: with trim), 'hflip' for all and
 'auto' on these files without EXIF (the plain transcode), and jpeg_batch_transcode beside them in
 the same run; k_coef_xform on its own from the context's launch marks; four outputs of each leg
-compared with the single call.  Writes profiles/transform_probe.json (or --out FILE)."""
+compared with the single call.  Writes profiles/transform_probe.json (or --out FILE).
+--gray N (default 64) instead: the N 1080p pictures of --batch converted to 'L' and saved as
+one-component files, plain and optimize=True, through jpeg_batch_to_rgb(out=tensor),
+jpeg_batch_transcode(optimize=True, out=tensor) and jpeg_batch_transform('rot90', trim, out=tensor);
+beside them, in the same run, the same pictures as 4:2:0 colour files (--batch's set).  Per leg
+and call: the median time, the per-kernel times from the context's launch marks, bytes in and out,
+the rounds; four outputs of each call compared with the single call.  Writes
+profiles/gray_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -335,7 +342,78 @@ def transform_main():
     return 0 if ok else 1
 
 
+def gray_leg(name, files):
+    import torch
+    from jds import _abi
+    n = len(files)
+    ctx = _abi.Context(0)
+    row = {'leg': name, 'n': n, 'input_bytes': int(sum(len(f) for f in files))}
+    ok = True
+    some = range(0, n, max(1, n // 4))
+
+    def marks(fn, reps=5):
+        ctx.profile(True)
+        for _ in range(reps):
+            fn()
+        kern, span = ctx.profile_read()
+        ctx.profile(False)
+        return {'kernels_ms_per_batch': {k: v[0] / reps for k, v in kern.items()},
+                'kernel_launches_per_batch': {k: v[1] / reps for k, v in kern.items()},
+                'marks_span_ms_per_batch': span / reps}
+
+    items, rgb_bytes, _ = codec.jpeg_batch_layout(files)
+    rgb = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    views, info = codec.jpeg_batch_to_rgb(files, out=rgb, with_info=True, ctx=ctx)
+    equal = all(np.array_equal(views[k].cpu().numpy(), codec.jpeg_to_rgb(files[k])) for k in some)
+    ok = ok and equal
+    row['batch_to_rgb'] = dict(timed(lambda: codec.jpeg_batch_to_rgb(files, out=rgb, ctx=ctx)), rounds=info['rounds'],
+                               output_bytes=int(rgb_bytes), equals_single_calls=bool(equal),
+                               **marks(lambda: codec.jpeg_batch_to_rgb(files, out=rgb, ctx=ctx)))
+    calls = [('batch_transcode', lambda **kw: codec.jpeg_batch_transcode(files, optimize=True, ctx=ctx, **kw),
+              lambda f: codec.jpeg_transcode(f, optimize=True)),
+             ('batch_transform_rot90_trim',
+              lambda **kw: codec.jpeg_batch_transform(files, 'rot90', trim=True, optimize=True, ctx=ctx, **kw),
+              lambda f: codec.jpeg_transform(f, 'rot90', trim=True, optimize=True))]
+    for cname, call, single in calls:
+        outs = call()
+        buf = torch.empty(sum(-(-len(o) // 256) * 256 for o in outs), dtype=torch.uint8, device='cuda')
+        equal = [outs[k] for k in some] == [single(files[k]) for k in some]
+        ok = ok and equal
+        row[cname] = dict(timed(lambda: call(out=buf)), output_bytes=int(sum(len(o) for o in outs)),
+                          equals_single_calls=bool(equal), **marks(lambda: call(out=buf)))
+    ctx.close()
+    row['ok'] = bool(ok)
+    return row
+
+
+def gray_main():
+    i = sys.argv.index('--gray')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    pics = [np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8) for k in range(n)]
+
+    def gray_file(img, **kw):
+        buf = io.BytesIO()
+        Image.fromarray(img).convert('L').save(buf, 'JPEG', quality=50, **kw)
+        return buf.getvalue()
+
+    legs = [('pillow_q50_gray_1080p', [gray_file(p) for p in pics]),
+            ('pillow_q50_gray_optimize_1080p', [gray_file(p, optimize=True) for p in pics]),
+            ('pillow_q50_420_1080p', [pillow_file(p) for p in pics])]
+    rows = []
+    for name, files in legs:
+        rows.append(gray_leg(name, files))
+        print(json.dumps(rows[-1]), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'gray_probe.json')
+    with open(out, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r['ok'] for r in rows) else 1
+
+
 def main():
+    if '--gray' in sys.argv:
+        return gray_main()
     if '--transform' in sys.argv:
         return transform_main()
     if '--batch' in sys.argv:
