@@ -640,6 +640,57 @@ int jds_jpeg_batch_to_rgb(jds_ctx* ctx, const uint8_t* const* data, const int64_
 int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
                             uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items);
 
+/* The libjpeg rendering (DESIGN.md "libjpeg rendering"; definition:
+ * tests/libjpeg_ref.py): a second rendering of the same decoded coefficients,
+ * byte for byte what libjpeg (libjpeg-turbo, hence Pillow, OpenCV, torchvision,
+ * browsers) gives with its default settings -- dequantise, the ISLOW integer
+ * IDCT (jidctint), +128, clamp, crop chroma to its T.81 plane, fancy upsampling
+ * (jdsample's h2v1 / h2v2 triangle taps; replication when the chroma plane is at
+ * most two samples wide), jdcolor's 16-bit fixed-point YCbCr -> RGB, clamp.
+ * `render` selects: JDS_RENDER_REFERENCE is the rendering above (k_jpeg_inv),
+ * and each _render call with it does exactly what its namesake without the
+ * argument does; JDS_RENDER_LIBJPEG runs k_jpeg_ljt / k_jpeg_ljt_batch.  Any
+ * other value is JDS_EINVAL ("unknown render ...").
+ *
+ * Scope: parity with libjpeg is stated for files it decodes as YCbCr (JFIF, or
+ *   no Adobe marker with ordinary component ids) or as grayscale, and for its
+ *   default settings only (ISLOW, fancy upsampling, no scaling, no block
+ *   smoothing).  A file libjpeg would take as RGB (Adobe transform 0, or ids
+ *   'R', 'G', 'B') is still treated as YCbCr here, as by every other call.
+ *   jds_decompress_jpeg, the transcode and the transforms have no rendering
+ *   argument.
+ * Arithmetic: 32-bit two's complement with wrap-around at every operation.
+ *   While every dequantised coefficient (coefficient x table entry) of a block
+ *   is within +-1173, or their absolute values sum to at most 14107 over the
+ *   block, no intermediate leaves 31 bits (DESIGN.md derives both bounds; blocks
+ *   coded from 8-bit samples are of the first kind) and the result is that of
+ *   libjpeg-turbo's SIMD decode, which saturates its output as this core does.
+ *   libjpeg's C inverse indexes a range table with x & 1023 instead: it gives
+ *   the same bytes only where the unclamped sample lies in about [-384, 639].
+ *   Beyond the bounds the result is defined -- kernel, host core and
+ *   tests/libjpeg_ref.py agree on every int16 input -- but need not be any
+ *   libjpeg's.
+ *
+ * jds_jpeg_render_dev: jds_jpeg_inverse_dev's arguments, checks and contract.
+ * jds_jpeg_to_rgb_render, jds_jpeg_batch_to_rgb_render: their namesakes'
+ *   arguments and contracts (a batch: zeros for an image with defective scan
+ *   data, the bytes between images never written).
+ * jds_selftest_jpeg_render, jds_selftest_jpeg_batch_render: test-only, host
+ *   only: the tile core (csrc/jds_jpeg_ljt.hpp) in a host tile loop. */
+#define JDS_RENDER_REFERENCE 0
+#define JDS_RENDER_LIBJPEG 1
+int jds_jpeg_render_dev(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream,
+                        int32_t render);
+int jds_jpeg_to_rgb_render(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                           int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render);
+int jds_jpeg_batch_to_rgb_render(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                                 int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                 uint32_t* rounds, int32_t render);
+int jds_selftest_jpeg_render(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out, int32_t render);
+int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                                   uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                   int32_t render);
+
 /* Lossless transcode (DESIGN.md "Transcode"; byte-for-byte definition:
  * tests/transcode_ref.py): the coefficients of jds_decode_jpeg written back as
  * the file form everybody else writes -- ONE interleaved scan (Ns = 3,

@@ -24,6 +24,7 @@
 #include "jds_huffopt.hpp"
 #include "jds_internal.hpp"
 #include "jds_jpeg_inv.hpp"
+#include "jds_jpeg_ljt.hpp"
 #include "jds_xform_dev.hpp"
 
 #ifdef JDS_INV6
@@ -144,6 +145,10 @@ bool jpeg_inv_fits(const JInvArgs& a);
 hipError_t launch_jpeg_inv(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 void jpeg_inv_host(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb);
 hipError_t launch_jpeg_inv_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
+                                 const int nmap[JI_MODES], const int tiles[JI_MODES], const uint32_t* status,
+                                 const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+hipError_t launch_jpeg_ljt(const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+hipError_t launch_jpeg_ljt_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
                                  const int nmap[JI_MODES], const int tiles[JI_MODES], const uint32_t* status,
                                  const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 }
@@ -2167,6 +2172,14 @@ int jds_jpeg_inverse_info(int32_t* tile_h, int32_t* tile_w) {
   return JDS_OK;
 }
 
+// The rendering a _render call names: JDS_RENDER_REFERENCE (k_jpeg_inv) or
+// JDS_RENDER_LIBJPEG (k_jpeg_ljt); anything else is the caller's error.
+static int render_check(int32_t render) {
+  if (render != JDS_RENDER_REFERENCE && render != JDS_RENDER_LIBJPEG)
+    return fail(JDS_EINVAL, "unknown render %d (JDS_RENDER_REFERENCE or JDS_RENDER_LIBJPEG)", (int)render);
+  return JDS_OK;
+}
+
 // The launch arguments of a parsed file: its tables by check_tables' rule, its
 // grids T.81's for H x W, every tile's chroma window within the kernel's arrays.
 static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
@@ -2184,21 +2197,38 @@ static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
   return JDS_OK;
 }
 
-int jds_jpeg_inverse_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream) {
+static hipError_t launch_render(int32_t render, const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s) {
+  return render == JDS_RENDER_LIBJPEG ? launch_jpeg_ljt(a, coeffs, rgb, s) : launch_jpeg_inv(a, coeffs, rgb, s);
+}
+
+int jds_jpeg_render_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream,
+                        int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
   if (!info) return fail(JDS_EINVAL, "null argument");
   JInvArgs a;
-  int rc;
   if ((rc = jpeg_inv_args(info, &a))) return rc;
   if (!c || !coeffs || !rgb) return fail(JDS_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(launch_jpeg_inv(a, coeffs, rgb, (hipStream_t)stream));
+  HIP_TRY(launch_render(render, a, coeffs, rgb, (hipStream_t)stream));
   return JDS_OK;
+}
+
+int jds_jpeg_inverse_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream) {
+  return jds_jpeg_render_dev(c, info, coeffs, rgb, stream, JDS_RENDER_REFERENCE);
 }
 
 int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
                     int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info) {
+  return jds_jpeg_to_rgb_render(c, data, len, rgb_out, rgb_cap, rgb_on_device, coeffs, info, JDS_RENDER_REFERENCE);
+}
+
+int jds_jpeg_to_rgb_render(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                           int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
   if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
-  int rc = jds_jpeg_parse(data, len, info);
+  rc = jds_jpeg_parse(data, len, info);
   if (rc) return rc;
   const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
   if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
@@ -2211,7 +2241,7 @@ int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_o
     HIP_TRY(c->out.ensure(nimg));
     dst = (uint8_t*)c->out.p;
   }
-  HIP_TRY(launch_jpeg_inv(a, (const int16_t*)c->ent_cf.p, dst, c->stream));
+  HIP_TRY(launch_render(render, a, (const int16_t*)c->ent_cf.p, dst, c->stream));
   if (!rgb_on_device) HIP_TRY(hipMemcpyAsync(rgb_out, dst, nimg, hipMemcpyDeviceToHost, c->stream));
   if (coeffs)
     HIP_TRY(hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
@@ -2220,13 +2250,21 @@ int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_o
   return JDS_OK;
 }
 
-int jds_selftest_jpeg_inverse(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out) {
+int jds_selftest_jpeg_render(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
   if (!info || !coeffs || !rgb_out) return fail(JDS_EINVAL, "null argument");
   JInvArgs a;
-  const int rc = jpeg_inv_args(info, &a);
-  if (rc) return rc;
-  jpeg_inv_host(a, coeffs, rgb_out);
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  if (render == JDS_RENDER_LIBJPEG)
+    jpeg_ljt_host_image(a, coeffs, rgb_out);
+  else
+    jpeg_inv_host(a, coeffs, rgb_out);
   return JDS_OK;
+}
+
+int jds_selftest_jpeg_inverse(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out) {
+  return jds_selftest_jpeg_render(info, coeffs, rgb_out, JDS_RENDER_REFERENCE);
 }
 
 int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_n, int32_t xaxis, int32_t* out) {
@@ -2341,9 +2379,17 @@ int jds_jpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32
 
 int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
                             uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items) {
+  return jds_selftest_jpeg_batch_render(data, lens, n, subseq_bits, rgb, rgb_cap, coeffs, items, JDS_RENDER_REFERENCE);
+}
+
+int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                                   uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                   int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
   if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
   BatchPlan bp;
-  const int rc = batch_layout(data, lens, n, items, bp);
+  rc = batch_layout(data, lens, n, items, bp);
   if (rc) return rc;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
     return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
@@ -2367,7 +2413,10 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
     maps[m] = bp.map[m].data();
     nmap[m] = (int)bp.map[m].size() - 1;
   }
-  jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  if (render == JDS_RENDER_LIBJPEG)
+    jpeg_ljt_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  else
+    jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
   batch_note(bp);
   return JDS_OK;
 }
@@ -2378,7 +2427,7 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
 // Synchronous.  Without `inverse` (jds_jpeg_batch_transcode) rgb is not used.
 static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
                      int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, uint32_t* rounds_out,
-                     bool inverse) {
+                     bool inverse, int32_t render = JDS_RENDER_REFERENCE) {
   int rc;
   const int nv = (int)bp.recs.size();
   hipStream_t s = c->stream;
@@ -2505,7 +2554,10 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
     return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
   HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivil), (long long)iv_il.size(), tabs_d, cf_d, st_d, s, mcu_d));
   HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivpl), (long long)iv_pl.size(), tabs_d, cf_d, st_d, s, nullptr));
-  if (inverse)
+  if (inverse && render == JDS_RENDER_LIBJPEG)
+    HIP_TRY(launch_jpeg_ljt_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
+                                  st_d, cf_d, dst, s));
+  else if (inverse)
     HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
                                   st_d, cf_d, dst, s));
   if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
@@ -2527,14 +2579,24 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
 int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
                           int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
                           uint32_t* rounds_out) {
+  return jds_jpeg_batch_to_rgb_render(c, data, lens, n, rgb, rgb_cap, rgb_on_device, coeffs, items, rounds_out,
+                                      JDS_RENDER_REFERENCE);
+}
+
+int jds_jpeg_batch_to_rgb_render(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                                 int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                 uint32_t* rounds_out, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
   if (!c) return fail(JDS_EINVAL, "null argument");
   BatchPlan bp;
-  int rc = batch_layout(data, lens, n, items, bp);
+  rc = batch_layout(data, lens, n, items, bp);
   if (rc) return rc;
   if (rounds_out) *rounds_out = 0;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
     return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
-  if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true)))
+  if (!bp.recs.empty() &&
+      (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true, render)))
     return rc;
   batch_note(bp);
   return JDS_OK;

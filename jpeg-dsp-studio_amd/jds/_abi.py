@@ -27,7 +27,15 @@ MODE_CODES = {'4:4:4': SS_444, '4:2:2': SS_422, '4:2:0': SS_420}
 # the calls on foreign files (jds_jpeg_*) know a fourth mode: one-component files
 SS_GRAY = 3
 JPEG_MODE_CODES = dict(MODE_CODES, gray=SS_GRAY)
+RENDER_CODES = {'reference': 0, 'libjpeg': 1}    # JDS_RENDER_*
 RUN_SSE, RUN_FWD, RUN_INV, RUN_EXACT, RUN_EXACT_INV, RUN_INV_FIXALL, RUN_FWD_FIXALL, RUN_INV_FAST = 1, 2, 4, 8, 16, 32, 64, 128
+
+
+def render_code(render) -> int:
+    """'reference' / 'libjpeg' -> JDS_RENDER_*; anything else: ValueError('unknown render ...')."""
+    if not isinstance(render, str) or render not in RENDER_CODES:
+        raise ValueError(f"unknown render {render!r}: 'reference' or 'libjpeg'")
+    return RENDER_CODES[render]
 
 
 class Params(C.Structure):
@@ -212,6 +220,14 @@ _SIGS = {
     'jds_jpeg_batch_to_rgb': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegBatchItem),
                                         C.POINTER(C.c_uint32)]),
     'jds_selftest_jpeg_batch': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.POINTER(JpegBatchItem)]),
+    'jds_jpeg_render_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P, _P, C.c_int32]),
+    'jds_jpeg_to_rgb_render': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegInfo),
+                                         C.c_int32]),
+    'jds_selftest_jpeg_render': (C.c_int, [C.POINTER(JpegInfo), _P, _P, C.c_int32]),
+    'jds_jpeg_batch_to_rgb_render': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P,
+                                               C.POINTER(JpegBatchItem), C.POINTER(C.c_uint32), C.c_int32]),
+    'jds_selftest_jpeg_batch_render': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P,
+                                                 C.POINTER(JpegBatchItem), C.c_int32]),
     'jds_encode_jpeg': (C.c_int, [_P, C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
                                   C.POINTER(C.c_int64)]),
     'jds_jpeg_transcode': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),

@@ -186,14 +186,42 @@ def host_jpeg_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, gr
     return img
 
 
-def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None):
+def jpeg_render_dev(info: dict, coeffs_ptr: int, rgb_ptr: int, render: str = 'libjpeg', stream=None,
+                    device: int = 0) -> None:
+    """jds_jpeg_render_dev: jpeg_inverse_dev with the rendering chosen -- 'reference' (the launch
+    jpeg_inverse_dev makes) or 'libjpeg' (k_jpeg_ljt: libjpeg's default decode byte for byte,
+    DESIGN.md "libjpeg rendering")."""
+    code = _abi.render_code(render)
+    st = _jpeg_info_struct(info['H'], info['W'], info['mode'], info['qtables'], info['grids'])
+    with lease(device) as ctx:
+        check(lib().jds_jpeg_render_dev(ctx.handle, C.byref(st), C.c_void_p(int(coeffs_ptr)),
+                                        C.c_void_p(int(rgb_ptr)), C.c_void_p(int(stream or 0)), code))
+
+
+def host_jpeg_render(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids, render: str = 'libjpeg') -> np.ndarray:
+    """Test aid (jds_selftest_jpeg_render): host_jpeg_inverse with the rendering chosen; 'libjpeg'
+    runs k_jpeg_ljt's tile core in a host tile loop.  No GPU."""
+    code = _abi.render_code(render)
+    st = _jpeg_info_struct(H, W, mode, qtables, grids)
+    cf = np.ascontiguousarray(coeffs, np.int16).reshape(-1)
+    if cf.size != int(st.coeffs_needed):
+        raise ValueError(f'expected {int(st.coeffs_needed)} coefficients, got {cf.size}')
+    img = np.empty((int(H), int(W), 3), np.uint8)
+    check(lib().jds_selftest_jpeg_render(C.byref(st), cf.ctypes.data, img.ctypes.data, code))
+    return img
+
+
+def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render: str = 'reference'):
     """jds_jpeg_to_rgb: any baseline JPEG parse_jpeg accepts -> the HxWx3 uint8 image, by the
     entropy decode and one fused inverse launch (k_jpeg_inv) with the file's own tables and
     grids: byte for byte decompress_jpeg(staged=True)'s image.  out: an object with data_ptr()
     (a contiguous uint8 torch tensor of shape (H, W, 3) on `device`): the image stays on the
     device, written there, and `out` is returned.  with_info: (image, decode_jpeg's dict plus
-    'route': 'fused')."""
+    'route': 'fused').  render='libjpeg': the same decode, rendered by k_jpeg_ljt to the bytes
+    libjpeg's default decode gives (np.asarray(PIL.Image.open(f).convert('RGB')); DESIGN.md
+    "libjpeg rendering")."""
     from . import entropy
+    code = _abi.render_code(render)
     a, p, n = entropy._bytes_arg(data)
     info = _abi.JpegInfo()
     check(lib().jds_jpeg_parse(p, n, C.byref(info)))
@@ -207,8 +235,12 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None):
         img, dst, on_dev = out, int(out.data_ptr()), 1
     cf = np.empty(int(info.coeffs_needed), np.int16) if with_info else None
     with lease(device) as ctx:
-        check(lib().jds_jpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
-                                    cf.ctypes.data if with_info else None, C.byref(info)))
+        if code == 0:
+            check(lib().jds_jpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
+                                        cf.ctypes.data if with_info else None, C.byref(info)))
+        else:
+            check(lib().jds_jpeg_to_rgb_render(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
+                                               cf.ctypes.data if with_info else None, C.byref(info), code))
     if not with_info:
         return img
     d = entropy._jpeg_dict(info)
@@ -261,7 +293,8 @@ def _batch_first_error(items) -> str:
     return ''
 
 
-def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False, errors: str = 'raise', ctx=None):
+def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False, errors: str = 'raise', ctx=None,
+                      render: str = 'reference'):
     """jds_jpeg_batch_to_rgb: a sequence of baseline JPEGs (bytes-likes; any mix of sizes,
     subsampling modes, tables, restart intervals and scan forms) -> their images, decoded in one
     set of launches; each image is byte for byte jpeg_to_rgb's.  out=None: a list of HxWx3 uint8
@@ -271,9 +304,11 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     raises ValueError naming the first such index after the batch has run, errors='return' puts
     None in its place.  with_info: (images, {'items': per-file dicts, 'rounds': the batch's
     propagation rounds, 'rgb_bytes', 'coef_entries'}).  ctx: a caller-owned Context of that device
-    (e.g. a profiled one) instead of a pooled one."""
+    (e.g. a profiled one) instead of a pooled one.  render='libjpeg': every image rendered as
+    jpeg_to_rgb(render='libjpeg') does (k_jpeg_ljt_batch), the same layout and error contract."""
     if errors not in ('raise', 'return'):
         raise ValueError("errors must be 'raise' or 'return'")
+    code = _abi.render_code(render)
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
     items = (_abi.JpegBatchItem * max(n, 1))()
@@ -298,13 +333,18 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
             cap = int(buf.numel())
         dst, on_dev = int(buf.data_ptr()), 1
     rounds = C.c_uint32(0)
+
+    def run(c):
+        if code == 0:
+            return lib().jds_jpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
+                                               C.byref(rounds))
+        return lib().jds_jpeg_batch_to_rgb_render(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
+                                                  C.byref(rounds), code)
     if ctx is not None:
-        check(lib().jds_jpeg_batch_to_rgb(ctx.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
-                                          C.byref(rounds)))
+        check(run(ctx))
     else:
         with lease(device) as c:
-            check(lib().jds_jpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
-                                              C.byref(rounds)))
+            check(run(c))
     info = [_batch_item_dict(items[i]) for i in range(n)]
     first = _batch_first_error(info)
     if first and errors == 'raise':
@@ -324,9 +364,11 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
                   'coef_entries': sum(it['coeffs_needed'] for it in ok)}
 
 
-def host_jpeg_batch(files, subseq_bits: int = 1024):
+def host_jpeg_batch(files, subseq_bits: int = 1024, render: str = 'reference'):
     """Test aid (jds_selftest_jpeg_batch): the batch's layout, the host decode model per file and
-    the host model of the batch inverse.  -> (rgb buffer, coefficient buffer, per-file dicts).  No GPU."""
+    the host model of the batch inverse.  -> (rgb buffer, coefficient buffer, per-file dicts).  No GPU.
+    render='libjpeg': jds_selftest_jpeg_batch_render with k_jpeg_ljt_batch's host model."""
+    code = _abi.render_code(render)
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
     items = (_abi.JpegBatchItem * max(n, 1))()
@@ -334,8 +376,12 @@ def host_jpeg_batch(files, subseq_bits: int = 1024):
     check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
     rgb = np.full(max(int(rb.value), 1), 0xA5, np.uint8)
     cf = np.zeros(max(int(ce.value), 1), np.int16)
-    check(lib().jds_selftest_jpeg_batch(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
-                                        cf.ctypes.data, items))
+    if code == 0:
+        check(lib().jds_selftest_jpeg_batch(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
+                                            cf.ctypes.data, items))
+    else:
+        check(lib().jds_selftest_jpeg_batch_render(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
+                                                   cf.ctypes.data, items, code))
     return rgb[:int(rb.value)], cf[:int(ce.value)], [_batch_item_dict(items[i]) for i in range(n)]
 
 

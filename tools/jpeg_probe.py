@@ -37,7 +37,9 @@ jpeg_batch_transcode(optimize=True, out=tensor) and jpeg_batch_transform('rot90'
 beside them, in the same run, the same pictures as 4:2:0 colour files (--batch's set).  Per leg
 and call: the median time, the per-kernel times from the context's launch marks, bytes in and out,
 the rounds; four outputs of each call compared with the single call.  Writes
-profiles/gray_probe.json (or --out FILE)."""
+profiles/gray_probe.json (or --out FILE).
+--render N (default 64) instead: the two renderings ('reference', 'libjpeg') side by side, see
+render_main.  Writes profiles/jpeg_render_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -411,7 +413,172 @@ def gray_main():
     return 0 if all(r['ok'] for r in rows) else 1
 
 
+def render_kernel_us(d, reps, KB=20):
+    """Both inverse kernels on the same coefficients by events around KB back-to-back launches
+    (rgb_leg's method), the two renderings alternating rep by rep.  -> {render: (median, min)}."""
+    import ctypes as C
+    import torch
+    from jds import _abi
+    h, w = d['H'], d['W']
+    st = codec._jpeg_info_struct(h, w, d['mode'], d['qtables'], d['grids'])
+    cf = torch.from_numpy(d['coeffs']).cuda()
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device='cuda')
+    fill = torch.empty(1 << 30, dtype=torch.uint8, device='cuda')
+    s = torch.cuda.current_stream()
+    us = {0: [], 1: []}
+    with _abi.lease(0) as ctx:
+        for i in range(3 + reps):
+            for code in (0, 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                for _ in range(12):
+                    fill.fill_(i)
+                e0.record(s)
+                for _ in range(KB):
+                    _abi.check(_abi.lib().jds_jpeg_render_dev(ctx.handle, C.byref(st), C.c_void_p(cf.data_ptr()),
+                                                              C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream), code))
+                e1.record(s)
+                e1.synchronize()
+                if i >= 3:
+                    us[code].append(e0.elapsed_time(e1) * 1e3 / KB)
+    return {name: (sorted(us[c])[len(us[c]) // 2], min(us[c])) for name, c in (('reference', 0), ('libjpeg', 1))}
+
+
+def render_single_leg(name, data, reps):
+    import torch
+    d = entropy.decode_jpeg(data)
+    h, w = d['H'], d['W']
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device='cuda')
+    ref = codec.jpeg_to_rgb(data)
+    lj = codec.jpeg_to_rgb(data, render='libjpeg')
+    pil = np.asarray(Image.open(io.BytesIO(bytes(data))).convert('RGB'))
+    t = {'reference': [], 'libjpeg': []}
+    for i in range(3 + reps):                               # alternating, whole calls by the host clock
+        for r in t:
+            t0 = time.perf_counter()
+            codec.jpeg_to_rgb(data, out=out, render=r)
+            if i >= 3:
+                t[r].append((time.perf_counter() - t0) * 1e3)
+    k = render_kernel_us(d, reps)
+    diff = ref.astype(np.int16) - lj
+    return {'leg': name, 'H': h, 'W': w, 'mode': d['mode'], 'file_bytes': int(len(data)), 'reps': reps,
+            'jpeg_to_rgb_device_ms': {r: {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v)} for r, v in t.items()},
+            'kernel_us_events': {'k_jpeg_inv': {'median': k['reference'][0], 'min': k['reference'][1]},
+                                 'k_jpeg_ljt': {'median': k['libjpeg'][0], 'min': k['libjpeg'][1]}},
+            'libjpeg_equals_pillow': bool(np.array_equal(lj, pil)),
+            'bytes_differing_between_renderings': int((diff != 0).sum()), 'bytes_total': int(diff.size),
+            'largest_difference': int(np.abs(diff).max())}
+
+
+def render_order_leg(name, data, reps=40):
+    """Does a difference between the renderings in whole calls follow the rendering or the call's
+    place?  jpeg_to_rgb(out=tensor) by the host clock: alternating pairs in both orders, then
+    blocks of `reps` calls of one rendering, twice.  Medians, ms."""
+    import torch
+    info = entropy.parse_jpeg(data)
+    out = torch.empty((info['H'], info['W'], 3), dtype=torch.uint8, device='cuda')
+
+    def one(r):
+        t0 = time.perf_counter()
+        codec.jpeg_to_rgb(data, out=out, render=r)
+        return (time.perf_counter() - t0) * 1e3
+
+    def med(v):
+        return sorted(v)[len(v) // 2]
+    for r in ('reference', 'libjpeg'):
+        for _ in range(5):
+            one(r)
+    row = {'leg': name, 'reps': reps, 'libjpeg_equals_pillow': True}
+    for key, order in (('alternating_reference_first', ('reference', 'libjpeg')),
+                       ('alternating_libjpeg_first', ('libjpeg', 'reference'))):
+        t = {'reference': [], 'libjpeg': []}
+        for _ in range(reps):
+            for r in order:
+                t[r].append(one(r))
+        row[key] = {r: med(v) for r, v in t.items()}
+    row['blocks'] = {'reference': [], 'libjpeg': []}
+    for _ in range(2):
+        for r in ('reference', 'libjpeg'):
+            row['blocks'][r].append(med([one(r) for _ in range(reps)]))
+    return row
+
+
+def render_batch_leg(name, files):
+    import torch
+    from jds import _abi
+    n = len(files)
+    items, rgb_bytes, _ = codec.jpeg_batch_layout(files)
+    out = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    ctx = _abi.Context(0)
+    row = {'leg': name, 'n': n, 'file_bytes_total': int(sum(len(f) for f in files))}
+    views = codec.jpeg_batch_to_rgb(files, out=out, ctx=ctx, render='libjpeg')
+    some = range(0, n, max(1, n // 4))
+    row['libjpeg_equals_pillow'] = all(
+        np.array_equal(views[k].cpu().numpy(), np.asarray(Image.open(io.BytesIO(files[k])).convert('RGB'))) for k in some)
+    t = {'reference': [], 'libjpeg': []}
+    for i in range(2 + 10):
+        for r in t:
+            t0 = time.perf_counter()
+            codec.jpeg_batch_to_rgb(files, out=out, ctx=ctx, render=r)
+            if i >= 2:
+                t[r].append((time.perf_counter() - t0) * 1e3)
+    row['jpeg_batch_to_rgb_device_ms'] = {r: {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v)}
+                                          for r, v in t.items()}
+    ctx.profile(True)
+    reps = 5
+    for _ in range(reps):
+        for r in t:
+            codec.jpeg_batch_to_rgb(files, out=out, ctx=ctx, render=r)
+    kern, _ = ctx.profile_read()
+    ctx.profile(False)
+    ctx.close()
+    row['inverse_kernels_ms_per_batch'] = {k: v[0] / reps for k, v in kern.items()
+                                           if k.startswith('k_jpeg_inv_batch') or k.startswith('k_jpeg_ljt_batch')}
+    return row
+
+
+def render_main():
+    """--render [N]: the two renderings side by side -- per 1080p Pillow Q50 file (4:2:0, 4:2:2,
+    4:4:4, one-component) jpeg_to_rgb(out=tensor) alternating between them, the two inverse kernels
+    by events around back-to-back launches, the bytes that differ; the 4:2:0 picture once more at
+    1080 x 1919 (rows at odd addresses: the byte-store path of both kernels) and in a call-order
+    check (render_order_leg); then N (default 64) 4:2:0 files
+    and N one-component files through jpeg_batch_to_rgb(out=tensor), alternating, with the batch
+    kernels from the context's launch marks.  Writes profiles/jpeg_render_probe.json (or --out FILE)."""
+    i = sys.argv.index('--render')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    reps = int(os.environ.get('REPS', '30'))
+    noise = np.random.default_rng(7).integers(0, 256, (H, W, 3), dtype=np.uint8)
+
+    def gray_file(img):
+        buf = io.BytesIO()
+        Image.fromarray(img).convert('L').save(buf, 'JPEG', quality=50)
+        return buf.getvalue()
+
+    rows = []
+    for name, data in (('pillow_q50_420_1080p', pillow_file(noise)), ('pillow_q50_422_1080p', pillow_file(noise, subsampling=1)),
+                       ('pillow_q50_444_1080p', pillow_file(noise, subsampling=0)), ('pillow_q50_gray_1080p', gray_file(noise))):
+        rows.append(render_single_leg(name, data, reps))
+        print(json.dumps(rows[-1]), flush=True)
+    rows.append(render_single_leg('pillow_q50_420_1080x1919', pillow_file(np.ascontiguousarray(noise[:, :W - 1])), reps))
+    print(json.dumps(rows[-1]), flush=True)
+    rows.append(render_order_leg('call_order_check_pillow_q50_420_1080p', pillow_file(noise)))
+    print(json.dumps(rows[-1]), flush=True)
+    pics = [np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8) for k in range(n)]
+    for name, files in (('batch_pillow_q50_420_1080p', [pillow_file(p) for p in pics]),
+                        ('batch_pillow_q50_gray_1080p', [gray_file(p) for p in pics])):
+        rows.append(render_batch_leg(name, files))
+        print(json.dumps(rows[-1]), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'jpeg_render_probe.json')
+    with open(out, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r['libjpeg_equals_pillow'] for r in rows) else 1
+
+
 def main():
+    if '--render' in sys.argv:
+        return render_main()
     if '--gray' in sys.argv:
         return gray_main()
     if '--transform' in sys.argv:
