@@ -1,0 +1,1236 @@
+// jds_abi_jpeg.hip — the C-ABI's foreign-file half (include/jds.h): parse and
+// decode of files of either scan form, rendering, batches, the lossless
+// transcode and transforms, and their host models (jds_selftest_*).
+//
+// Host side only: descriptors (jds_dec_jobs.hpp), uploads and launches.
+#include <algorithm>
+#include <string>
+
+#include "jds_abi.hpp"
+#include "jds_dec_jobs.hpp"
+#include "jds_entropy_mcu_dev.hpp"
+#include "jds_jpeg_ljt.hpp"
+#include "jds_xform_dev.hpp"
+
+extern "C" {
+
+// ------------------------------------------------------ entropy decoding --
+
+int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out) {
+  const int rc = hd_parse(data, len, out, false, g_err, sizeof g_err);
+  if (rc) return rc;
+  if (out->H * out->W > (int64_t)1 << 28)
+    return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
+  return JDS_OK;
+}
+
+static int check_coef_cap(const int16_t* coeffs, int64_t cap, int64_t needed) {
+  if (!coeffs || cap < needed)
+    return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)needed);
+  return JDS_OK;
+}
+
+int jds_entropy_decode_info(int32_t* subseq_bits, int32_t* subseq_per_group) {
+  if (!subseq_bits || !subseq_per_group) return fail(JDS_EINVAL, "null argument");
+  int s, g;
+  dec_constants(&s, &g);
+  *subseq_bits = s;
+  *subseq_per_group = g;
+  return JDS_OK;
+}
+
+int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  jds_jfif_info info;
+  int rc = jds_jfif_parse(data, len, &info);
+  if (rc) return rc;
+  if ((rc = check_coef_cap(coeffs, coeffs_cap, info.coeffs_needed))) return rc;
+  rounds_out[0] = rounds_out[1] = rounds_out[2] = 0;
+  const uint32_t st = hd_host_decode(data, &info, subseq_bits, coeffs, rounds_out);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+// A file's four decode tables ([0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1; an
+// undefined one stays zeroed).  False: a DHT's BITS over-subscribe the code space.
+static bool dec_tables(const jds_jfif_huff* huff, HuffDecTab* tabs) {
+  bool ok = true;
+  for (int i = 0; i < 4; ++i) {
+    memset(&tabs[i], 0, sizeof tabs[i]);
+    if (huff[i].defined && hd_build(huff[i].bits, huff[i].vals, &tabs[i]) < 0) ok = false;
+  }
+  return ok;
+}
+static const char* const DHT_OVERSUBSCRIBED = "DHT: BITS over-subscribe the code space";
+
+// Upload one parsed file and decode it into c->ent_cf (device coefficients).
+// jf: its scans (jds_dec_jobs.hpp); m: the MCU record of an interleaved scan,
+// else null.  The status word and the propagation rounds come back.
+static int decode_dev(jds_ctx* c, const uint8_t* data, int64_t len, const jds_jfif_huff* huff, const DecJobFile& jf,
+                      const HdMcu* m, int64_t n_coeffs, uint32_t* status, uint32_t* rounds_out) {
+  hipStream_t s = c->stream;
+  HuffDecTab tabs[4];
+  if (!dec_tables(huff, tabs)) return fail(JDS_EINVAL, "%s", DHT_OVERSUBSCRIBED);
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<DecScan> sc;
+  std::vector<RstIv> ivs;
+  const DecJobsResult jr = dec_jobs_build(data, jf, FilePlace{0, 0, 0, 0}, lane_max, sc, ivs, g_err, sizeof g_err);
+  if (jr) return jr == DEC_JOBS_MARKERS ? JDS_EINVAL : JDS_ENOTSUP;
+  if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
+  const int nsc = (int)sc.size();
+  int max_ngrp = 0;
+  const long long ng = dec_layout(sc.data(), nsc, &max_ngrp);
+  if (ng < 0) return fail(JDS_ENOTSUP, "scan too long");
+  // interleaved: the MCU record, then the DC staging array of the scan's blocks
+  const size_t dcs_off = (sizeof(HdMcu) + 15) & ~(size_t)15, dcs_bytes = m ? sizeof(int16_t) * (size_t)jf.scan[0].nblocks : 0;
+  HIP_TRY(c->dec_file.ensure((size_t)len));
+  HIP_TRY(c->dec_tab.ensure(sizeof tabs));
+  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, nsc)));
+  HIP_TRY(c->dec_st.ensure(16));
+  HIP_TRY(c->dec_iv.ensure(sizeof(RstIv) * ivs.size()));
+  if (m) HIP_TRY(c->dec_mcu.ensure(dcs_off + dcs_bytes));
+  if (!ivs.empty())
+    HIP_TRY(hipMemcpyAsync(c->dec_iv.p, ivs.data(), sizeof(RstIv) * ivs.size(), hipMemcpyHostToDevice, s));
+  HIP_TRY(c->ent_cf.ensure((size_t)n_coeffs * sizeof(int16_t)));
+  HIP_TRY(hipMemcpyAsync(c->dec_file.p, data, (size_t)len, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(c->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice, s));
+  const HdMcu* mcu_dev = m ? (const HdMcu*)c->dec_mcu.p : nullptr;
+  int16_t* dcs = m ? (int16_t*)((char*)c->dec_mcu.p + dcs_off) : nullptr;
+  if (m) {
+    HIP_TRY(hipMemcpyAsync(c->dec_mcu.p, m, sizeof *m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(dcs, 0, dcs_bytes, s));
+  }
+  HIP_TRY(hipMemsetAsync(c->dec_st.p, 0, 16, s));
+  HIP_TRY(hipStreamSynchronize(s));  // tabs (and the caller's m) are stack objects
+  unsigned rounds = 0;
+  int too_many = 0;
+  // (zero-fills the coefficients; with no descriptors that is all it does, and rounds stays 0)
+  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc.data(), nsc, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p,
+                  c->dec_scr.p, (int16_t*)c->ent_cf.p, n_coeffs, (uint32_t*)c->dec_st.p, s, &rounds, &too_many,
+                  mcu_dev, dcs));
+  if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
+  HIP_TRY(launch_dec_rst((const uint8_t*)c->dec_file.p, (const RstIv*)c->dec_iv.p, (long long)ivs.size(),
+                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s, mcu_dev));
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *status = st;
+  *rounds_out = rounds;
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+// A parsed file of this library's profile into c->ent_cf.
+static int decode_jfif_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfif_info* info) {
+  return decode_dev(c, data, len, info->huff, dec_jobs_of(info), nullptr, info->coeffs_needed, &info->status,
+                    &info->rounds);
+}
+
+int jds_decode_jfif(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jfif_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jfif_parse(data, len, info);
+  if (rc) return rc;
+  if ((rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jfif_dev(c, data, len, info))) return rc;
+  HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+// ------------------------------------------ files of either scan form --
+
+int jds_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out) {
+  const int rc = hd_jpeg_parse(data, len, out, g_err, sizeof g_err);
+  if (rc) return rc;
+  if (out->H * out->W > (int64_t)1 << 28)
+    return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
+  return JDS_OK;
+}
+
+int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  if ((rc = check_coef_cap(coeffs, coeffs_cap, info.coeffs_needed))) return rc;
+  int lane_max;
+  rst_constants(&lane_max);
+  const uint32_t st = hd_jpeg_host_decode(data, &info, subseq_bits, lane_max, coeffs, rounds_out);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  return JDS_OK;
+}
+
+
+// A parsed file of either scan form into c->ent_cf.
+static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
+  const HdMcu m = hd_jpeg_mcu(info);
+  return decode_dev(c, data, len, info->huff, dec_jobs_of(info), info->interleaved ? &m : nullptr,
+                    info->coeffs_needed, &info->status, &info->rounds);
+}
+
+int jds_decode_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jpeg_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  if ((rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+// The parameter block of the plan's inverse for a file of 8x8 blocks with one quantisation table.
+static jds_params params_of_file(int32_t subsampling, const double* qtable) {
+  jds_params prm;
+  memset(&prm, 0, sizeof prm);
+  prm.block_size = 8;
+  prm.quality = 0;
+  prm.subsampling = subsampling;
+  memcpy(prm.qtable, qtable, sizeof prm.qtable);
+  return prm;
+}
+
+int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jpeg_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  if (info->subsampling == JDS_SS_GRAY)
+    return fail(JDS_ENOTSUP, "the plan's inverse takes three components: this is a grayscale file "
+                             "(jds_jpeg_to_rgb reconstructs it)");
+  if (!info->single_table || !info->reference_grid)
+    return fail(JDS_ENOTSUP, "the plan's inverse takes one quantisation table and the reference's block grids: "
+                             "%s (the per-stage calls reconstruct such a file)",
+                info->single_table ? "this size has other grids" : "the file has a table per component");
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  const jds_params prm = params_of_file(info->subsampling, info->qtable[0]);
+  if ((rc = check_tables(&prm))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
+// ----------------------------------- foreign files to pixels (k_jpeg_inv) --
+
+int jds_jpeg_inverse_info(int32_t* tile_h, int32_t* tile_w) {
+  if (!tile_h || !tile_w) return fail(JDS_EINVAL, "null argument");
+  int th, tw;
+  jpeg_inv_constants(&th, &tw);
+  *tile_h = th;
+  *tile_w = tw;
+  return JDS_OK;
+}
+
+// The rendering a _render call names: JDS_RENDER_REFERENCE (k_jpeg_inv) or
+// JDS_RENDER_LIBJPEG (k_jpeg_ljt); anything else is the caller's error.
+static int render_check(int32_t render) {
+  if (render != JDS_RENDER_REFERENCE && render != JDS_RENDER_LIBJPEG)
+    return fail(JDS_EINVAL, "unknown render %d (JDS_RENDER_REFERENCE or JDS_RENDER_LIBJPEG)", (int)render);
+  return JDS_OK;
+}
+
+// The launch arguments of a parsed file: its tables by check_tables' rule, its
+// grids T.81's for H x W, every tile's chroma window within the kernel's arrays.
+static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
+  const int rc = jinv_args(info, a);
+  if (rc == -1000)
+    return fail(JDS_EINVAL, "jpeg inverse: %lldx%lld with these grids is not a T.81 geometry of subsampling %d",
+                (long long)info->H, (long long)info->W, info->subsampling);
+  if (rc < 0) {
+    const int c = (-rc - 1) / 64, i = (-rc - 1) % 64;
+    return fail(JDS_EINVAL, "qtable[%d][%d] = %g is not an integer in [1, 255]", c, i, info->qtable[c][i]);
+  }
+  if (!jpeg_inv_fits(*a))
+    return fail(JDS_ENOTSUP, "jpeg inverse: a tile of %lldx%lld reads a wider chroma window than the kernel keeps",
+                (long long)info->H, (long long)info->W);
+  return JDS_OK;
+}
+
+static hipError_t launch_render(int32_t render, const JInvArgs& a, const int16_t* coeffs, uint8_t* rgb, hipStream_t s) {
+  return render == JDS_RENDER_LIBJPEG ? launch_jpeg_ljt(a, coeffs, rgb, s) : launch_jpeg_inv(a, coeffs, rgb, s);
+}
+
+int jds_jpeg_render_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream,
+                        int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
+  if (!info) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  if (!c || !coeffs || !rgb) return fail(JDS_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_render(render, a, coeffs, rgb, (hipStream_t)stream));
+  return JDS_OK;
+}
+
+int jds_jpeg_inverse_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream) {
+  return jds_jpeg_render_dev(c, info, coeffs, rgb, stream, JDS_RENDER_REFERENCE);
+}
+
+int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                    int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info) {
+  return jds_jpeg_to_rgb_render(c, data, len, rgb_out, rgb_cap, rgb_on_device, coeffs, info, JDS_RENDER_REFERENCE);
+}
+
+int jds_jpeg_to_rgb_render(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                           int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: rgb_out is not written)
+  uint8_t* dst = rgb_out;
+  if (!rgb_on_device) {
+    HIP_TRY(c->out.ensure(nimg));
+    dst = (uint8_t*)c->out.p;
+  }
+  HIP_TRY(launch_render(render, a, (const int16_t*)c->ent_cf.p, dst, c->stream));
+  if (!rgb_on_device) HIP_TRY(hipMemcpyAsync(rgb_out, dst, nimg, hipMemcpyDeviceToHost, c->stream));
+  if (coeffs)
+    HIP_TRY(hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
+                           c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_render(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
+  if (!info || !coeffs || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  if (render == JDS_RENDER_LIBJPEG)
+    jpeg_ljt_host_image(a, coeffs, rgb_out);
+  else
+    jpeg_inv_host(a, coeffs, rgb_out);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_inverse(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out) {
+  return jds_selftest_jpeg_render(info, coeffs, rgb_out, JDS_RENDER_REFERENCE);
+}
+
+int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_n, int32_t xaxis, int32_t* out) {
+  if (!out || dst_n < 1 || src_n < 1 || d0 < 0 || d1 < d0 || d1 >= dst_n) return fail(JDS_EINVAL, "bad argument");
+  jpeg_inv_window(d0, d1, 1.0 / ((double)dst_n / (double)src_n), src_n, xaxis != 0, &out[0], &out[1]);
+  out[2] = JI_CAP_ROWS2;
+  out[3] = JI_CAP_COLS2;
+  return JDS_OK;
+}
+
+// ------------------------------------------- batches of foreign files --
+// (DESIGN.md "Batches of foreign files")
+
+// What the layout keeps per batch: the parsed files, the inverse records of the
+// ones that take part (in batch order) and the tile maps of the four launches.
+struct BatchPlan {
+  std::vector<jds_jpeg_info> info;  // per file
+  std::vector<int> rec_of;          // per file: its record, or -1
+  std::vector<int> file_of;         // per record: its file
+  std::vector<JInvRec> recs;
+  std::vector<JInvMap> map[JI_MODES];
+  int64_t rgb_bytes = 0, coef_entries = 0;
+  int first_bad = -1;
+  char first_msg[400] = "";
+};
+
+// Parse every file, check what the single call checks before it decodes, and
+// lay the outputs out: images JI_RGB_ALIGN apart at least, coefficients end to
+// end.  A file that fails takes no space and does not stop the batch.
+static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                        BatchPlan& bp) {
+  if (n < 0 || (n > 0 && (!data || !lens || !items))) return fail(JDS_EINVAL, "null argument");
+  bp.info.resize((size_t)n);
+  bp.rec_of.assign((size_t)n, -1);
+  std::vector<JInvRec> parsed((size_t)n);
+  std::vector<std::string> msg((size_t)n);  // (the message of a failing file: g_err is per thread)
+  batch_parallel(n, [&](int i) {
+    jds_jpeg_batch_item& it = items[i];
+    memset(&it, 0, sizeof it);
+    it.rgb_off = -1;
+    it.coef_off = -1;
+    jds_jpeg_info& info = bp.info[(size_t)i];
+    JInvRec& r = parsed[(size_t)i];
+    memset(&r, 0, sizeof r);
+    int rc = data[i] && lens[i] >= 0 ? jds_jpeg_parse(data[i], lens[i], &info) : fail(JDS_EINVAL, "null file");
+    if (rc == JDS_OK) {
+      it.H = info.H;
+      it.W = info.W;
+      it.subsampling = info.subsampling;
+      it.interleaved = info.interleaved;
+      rc = jpeg_inv_args(&info, &r.a);
+    }
+    if (rc == JDS_OK) {
+      HuffDecTab t[4];
+      if (!dec_tables(info.huff, t)) rc = fail(JDS_EINVAL, "%s", DHT_OVERSUBSCRIBED);
+    }
+    it.rc = rc;
+    if (rc != JDS_OK) msg[(size_t)i] = g_err;
+  });
+  for (int i = 0; i < n; ++i) {
+    jds_jpeg_batch_item& it = items[i];
+    const jds_jpeg_info& info = bp.info[(size_t)i];
+    JInvRec& r = parsed[(size_t)i];
+    if (it.rc != JDS_OK) {
+      if (bp.first_bad < 0) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", msg[(size_t)i].c_str());
+      }
+      continue;
+    }
+    long long rb = bp.rgb_bytes, ce = bp.coef_entries;
+    jinv_batch_place(r, (int)bp.recs.size(), info.coeffs_needed, &rb, &ce);
+    bp.rgb_bytes = rb;
+    bp.coef_entries = ce;
+    it.rgb_off = r.rgb_off;
+    it.coef_off = r.coef_off;
+    it.coeffs_needed = info.coeffs_needed;
+    bp.rec_of[(size_t)i] = r.st;
+    bp.file_of.push_back(i);
+    bp.recs.push_back(r);
+  }
+  // what the grids and the 32-bit indices of the kernels take
+  if (bp.coef_entries / 64 > 0x7fffffffll || !jinv_batch_maps(bp.recs.data(), (int)bp.recs.size(), bp.map))
+    return fail(JDS_ENOTSUP, "batch of %d files: too many blocks or tiles for one set of launches", n);
+  return JDS_OK;
+}
+
+// The first failing file by index, where jds_last_error finds it.
+static void batch_note(const BatchPlan& bp) {
+  if (bp.first_bad >= 0) {
+    char m[400];
+    snprintf(m, sizeof m, "%s", bp.first_msg);
+    fail(0, "file %d: %s", bp.first_bad, m);
+  } else {
+    g_err[0] = 0;
+  }
+}
+
+int jds_jpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                          int64_t* rgb_bytes, int64_t* coef_entries) {
+  if (!rgb_bytes || !coef_entries) return fail(JDS_EINVAL, "null argument");
+  BatchPlan bp;
+  const int rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  *rgb_bytes = bp.rgb_bytes;
+  *coef_entries = bp.coef_entries;
+  batch_note(bp);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                            uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items) {
+  return jds_selftest_jpeg_batch_render(data, lens, n, subseq_bits, rgb, rgb_cap, coeffs, items, JDS_RENDER_REFERENCE);
+}
+
+int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
+                                   uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                   int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
+  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
+  BatchPlan bp;
+  rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
+    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+  std::vector<int16_t> own;
+  if (!coeffs) {
+    own.resize((size_t)bp.coef_entries);
+    coeffs = own.data();
+  }
+  int lane_max;
+  rst_constants(&lane_max);
+  std::vector<uint32_t> st(bp.recs.size() + 1, 0u);
+  for (size_t k = 0; k < bp.recs.size(); ++k) {
+    const int i = bp.file_of[k];
+    int32_t rounds[3];
+    st[k] = hd_jpeg_host_decode(data[i], &bp.info[(size_t)i], subseq_bits, lane_max, coeffs + bp.recs[k].coef_off, rounds);
+    items[i].status = st[k];
+  }
+  const JInvMap* maps[JI_MODES];
+  int nmap[JI_MODES];
+  for (int m = 0; m < JI_MODES; ++m) {
+    maps[m] = bp.map[m].data();
+    nmap[m] = (int)bp.map[m].size() - 1;
+  }
+  if (render == JDS_RENDER_LIBJPEG)
+    jpeg_ljt_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  else
+    jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  batch_note(bp);
+  return JDS_OK;
+}
+
+// The launches of a laid-out batch with at least one record: upload, entropy
+// decode into c->ent_cf (file k's coefficients at bp.recs[k].coef_off), then
+// with `inverse` the batch inverse into rgb; the status words into items.
+// Synchronous.  Without `inverse` (jds_jpeg_batch_transcode) rgb is not used.
+static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
+                     int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, uint32_t* rounds_out,
+                     bool inverse, int32_t render = JDS_RENDER_REFERENCE) {
+  const int nv = (int)bp.recs.size();
+  hipStream_t s = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  int lane_max;
+  rst_constants(&lane_max);
+  const int rst_g = rst_group_lanes();
+  // the upload: every part at a 256-byte boundary, files at 16-byte ones inside theirs
+  auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+  std::vector<size_t> foff((size_t)nv);
+  size_t o = 0;
+  for (int k = 0; k < nv; ++k) {
+    foff[(size_t)k] = o;
+    o = up(o + (size_t)lens[bp.file_of[(size_t)k]], 16);
+  }
+  // descriptors of both decode groups, lane intervals of both forms (a file's padded to whole workgroups)
+  std::vector<DecScan> sc_il, sc_pl;
+  std::vector<RstIv> iv_il, iv_pl;
+  std::vector<HuffDecTab> tabs(4 * (size_t)nv);
+  std::vector<HdMcu> mcus((size_t)nv);
+  std::vector<uint32_t> st0((size_t)nv, 0u);
+  long long dcs_n = 0;
+  for (int k = 0; k < nv; ++k) {
+    const int i = bp.file_of[(size_t)k];
+    const jds_jpeg_info& info = bp.info[(size_t)i];
+    (void)dec_tables(info.huff, &tabs[4 * (size_t)k]);  // (the layout checked them)
+    memset(&mcus[(size_t)k], 0, sizeof(HdMcu));
+    const FilePlace pl{k, (long long)foff[(size_t)k], bp.recs[(size_t)k].coef_off, dcs_n};
+    std::vector<DecScan>& sc = info.interleaved ? sc_il : sc_pl;
+    std::vector<RstIv>& iv = info.interleaved ? iv_il : iv_pl;
+    const size_t nsc0 = sc.size(), niv0 = iv.size();
+    if (info.interleaved) {
+      HdMcu m = hd_jpeg_mcu(&info);
+      for (int cc = 0; cc < 3; ++cc) m.off[cc] += pl.coef_off;
+      mcus[(size_t)k] = m;
+      dcs_n += (long long)m.bpm * m.mcu_cols * m.mcu_rows;
+    }
+    const DecJobsResult jr = dec_jobs_build(data[i], dec_jobs_of(&info), pl, lane_max, sc, iv, g_err, sizeof g_err);
+    if (jr == DEC_JOBS_MARKERS) {  // a defective scan, nothing of it is decoded
+      sc.resize(nsc0);
+      iv.resize(niv0);
+      st0[(size_t)k] = HD_RESTART;
+    } else if (jr) {
+      return JDS_ENOTSUP;
+    }
+    while (iv.size() % (size_t)rst_g) {
+      RstIv v{};
+      v.file = v.frame = k;
+      iv.push_back(v);
+    }
+  }
+  if (sc_il.size() > 0x7fffffffull || sc_pl.size() > 0x7fffffffull || iv_il.size() > 0x7fffffffull ||
+      iv_pl.size() > 0x7fffffffull)
+    return fail(JDS_ENOTSUP, "too many restart intervals");
+  int mx_il = 0, mx_pl = 0;
+  const long long ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
+  const long long ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
+  if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
+  int map_off[JI_MODES], nmap[JI_MODES], tiles[JI_MODES], nm = 0;
+  for (int m = 0; m < JI_MODES; ++m) {
+    map_off[m] = nm;
+    nmap[m] = (int)bp.map[m].size() - 1;
+    tiles[m] = bp.map[m].back().tile0;
+    nm += (int)bp.map[m].size();
+  }
+  const size_t o_files = 0, o_tabs = up(o, 256), o_mcu = up(o_tabs + sizeof(HuffDecTab) * tabs.size(), 256),
+               o_rec = up(o_mcu + sizeof(HdMcu) * mcus.size(), 256), o_map = up(o_rec + sizeof(JInvRec) * (size_t)nv, 256),
+               o_ivil = up(o_map + sizeof(JInvMap) * (size_t)nm, 256), o_ivpl = up(o_ivil + sizeof(RstIv) * iv_il.size(), 256),
+               o_st = up(o_ivpl + sizeof(RstIv) * iv_pl.size(), 256), total = up(o_st + 4 * (size_t)nv, 256);
+  if (total > c->bat_host_cap) {
+    if (c->bat_host) (void)hipHostFree(c->bat_host);
+    c->bat_host = nullptr;
+    c->bat_host_cap = 0;
+    HIP_TRY(hipHostMalloc(&c->bat_host, total, hipHostMallocDefault));
+    c->bat_host_cap = total;
+  }
+  char* h = (char*)c->bat_host;
+  batch_parallel(nv, [&](int k) {
+    const int i = bp.file_of[(size_t)k];
+    memcpy(h + o_files + foff[(size_t)k], data[i], (size_t)lens[i]);
+  });
+  memcpy(h + o_tabs, tabs.data(), sizeof(HuffDecTab) * tabs.size());
+  memcpy(h + o_mcu, mcus.data(), sizeof(HdMcu) * mcus.size());
+  memcpy(h + o_rec, bp.recs.data(), sizeof(JInvRec) * (size_t)nv);
+  for (int m = 0; m < JI_MODES; ++m)
+    memcpy(h + o_map + sizeof(JInvMap) * (size_t)map_off[m], bp.map[m].data(), sizeof(JInvMap) * bp.map[m].size());
+  if (!iv_il.empty()) memcpy(h + o_ivil, iv_il.data(), sizeof(RstIv) * iv_il.size());
+  if (!iv_pl.empty()) memcpy(h + o_ivpl, iv_pl.data(), sizeof(RstIv) * iv_pl.size());
+  memcpy(h + o_st, st0.data(), 4 * (size_t)nv);
+  const size_t scr_il = (dec_scratch_bytes(ng_il, (int)sc_il.size()) + 255) & ~(size_t)255;
+  HIP_TRY(c->bat.ensure(total));
+  HIP_TRY(c->dec_scr.ensure(scr_il + dec_scratch_bytes(ng_pl, (int)sc_pl.size())));
+  HIP_TRY(c->dec_mcu.ensure(sizeof(int16_t) * (size_t)dcs_n));
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)bp.coef_entries));
+  uint8_t* dst = rgb;
+  if (inverse && !rgb_on_device) {
+    HIP_TRY(c->out.ensure((size_t)bp.rgb_bytes));
+    dst = (uint8_t*)c->out.p;
+  }
+  char* dv = (char*)c->bat.p;
+  const CtxMarkScope marks_(c, s);
+  HIP_TRY(hipMemcpyAsync(dv, h, total, hipMemcpyHostToDevice, s));
+  if (dcs_n) HIP_TRY(hipMemsetAsync(c->dec_mcu.p, 0, sizeof(int16_t) * (size_t)dcs_n, s));
+  kmark(s, "(batch upload)");
+  const uint8_t* files_d = (const uint8_t*)(dv + o_files);
+  const HuffDecTab* tabs_d = (const HuffDecTab*)(dv + o_tabs);
+  const HdMcu* mcu_d = (const HdMcu*)(dv + o_mcu);
+  uint32_t* st_d = (uint32_t*)(dv + o_st);
+  int16_t* cf_d = (int16_t*)c->ent_cf.p;
+  const DecGroup grp[2] = {{sc_il.data(), (int)sc_il.size(), ng_il, mx_il, c->dec_scr.p, true},
+                           {sc_pl.data(), (int)sc_pl.size(), ng_pl, mx_pl, (char*)c->dec_scr.p + scr_il, false}};
+  unsigned rounds = 0;
+  int too_many = 0;
+  HIP_TRY(dec_run_groups(files_d, grp, 2, tabs_d, cf_d, bp.coef_entries, st_d, s, &rounds, &too_many, mcu_d,
+                         (int16_t*)c->dec_mcu.p));
+  if (too_many)
+    return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
+  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivil), (long long)iv_il.size(), tabs_d, cf_d, st_d, s, mcu_d));
+  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivpl), (long long)iv_pl.size(), tabs_d, cf_d, st_d, s, nullptr));
+  if (inverse && render == JDS_RENDER_LIBJPEG)
+    HIP_TRY(launch_jpeg_ljt_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
+                                  st_d, cf_d, dst, s));
+  else if (inverse)
+    HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
+                                  st_d, cf_d, dst, s));
+  if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
+    for (int k = 0; k < nv; ++k) {
+      const JInvRec& r = bp.recs[(size_t)k];
+      HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)r.a.H * (size_t)r.a.W * 3, hipMemcpyDeviceToHost,
+                             s));
+    }
+  if (coeffs)
+    HIP_TRY(hipMemcpyAsync(coeffs, cf_d, sizeof(int16_t) * (size_t)bp.coef_entries, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(st0.data(), st_d, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
+  kmark(s, "(batch download)");
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < nv; ++k) items[bp.file_of[(size_t)k]].status = st0[(size_t)k];
+  if (rounds_out) *rounds_out = rounds;
+  return JDS_OK;
+}
+
+int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                          int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                          uint32_t* rounds_out) {
+  return jds_jpeg_batch_to_rgb_render(c, data, lens, n, rgb, rgb_cap, rgb_on_device, coeffs, items, rounds_out,
+                                      JDS_RENDER_REFERENCE);
+}
+
+int jds_jpeg_batch_to_rgb_render(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                                 int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                 uint32_t* rounds_out, int32_t render) {
+  int rc;
+  if ((rc = render_check(render))) return rc;
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  BatchPlan bp;
+  rc = batch_layout(data, lens, n, items, bp);
+  if (rc) return rc;
+  if (rounds_out) *rounds_out = 0;
+  if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
+    return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
+  if (!bp.recs.empty() &&
+      (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true, render)))
+    return rc;
+  batch_note(bp);
+  return JDS_OK;
+}
+
+// ------------------------------------------------- lossless transcode --
+// (DESIGN.md "Transcode"; kernels: jds_entropy_mcu.hip)
+
+// One file of a writer batch: its geometry record (the planes' offsets count
+// from the start of c->ent_cf) and its header prefix.
+struct McuJob {
+  McuFile f;
+  std::vector<uint8_t> pfx;
+};
+
+static int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j) {
+  if (mcu_file_of(info, &j->f))
+    return fail(JDS_EINVAL,
+                "%lldx%lld with block grids %lldx%lld, %lldx%lld, %lldx%lld is not a T.81 geometry of subsampling %d",
+                (long long)info->H, (long long)info->W, (long long)info->grid_rows[0], (long long)info->grid_cols[0],
+                (long long)info->grid_rows[1], (long long)info->grid_cols[1], (long long)info->grid_rows[2],
+                (long long)info->grid_cols[2], info->subsampling);
+  for (int cc = 0; cc < 3; ++cc) j->f.off[cc] += coef_off;
+  return JDS_OK;
+}
+
+static int mcu_job_splice(const uint8_t* data, int64_t len, McuJob* j) {
+  const int64_t n = mcu_splice(data, len, nullptr, 0);
+  if (n < 0 || n > 0x7fffffffll) return fail(JDS_EINVAL, "header splice: no marker sequence from SOI to an SOS");
+  j->pfx.resize((size_t)n);
+  if (mcu_splice(data, len, j->pfx.data(), n) != n) return fail(JDS_EINVAL, "header splice: length mismatch");
+  return JDS_OK;
+}
+
+static int mcu_job_prefix(const jds_jpeg_info* info, const uint8_t* prefix, int64_t prefix_len, McuJob* j) {
+  if (prefix) {
+    if (prefix_len < 0 || prefix_len > 0x7fffffffll) return fail(JDS_EINVAL, "prefix_len %lld", (long long)prefix_len);
+    j->pfx.assign(prefix, prefix + prefix_len);
+    return JDS_OK;
+  }
+  j->pfx.resize(MCU_PFX_DEFAULT_MAX);
+  const int n = mcu_default_prefix(info, j->pfx.data());
+  if (n == -1000) return fail(JDS_EINVAL, "quantisation table id outside 0..3");
+  if (n < 0) {
+    const int cc = (-n - 1) / 64, i = (-n - 1) % 64;
+    return fail(JDS_EINVAL, "qtable[%d][%d] = %g is not an integer in [1, 255]", cc, i, info->qtable[cc][i]);
+  }
+  j->pfx.resize((size_t)n);
+  return JDS_OK;
+}
+
+static const char* const MCU_NOT_CODABLE =
+    "not baseline-codable: a DC difference category above 11 or an AC category above 10";
+
+// The Annex K table object on this thread's host side (and, with a context, on its device).
+static int mcu_tables(jds_ctx* c, const char** host) {
+  alignas(16) static thread_local char t[16384];
+  static thread_local bool built = false;
+  if (ent_tab_size() > sizeof t) return fail(JDS_EINVAL, "entropy tables exceed the staging buffer");
+  if (!built) {
+    ent_build_tables((EntTab*)t);
+    built = true;
+  }
+  if (c && !c->ent_tab.p) {
+    HIP_TRY(c->ent_tab.ensure(ent_tab_size()));
+    HIP_TRY(hipMemcpy(c->ent_tab.p, t, ent_tab_size(), hipMemcpyHostToDevice));
+  }
+  *host = t;
+  return JDS_OK;
+}
+
+static void mcu_std_tabs(McuStdTabs* t) {
+  for (int i = 0; i < 4; ++i) t->n_vals[i] = ent_std_table(i, &t->bits[i], &t->vals[i]);
+}
+
+// The transformed files of a writer batch (DESIGN.md "Lossless transforms"):
+// their records, tiles assigned, travel in the writer's upload and
+// k_coef_xform runs in front of the writer's first kernel.
+struct XfSet {
+  std::vector<XfFile> files;
+  int64_t tiles = 0;
+  void add(XfFile f) {
+    tiles += xf_set_tiles(&f, tiles);
+    files.push_back(f);
+  }
+};
+
+struct McuRun {
+  McuDev d;
+  int nf = 0, nseg = 0;
+  std::vector<int64_t> len;  // per job: the file's bytes, 0: not baseline-codable
+};
+
+// The writer's launches up to the files' lengths, over the coefficients in
+// c->ent_cf; the lengths and flags come back (the call's one read between the
+// placement and the emit).
+static int mcu_code(jds_ctx* c, std::vector<McuJob>& jobs, int optimize, McuRun* r, const XfSet* xf = nullptr) {
+  hipStream_t s = c->stream;
+  const int nf = (int)jobs.size();
+  long long nseg = 0, raw_words = 0, pfx_bytes = 0;
+  bool any_long = false;
+  for (int k = 0; k < nf; ++k) {
+    McuFile& f = jobs[(size_t)k].f;
+    f.seg0 = (int32_t)nseg;
+    f.frame = optimize ? k : 0;
+    f.raw_w0 = raw_words;
+    f.raw_words = mcu_raw_words(f.nblk);
+    f.pfx_off = pfx_bytes;
+    f.pfx_len = (int32_t)jobs[(size_t)k].pfx.size();
+    if (f.gray) f.comp_id = mcu_gray_id(jobs[(size_t)k].pfx.data(), f.pfx_len);
+    nseg += f.nseg;
+    raw_words += f.raw_words;
+    pfx_bytes += f.pfx_len;
+    any_long = any_long || f.nseg > mcu_self_max();
+    if (nseg > 0x1fffffffll || raw_words > 0x7fffffffll * 16)
+      return fail(JDS_ENOTSUP, "batch of %d files: too many blocks for one set of writer launches", nf);
+  }
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t nxf = xf ? xf->files.size() : 0, nxt = xf ? (size_t)xf->tiles : 0;
+  if (nxt > 0x7fffffffull) return fail(JDS_ENOTSUP, "batch of %d files: too many blocks for one transform launch", nf);
+  const size_t o_seg = up(sizeof(McuFile) * (size_t)nf), o_pfx = up(o_seg + 4 * (size_t)nseg),
+               o_xf = up(o_pfx + (size_t)pfx_bytes), o_xt = nxf ? up(o_xf + sizeof(XfFile) * nxf) : o_xf,
+               total = nxf ? up(o_xt + 4 * nxt) : o_xf;
+  std::vector<char> h(total, 0);
+  for (size_t k = 0; k < nxf; ++k) {
+    const XfFile& x = xf->files[k];
+    memcpy(h.data() + o_xf + sizeof(XfFile) * k, &x, sizeof(XfFile));
+    int32_t* tf = (int32_t*)(h.data() + o_xt) + x.tile0;
+    const int64_t nt = (k + 1 < nxf ? (int64_t)xf->files[k + 1].tile0 : xf->tiles) - x.tile0;
+    for (int64_t i = 0; i < nt; ++i) tf[i] = (int32_t)k;
+  }
+  for (int k = 0; k < nf; ++k) {
+    const McuJob& j = jobs[(size_t)k];
+    memcpy(h.data() + sizeof(McuFile) * (size_t)k, &j.f, sizeof(McuFile));
+    int32_t* sf = (int32_t*)(h.data() + o_seg) + j.f.seg0;
+    for (int i = 0; i < j.f.nseg; ++i) sf[i] = k;
+    if (!j.pfx.empty()) memcpy(h.data() + o_pfx + j.f.pfx_off, j.pfx.data(), j.pfx.size());
+  }
+  const char* tab_host;
+  int rc = mcu_tables(c, &tab_host);
+  if (rc) return rc;
+  HIP_TRY(c->mcu_up.ensure(total));
+  HIP_TRY(c->mcu_scr.ensure(mcu_scratch_bytes(nf, nseg, raw_words)));
+  McuDev& d = r->d;
+  (void)mcu_carve(c->mcu_scr.p, nf, nseg, raw_words, &d);
+  d.files = (const McuFile*)c->mcu_up.p;
+  d.segfile = (const int32_t*)((const char*)c->mcu_up.p + o_seg);
+  d.pfx = (const uint8_t*)c->mcu_up.p + o_pfx;
+  // a header template: the DHT segments a table class falls back to (its other bytes are not used)
+  uint8_t hdr[ENT_HDR];
+  double ones[64];
+  for (double& v : ones) v = 1.0;
+  if (ent_header(ones, M444, 8, 8, hdr) != ENT_HDR) return fail(JDS_EINVAL, "header template");
+  std::vector<char> frame(mcu_optframe_bytes());
+  mcu_std_frame(ent_es_tab(tab_host), hdr, frame.data());
+  HIP_TRY(hipMemcpyAsync(c->mcu_up.p, h.data(), total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d.hdr_std, hdr, ENT_HDR, hipMemcpyHostToDevice, s));
+  if (!optimize) HIP_TRY(hipMemcpyAsync(d.of, frame.data(), frame.size(), hipMemcpyHostToDevice, s));
+  if (nxf)  // the transformed files' planes into the second coefficient region, where their McuFile points
+    HIP_TRY(launch_coef_xform((const XfFile*)((const char*)c->mcu_up.p + o_xf),
+                              (const int32_t*)((const char*)c->mcu_up.p + o_xt), (long long)nxt,
+                              (const int16_t*)c->ent_cf.p, (int16_t*)c->ent_cf.p, s));
+  HIP_TRY(launch_mcu_code(d, nf, (int)nseg, any_long, (const int16_t*)c->ent_cf.p, optimize != 0,
+                          ent_es_tab(c->ent_tab.p), s));
+  std::vector<unsigned long long> fl((size_t)nf);
+  std::vector<uint32_t> fb((size_t)nf);
+  HIP_TRY(hipMemcpyAsync(fl.data(), d.flen, 8 * (size_t)nf, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(fb.data(), d.fbad, 4 * (size_t)nf, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (h, hdr and frame are this call's objects)
+  r->nf = nf;
+  r->nseg = (int)nseg;
+  r->len.assign((size_t)nf, 0);
+  for (int k = 0; k < nf; ++k) {
+    if ((long long)fl[(size_t)k] > mcu_capacity(jobs[(size_t)k].f) || fl[(size_t)k] < 4)
+      return fail(JDS_EHIP, "writer: file %d reports %llu bytes, outside its bound", k, fl[(size_t)k]);
+    r->len[(size_t)k] = fb[(size_t)k] ? 0 : (int64_t)fl[(size_t)k];
+  }
+  return JDS_OK;
+}
+
+// The files at fout (per job; < 0: not written) into out_dev; asynchronous on the context's stream.
+static int mcu_emit(jds_ctx* c, const McuRun& r, const std::vector<long long>& fout, uint8_t* out_dev) {
+  HIP_TRY(hipMemcpyAsync(r.d.fout, fout.data(), 8 * (size_t)r.nf, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_mcu_emit(r.d, r.nf, r.nseg, out_dev, c->stream));
+  return JDS_OK;
+}
+
+// One job whose coefficients are in c->ent_cf, to host memory.
+static int mcu_single(jds_ctx* c, McuJob& job, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len,
+                      const XfSet* xf = nullptr) {
+  std::vector<McuJob> jobs(1);
+  jobs[0] = std::move(job);
+  McuRun r;
+  const CtxMarkScope marks_(c, c->stream);
+  int rc = mcu_code(c, jobs, optimize, &r, xf);
+  if (rc) return rc;
+  if (r.len[0] == 0) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+  *out_len = r.len[0];
+  if (r.len[0] > out_cap || !out)
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)r.len[0]);
+  HIP_TRY(c->ent_out.ensure((size_t)r.len[0]));
+  const std::vector<long long> fout(1, 0ll);
+  if ((rc = mcu_emit(c, r, fout, (uint8_t*)c->ent_out.p))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, c->ent_out.p, (size_t)r.len[0], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return JDS_OK;
+}
+
+int jds_encode_jpeg(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize,
+                    const uint8_t* prefix, int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  if (!c || !info || !coeffs || !out_len) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_prefix(info, prefix, prefix_len, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nbytes = (size_t)mcu_coeffs(job.f) * sizeof(int16_t);
+  HIP_TRY(c->ent_cf.ensure(nbytes));
+  HIP_TRY(hipMemcpyAsync(c->ent_cf.p, coeffs, nbytes, hipMemcpyHostToDevice, c->stream));
+  return mcu_single(c, job, optimize, out, out_cap, out_len);
+}
+
+int jds_jpeg_transcode(jds_ctx* c, const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                       int64_t* out_len, jds_jpeg_info* info) {
+  if (!c || !data || !info || !out_len) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_splice(data, len, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  return mcu_single(c, job, optimize, out, out_cap, out_len);
+}
+
+// One file's transform, settled on the host before anything runs: the
+// operation (JDS_XF_AUTO resolved from the spliced prefix), its geometry and
+// the prefix, edited unless the operation is none.
+struct XfJob {
+  int op = JDS_XF_NONE;
+  XfPlan plan;
+  std::vector<uint8_t> pfx;
+};
+
+static inline int64_t xf_align(int64_t entries) { return (entries + 127) & ~(int64_t)127; }
+
+static int xf_prepare(const uint8_t* data, int64_t len, const jds_jpeg_info* info, int32_t op_in, XfJob* x) {
+  const int base = op_in & 0xFF;
+  if (op_in < 0 || (op_in & ~(0xFF | JDS_XF_TRIM)) || base > JDS_XF_AUTO)
+    return fail(JDS_EINVAL, "unknown transform operation 0x%x", (unsigned)op_in);
+  McuJob sp;
+  int rc = mcu_job_splice(data, len, &sp);
+  if (rc) return rc;
+  x->pfx = std::move(sp.pfx);
+  int64_t pos = -1;
+  int big = 0, op = base;
+  if (base == JDS_XF_AUTO)
+    op = xf_op_of_orientation(xf_exif_orientation(x->pfx.data(), (int64_t)x->pfx.size(), &pos, &big));
+  char msg[320];
+  if ((rc = xf_plan(info, op, (op_in & JDS_XF_TRIM) != 0, &x->plan, msg, sizeof msg))) return fail(rc, "%s", msg);
+  x->op = op;
+  if (op == JDS_XF_NONE) return JDS_OK;
+  const int e = xf_edit_prefix(x->pfx.data(), (int64_t)x->pfx.size(), x->plan.flags, x->plan.dst.H, x->plan.dst.W);
+  if (e == -2) return fail(JDS_ENOTSUP, "DQT: a 16-bit or incomplete table cannot be transposed");
+  if (e) return fail(JDS_EINVAL, "header prefix: %s", e == -3 ? "no SOF0 segment" : "not a sequence of marker segments");
+  if (pos >= 0) xf_exif_reset(x->pfx.data(), pos, big);
+  return JDS_OK;
+}
+
+// jds_jpeg_batch_transcode, and with `xform` jds_jpeg_batch_transform: the same
+// launches with per-file transformed records handed to the writer's driver.
+static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, bool xform,
+                           const int32_t* ops, int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                           jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  if (!c || !out_bytes || (n > 0 && !items)) return fail(JDS_EINVAL, "null argument");
+  *out_bytes = 0;
+  std::vector<jds_jpeg_batch_item> bi((size_t)(n > 0 ? n : 0));
+  BatchPlan bp;
+  int rc = batch_layout(data, lens, n, bi.data(), bp);
+  if (rc) return rc;
+  // the transformed planes follow the decoder's in c->ent_cf: sized before the decode fills it
+  std::vector<XfJob> xj((size_t)(xform && n > 0 ? n : 0));
+  const int64_t xbase = xf_align(bp.coef_entries);
+  int64_t xtotal = 0;
+  for (int i = 0; xform && i < n; ++i) {
+    if (bp.rec_of[(size_t)i] < 0) continue;
+    XfJob& x = xj[(size_t)i];
+    const int rc1 = xf_prepare(data[i], lens[i], &bp.info[(size_t)i], ops ? ops[i] : JDS_XF_AUTO, &x);
+    if (rc1) {  // refused: an item error with the code the file would get alone
+      bi[(size_t)i].rc = rc1;
+      if (bp.first_bad < 0 || i < bp.first_bad) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", g_err);
+      }
+      continue;
+    }
+    bi[(size_t)i].H = x.plan.dst.H;
+    bi[(size_t)i].W = x.plan.dst.W;
+    if (x.op != JDS_XF_NONE) xtotal += xf_align(x.plan.dst.coeffs_needed);
+  }
+  if (xtotal) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(xbase + xtotal)));
+  }
+  if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, nullptr, 0, nullptr, bi.data(), nullptr, false)))
+    return rc;
+  for (int i = 0; i < n; ++i) {
+    jds_jpeg_transcode_item& it = items[i];
+    memset(&it, 0, sizeof it);
+    it.rc = bi[(size_t)i].rc;
+    it.status = bi[(size_t)i].status;
+    it.H = bi[(size_t)i].H;
+    it.W = bi[(size_t)i].W;
+    it.subsampling = bi[(size_t)i].subsampling;
+    it.interleaved = bi[(size_t)i].interleaved;
+    it.out_off = -1;
+  }
+  // the files that decoded take part in the writer's launches
+  std::vector<McuJob> jobs;
+  std::vector<int> job_file;
+  XfSet xs;
+  int64_t xcur = xbase;
+  for (size_t k = 0; k < bp.recs.size(); ++k) {
+    const int i = bp.file_of[k];
+    if (items[i].status || items[i].rc) continue;
+    McuJob j;
+    if (xform && xj[(size_t)i].op != JDS_XF_NONE) {  // the writer sees the destination planes
+      XfJob& x = xj[(size_t)i];
+      if ((rc = mcu_job_geo(&x.plan.dst, xcur, &j))) return rc;
+      XfFile rec = x.plan.rec;
+      for (int cc = 0; cc < 3; ++cc) {
+        rec.soff[cc] += bp.recs[k].coef_off;
+        rec.doff[cc] += xcur;
+      }
+      xs.add(rec);
+      xcur += xf_align(x.plan.dst.coeffs_needed);
+      j.pfx = std::move(x.pfx);
+    } else {
+      if ((rc = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, &j))) return rc;
+      if ((rc = mcu_job_splice(data[i], lens[i], &j))) return rc;
+    }
+    jobs.push_back(std::move(j));
+    job_file.push_back(i);
+  }
+  if (jobs.empty()) {
+    batch_note(bp);
+    return JDS_OK;
+  }
+  hipStream_t s = c->stream;
+  const CtxMarkScope marks_(c, s);
+  McuRun r;
+  if ((rc = mcu_code(c, jobs, optimize, &r, xs.files.empty() ? nullptr : &xs))) return rc;
+  std::vector<long long> fout(jobs.size(), -1ll);
+  int64_t cur = 0;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const int i = job_file[k];
+    if (r.len[k] == 0) {
+      items[i].rc = fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+      if (bp.first_bad < 0 || i < bp.first_bad) {
+        bp.first_bad = i;
+        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", MCU_NOT_CODABLE);
+      }
+      continue;
+    }
+    fout[k] = cur;
+    items[i].out_off = cur;
+    items[i].out_len = r.len[k];
+    cur = (cur + r.len[k] + 255) & ~(int64_t)255;
+  }
+  *out_bytes = cur;
+  if (cur > 0 && (!out || out_cap < cur))
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)cur);
+  if (cur > 0) {
+    uint8_t* dst = out;
+    if (!out_on_device) {
+      HIP_TRY(c->ent_out.ensure((size_t)cur));
+      dst = (uint8_t*)c->ent_out.p;
+    }
+    if ((rc = mcu_emit(c, r, fout, dst))) return rc;
+    if (!out_on_device)  // file by file: the gaps of the caller's buffer stay as they are
+      for (size_t k = 0; k < jobs.size(); ++k)
+        if (fout[k] >= 0)
+          HIP_TRY(hipMemcpyAsync(out + fout[k], dst + fout[k], (size_t)r.len[k], hipMemcpyDeviceToHost, s));
+    kmark(s, "(transcode download)");
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  batch_note(bp);
+  return JDS_OK;
+}
+
+int jds_jpeg_batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                             jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  return batch_transcode(c, data, lens, n, false, nullptr, optimize, out, out_cap, out_on_device, items, out_bytes);
+}
+
+// ------------------------------------------------ lossless transforms --
+// (DESIGN.md "Lossless transforms"; kernel: jds_xform.hip; host side: jds_xform.hpp)
+
+int jds_jpeg_batch_transform(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                             const int32_t* ops, int32_t optimize, uint8_t* out, int64_t out_cap,
+                             int32_t out_on_device, jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  return batch_transcode(c, data, lens, n, true, ops, optimize, out, out_cap, out_on_device, items, out_bytes);
+}
+
+int jds_jpeg_transform_info(const uint8_t* data, int64_t len, int32_t op, int32_t* op_out, int64_t* H_out,
+                            int64_t* W_out) {
+  if (!data || !op_out || !H_out || !W_out) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, &info, op, &x))) return rc;
+  *op_out = x.op;
+  *H_out = x.plan.dst.H;
+  *W_out = x.plan.dst.W;
+  return JDS_OK;
+}
+
+int jds_jpeg_transform(jds_ctx* c, const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                       int64_t out_cap, int64_t* out_len, jds_jpeg_info* info) {
+  if (!c || !data || !info || !out_len) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jpeg_parse(data, len, info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, info, op, &x))) return rc;
+  McuJob job;
+  if (x.op == JDS_XF_NONE) {  // jds_jpeg_transcode
+    if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+    job.pfx = std::move(x.pfx);
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+    return mcu_single(c, job, optimize, out, out_cap, out_len);
+  }
+  const int64_t base = xf_align(info->coeffs_needed);
+  if ((rc = mcu_job_geo(&x.plan.dst, base, &job))) return rc;
+  job.pfx = std::move(x.pfx);
+  XfFile rec = x.plan.rec;
+  for (int cc = 0; cc < 3; ++cc) rec.doff[cc] += base;
+  XfSet xs;
+  xs.add(rec);
+  HIP_TRY(hipSetDevice(c->device));
+  // the transformed planes follow the decoder's: sized before the decode fills the buffer
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(base + x.plan.dst.coeffs_needed)));
+  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  return mcu_single(c, job, optimize, out, out_cap, out_len, &xs);
+}
+
+int jds_selftest_coef_transform_dev(jds_ctx* c, const jds_jpeg_info* info, int32_t op, const int16_t* coeffs,
+                                    int16_t* coeffs_out) {
+  if (!c || !info || !coeffs || !coeffs_out) return fail(JDS_EINVAL, "null argument");
+  const int base_op = op & 0xFF;
+  if (op < 0 || (op & ~(0xFF | JDS_XF_TRIM)) || base_op >= JDS_XF_AUTO)
+    return fail(JDS_EINVAL, "unknown transform operation 0x%x (an explicit operation is needed)", (unsigned)op);
+  XfPlan p;
+  char msg[320];
+  int rc = xf_plan(info, base_op, (op & JDS_XF_TRIM) != 0, &p, msg, sizeof msg);
+  if (rc) return fail(rc, "%s", msg);
+  McuFile sf;
+  (void)mcu_file_of(info, &sf);  // (xf_plan has checked it)
+  const int64_t nsrc = mcu_coeffs(sf), base = xf_align(nsrc), ndst = p.dst.coeffs_needed;
+  XfFile rec = p.rec;
+  for (int cc = 0; cc < 3; ++cc) rec.doff[cc] += base;
+  const size_t o_t = (sizeof(XfFile) + 255) & ~(size_t)255, total = o_t + 4 * (size_t)p.tiles;
+  std::vector<char> h(total, 0);  // (the tile table: every tile is record 0's)
+  memcpy(h.data(), &rec, sizeof rec);
+  hipStream_t s = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(c->mcu_up.ensure(total));
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(base + ndst)));
+  int16_t* cf = (int16_t*)c->ent_cf.p;
+  HIP_TRY(hipMemcpyAsync(c->mcu_up.p, h.data(), total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(cf, coeffs, sizeof(int16_t) * (size_t)nsrc, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_coef_xform((const XfFile*)c->mcu_up.p, (const int32_t*)((const char*)c->mcu_up.p + o_t),
+                            (long long)p.tiles, cf, cf, s));
+  HIP_TRY(hipMemcpyAsync(coeffs_out, cf + base, sizeof(int16_t) * (size_t)ndst, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return JDS_OK;
+}
+
+// the host model's result into the caller's buffer
+static int mcu_host_result(int wrc, const std::vector<uint8_t>& file, uint8_t* out, int64_t out_cap,
+                           int64_t* out_len) {
+  if (wrc) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+  *out_len = (int64_t)file.size();
+  if (!out || out_cap < (int64_t)file.size())
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)file.size());
+  memcpy(out, file.data(), file.size());
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_transcode(const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out, int64_t out_cap,
+                                int64_t* out_len) {
+  if (!data || !out_len) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(&info, 0, &job))) return rc;
+  if ((rc = mcu_job_splice(data, len, &job))) return rc;
+  int lane_max, sb, spg;
+  rst_constants(&lane_max);
+  dec_constants(&sb, &spg);
+  std::vector<int16_t> cf((size_t)info.coeffs_needed);
+  int32_t rounds[3];
+  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, cf.data(), optimize, job.pfx.data(), (int64_t)job.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_transform(const uint8_t* data, int64_t len, int32_t op, int32_t optimize, uint8_t* out,
+                                int64_t out_cap, int64_t* out_len) {
+  if (!data || !out_len) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc = jds_jpeg_parse(data, len, &info);
+  if (rc) return rc;
+  XfJob x;
+  if ((rc = xf_prepare(data, len, &info, op, &x))) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(x.op == JDS_XF_NONE ? &info : &x.plan.dst, 0, &job))) return rc;
+  int lane_max, sb, spg;
+  rst_constants(&lane_max);
+  dec_constants(&sb, &spg);
+  std::vector<int16_t> cf((size_t)info.coeffs_needed);
+  int32_t rounds[3];
+  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
+  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  if (x.op != JDS_XF_NONE) {
+    std::vector<int16_t> dst((size_t)x.plan.dst.coeffs_needed);
+    xf_host(x.plan.rec, cf.data(), dst.data());
+    cf.swap(dst);
+  }
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, cf.data(), optimize, x.pfx.data(), (int64_t)x.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_encode(const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize, const uint8_t* prefix,
+                             int64_t prefix_len, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  if (!info || !coeffs || !out_len) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  if ((rc = mcu_job_prefix(info, prefix, prefix_len, &job))) return rc;
+  McuStdTabs std_tabs;
+  mcu_std_tabs(&std_tabs);
+  std::vector<uint8_t> file;
+  const int wrc = mcu_host_write(job.f, coeffs, optimize, job.pfx.data(), (int64_t)job.pfx.size(), std_tabs, &file);
+  return mcu_host_result(wrc, file, out, out_cap, out_len);
+}
+
+int jds_selftest_jpeg_hist_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint32_t* counts) {
+  if (!c || !info || !coeffs || !counts) return fail(JDS_EINVAL, "null argument");
+  McuJob job;
+  int rc;
+  if ((rc = mcu_job_geo(info, 0, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nbytes = (size_t)mcu_coeffs(job.f) * sizeof(int16_t);
+  HIP_TRY(c->ent_cf.ensure(nbytes));
+  HIP_TRY(hipMemcpyAsync(c->ent_cf.p, coeffs, nbytes, hipMemcpyHostToDevice, c->stream));
+  std::vector<McuJob> jobs(1);
+  jobs[0] = std::move(job);
+  McuRun r;
+  if ((rc = mcu_code(c, jobs, 1, &r))) return rc;
+  // (the counters open the file's frame)
+  HIP_TRY(hipMemcpy(counts, r.d.of, sizeof(uint32_t) * 2 * OPT_BINS, hipMemcpyDeviceToHost));
+  return JDS_OK;
+}
+
+int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jfif_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  int rc = jds_jfif_parse(data, len, info);
+  if (rc) return rc;
+  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
+  const jds_params prm = params_of_file(info->subsampling, info->qtable);
+  if ((rc = check_tables(&prm))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = decode_jfif_dev(c, data, len, info))) return rc;
+  return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
+}  // extern "C"

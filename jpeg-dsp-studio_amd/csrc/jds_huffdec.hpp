@@ -342,7 +342,7 @@ JDS_HDI uint32_t hd_write_lane(const Src& src, const TC& tc, uint64_t entry, uin
   return fl;
 }
 
-// One scan of one frame (host-built, jds_abi.hip).  A launch serves descriptors
+// One scan of one frame (host-built, jds_dec_jobs.hpp).  A launch serves descriptors
 // of different files (jds_jpeg_batch_to_rgb): `file` selects the file's four
 // decode tables (tabs + 4 * file) and, interleaved, its MCU descriptor
 // (mcu + file), whose off[] then include the file's place in the batch's

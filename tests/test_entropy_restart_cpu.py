@@ -225,3 +225,54 @@ def test_restart_parser_and_model_clean_under_host_sanitizers(tmp_path):
     assert r.stderr == '', r.stderr[-4000:]
     files, parsed, clean = (int(r.stdout.split()[i]) for i in (0, 2, 4))
     assert files == len(os.listdir(corpus)) and parsed >= len(valid) and clean >= 3 * len(valid)
+
+
+def test_decode_descriptor_builder_clean_under_host_sanitizers(tmp_path):
+    """tools/dec_jobs_san.cpp (its own main, no HIP, nothing loaded into Python) built with
+    -fsanitize=address,undefined over csrc/jds_dec_jobs.hpp: the interleaved fixtures, non-interleaved
+    files with and without intervals, a one-component file, and one restart file of each form truncated
+    at every length and with every scan byte replaced by an RST0 marker.  lane_max 1, 5 and the
+    library's own send the same small files down all three routes; the program checks coverage, byte
+    ranges, routing, destinations, tables and placement of whatever the builder does not refuse."""
+    pytest.importorskip('PIL.Image')
+    import gray_ref
+    from jds import entropy
+    cxx = next((c for c in ('/opt/rocm/lib/llvm/bin/clang++', shutil.which('clang++'), shutil.which('g++'))
+                if c and os.path.exists(c)), None)
+    assert cxx, 'no host C++ compiler'
+    exe = tmp_path / 'dec_jobs_san'
+    subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    '-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'jpeg-dsp-studio_amd', 'csrc'),
+                    os.path.join(ROOT, 'tools', 'dec_jobs_san.cpp'), '-o', str(exe)], check=True)
+    corpus = tmp_path / 'corpus'
+    corpus.mkdir()
+    gold = os.path.join(ROOT, 'tests', 'golden', 'jpeg_interleaved')
+    ok = {f'il_{n}': open(os.path.join(gold, n), 'rb').read() for n in sorted(os.listdir(gold)) if n.endswith('.jpg')}
+    assert len(ok) == 8
+    for h, w, mode in ((16, 16, '4:4:4'), (40, 56, '4:2:0'), (33, 35, '4:2:2')):
+        ok[f'pl_{h}x{w}_{mode[::2]}_ri0.jpg'] = plain_file(h, w, mode, 50)
+        for ri in (1, 2, 5, 7):
+            ok[f'pl_{h}x{w}_{mode[::2]}_ri{ri}.jpg'] = rst_file(h, w, mode, 50, ri)
+    ok['gray_ri2.jpg'] = gray_ref.pillow_gray(37, 53, 0, restart_marker_blocks=2)
+    for name, d in ok.items():
+        (corpus / f'ok_{name}').write_bytes(d)
+    for form, d in (('il', ok['il_p40x72_420_rst2.jpg']), ('pl', ok['pl_16x16_444_ri2.jpg'])):
+        scans = entropy.parse_jpeg(d)['scans']
+        assert scans[0]['restart_interval'] and len(scans) == (1 if form == 'il' else 3)
+        for n in range(len(d)):
+            (corpus / f'trunc_{form}_{n}.jpg').write_bytes(d[:n])
+        for s in scans:
+            for i in range(s['offset'], s['offset'] + s['length']):
+                (corpus / f'rst_{form}_{i}.jpg').write_bytes(d[:i] + b'\xff\xd0' + d[i + 1:])
+    lane_max = entropy.restart_info()[1]
+    assert lane_max > 7
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+    r = subprocess.run([str(exe), str(corpus), '1', '5', str(lane_max)], capture_output=True, text=True, env=env,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert r.stderr == '', r.stderr[-4000:]
+    words = r.stdout.replace('(', ' ').split()
+    files, parsed, both, built, refused, descriptors, lanes = (int(words[i]) for i in (0, 2, 4, 8, 10, 12, 14))
+    assert files == len(os.listdir(corpus)) and parsed >= len(ok) and both >= 15
+    # (the parser checks the markers' number and order, so the builder seldom has anything to refuse)
+    assert built >= 3 * len(ok) and built + refused == 3 * parsed and descriptors > 0 and lanes > 0

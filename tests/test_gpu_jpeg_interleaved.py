@@ -203,3 +203,35 @@ def test_gpu_existing_paths_unchanged():
         assert np.array_equal(a, codec.decompress_jpeg(data)) and np.array_equal(a, codec.decompress_jpeg(data, staged=True))
     with pytest.raises(ValueError, match='two quantisation tables|interleaved scan'):
         entropy.decode_jfif(fixture('p24x40_420')[0])
+
+
+def test_gpu_one_context_alternates_scan_forms():
+    """The single-file driver serves both scan forms over the same context buffers: lanes,
+    one descriptor, and descriptors per interval, interleaved and not, in turn on one
+    context.  A stale interval table, MCU record or DC staging array of the previous file
+    would show; the first file decodes the same again at the end."""
+    import ctypes as C
+    from jds import _abi, entropy
+    lane_max = entropy.restart_info()[1]
+    rstrow, small, rst2 = (fixture(n)[0] for n in ('p48x48_420_opt_rstrow', 'p9x9_444', 'p40x72_420_rst2'))
+    own = entropy.encode_jfif(fixture('p9x9_444')[1], 16, 16, '4:4:4', Q50)[0]   # (2 x 2 blocks per component, as 9x9)
+    ny, nc = rr.counts(40, 56, '4:2:0')
+    blocks = fixture('p40x72_420_rst2')[1].reshape(-1, 64)[:ny + 2 * nc]
+    plain5 = rr.encode_jfif_rst(blocks.reshape(-1), 40, 56, '4:2:0', Q50, 5)[0]
+    il = [entropy.parse_jpeg(d)['interleaved'] for d in (rstrow, small, rst2, plain5)]
+    assert il == [True, True, True, False] and 5 <= lane_max
+    order = [(rstrow, False), (own, True), (small, False), (rst2, False), (plain5, False), (rstrow, False)]
+    got = []
+    with _abi.lease(0) as ctx:
+        for data, jfif in order:
+            a, p, n = entropy._bytes_arg(data)
+            info = _abi.JfifInfo() if jfif else _abi.JpegInfo()
+            _abi.check((_abi.lib().jds_jfif_parse if jfif else _abi.lib().jds_jpeg_parse)(p, n, C.byref(info)))
+            cf = np.full(int(info.coeffs_needed), 0x5555, np.int16)
+            call = _abi.lib().jds_decode_jfif if jfif else _abi.lib().jds_decode_jpeg
+            _abi.check(call(ctx.handle, p, n, cf.ctypes.data, cf.size, C.byref(info)))
+            got.append(cf)
+    for (data, jfif), cf in zip(order, got):
+        exp = (entropy.host_decode_jfif if jfif else entropy.host_decode_jpeg)(data)[0]
+        assert np.array_equal(cf, exp)
+    assert np.array_equal(got[0], got[-1])

@@ -1,0 +1,222 @@
+// dec_jobs_san.cpp — stand-alone host program over the decode descriptor
+// builder (csrc/jds_dec_jobs.hpp), for sanitizer runs:
+//
+//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -Iinclude -Ijpeg-dsp-studio_amd/csrc tools/dec_jobs_san.cpp -o dec_jobs_san
+//   ./dec_jobs_san DIR lane_max [lane_max ...]
+//
+// Parses every file of DIR from an exactly-sized heap copy (a read past the end
+// is a sanitizer report) and, where hd_jpeg_parse accepts it, builds its
+// descriptors and lane intervals with every lane_max, at a zero FilePlace and
+// at a non-zero one.  The builder may refuse a file (restart markers missing, a
+// size beyond its fields); what it returns otherwise is checked in full:
+//
+//   coverage     per scan the pieces' block ranges are [0, nblocks), ascending
+//                and disjoint, every piece but the last of the interval's size
+//   byte ranges  inside the scan; from the scan's start or two bytes after an
+//                RSTm, to an RSTm or the scan's end; no RSTm inside
+//   routing      no interval: one descriptor; interval <= lane_max: lanes only;
+//                longer: descriptors only
+//   destinations and tables as jds_dec_jobs.hpp states them for the two forms
+//   placement    the non-zero place shifts every output by its amounts only
+//
+// A file hd_parse accepts too (this library's profile) must give the same
+// result through the jds_jfif_info filler.  Files named ok_* must parse and
+// build.  Exit 1 on the first violation.  No HIP, no GPU.
+#include <dirent.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <string>
+#include <vector>
+
+#include "jds_huffdec.hpp"
+#include "jds_dec_jobs.hpp"
+
+using namespace jds;
+
+static const char* g_file = "";
+static int g_lane_max = 0;
+
+#define CHECK(cond)                                                                              \
+  do {                                                                                           \
+    if (!(cond)) {                                                                               \
+      fprintf(stderr, "%s (lane_max %d): %s:%d: %s\n", g_file, g_lane_max, __FILE__, __LINE__, #cond); \
+      exit(1);                                                                                   \
+    }                                                                                            \
+  } while (0)
+
+static bool rst_at(const uint8_t* d, long long i, long long end) {
+  return i + 1 < end && d[i] == 0xFF && d[i + 1] >= 0xD0 && d[i + 1] <= 0xD7;
+}
+
+// The byte range [off, off + n) of a piece of scan [s0, s1) that follows the piece ending at prev_end (-1: the first).
+static void check_bytes(const uint8_t* d, long long s0, long long s1, long long off, long long n, long long prev_end) {
+  CHECK(n >= 0 && off >= s0 && off + n <= s1);
+  if (prev_end < 0)
+    CHECK(off == s0);
+  else
+    CHECK(off == prev_end + 2 && rst_at(d, off - 2, s1));
+  CHECK(off + n == s1 || rst_at(d, off + n, s1));
+  for (long long i = off; i + 1 < off + n; ++i) CHECK(!rst_at(d, i, off + n));
+}
+
+static bool same(const DecScan& a, const DecScan& b) {
+  return a.data_off == b.data_off && a.nbytes == b.nbytes && a.coef_off == b.coef_off && a.dcs_off == b.dcs_off &&
+         a.nblocks == b.nblocks && a.frame == b.frame && a.dc_tab == b.dc_tab && a.ac_tab == b.ac_tab &&
+         a.grp0 == b.grp0 && a.ngrp == b.ngrp && a.nsub == b.nsub && a.blk_base == b.blk_base && a.file == b.file;
+}
+static bool same(const RstIv& a, const RstIv& b) {
+  return a.data_off == b.data_off && a.coef_off == b.coef_off && a.nbytes == b.nbytes && a.nblk == b.nblk &&
+         a.frame == b.frame && a.tabs == b.tabs && a.file == b.file && a.pad_ == b.pad_;
+}
+
+// Everything but placement, for the result built at place pl.
+static void check_result(const uint8_t* data, const jds_jpeg_info& info, const FilePlace& pl, int lane_max,
+                         const std::vector<DecScan>& sc, const std::vector<RstIv>& ivs) {
+  const bool il = info.interleaved != 0;
+  const long long yb = info.grid_cols[0] * info.grid_rows[0], cb = info.grid_cols[1] * info.grid_rows[1];
+  size_t isc = 0, iiv = 0;
+  for (int i = 0; i < info.n_scans; ++i) {
+    const jds_jpeg_scan& s = info.scan[i];
+    const int comp = s.component[0] - 1;
+    const long long nblocks = il ? (long long)info.blocks_per_mcu * info.mcu_cols * info.mcu_rows : (comp ? cb : yb);
+    const long long ri = il ? (long long)s.restart_interval * info.blocks_per_mcu : s.restart_interval;
+    const long long plane = il || comp == 0 ? 0 : 64 * (yb + (comp - 1) * cb);
+    const long long s0 = s.offset, s1 = s.offset + s.length;
+    const long long pieces = ri == 0 ? 1 : (nblocks + ri - 1) / ri;
+    const bool lanes = ri != 0 && ri <= lane_max;
+    // routing: this scan's pieces are all of one kind, and nothing of the other kind belongs to it
+    CHECK(lanes ? iiv + (size_t)pieces <= ivs.size() : isc + (size_t)pieces <= sc.size());
+    long long prev_end = -1;
+    for (long long k = 0; k < pieces; ++k) {
+      const long long blk0 = ri == 0 ? 0 : k * ri;
+      const long long nb = ri == 0 ? nblocks : (nblocks - blk0 < ri ? nblocks - blk0 : ri);
+      CHECK(nb > 0 || nblocks == 0);
+      long long off, n;
+      if (lanes) {
+        const RstIv& v = ivs[iiv++];
+        off = v.data_off - pl.data_off;
+        n = v.nbytes;
+        CHECK(v.nblk == nb && v.frame == pl.file && v.file == pl.file && v.pad_ == 0);
+        CHECK(v.coef_off == (il ? blk0 : pl.coef_off + plane + 64 * blk0));
+        CHECK(v.tabs == (il ? 0 : s.dc_table[0] | ((2 + s.ac_table[0]) << 8)));
+      } else {
+        const DecScan& d = sc[isc++];
+        off = d.data_off - pl.data_off;
+        n = d.nbytes;
+        CHECK(d.nblocks == nb && d.frame == pl.file && d.file == pl.file);
+        CHECK(d.grp0 == 0 && d.ngrp == 0 && d.nsub == 0);  // (dec_layout's)
+        if (il) {
+          CHECK(d.coef_off == 0 && d.blk_base == blk0 && d.dcs_off == pl.dcs_off && d.dc_tab == 0 && d.ac_tab == 0);
+        } else {
+          CHECK(d.coef_off == pl.coef_off + plane + 64 * blk0 && d.blk_base == 0 && d.dcs_off == 0);
+          CHECK(d.dc_tab == 4 * pl.file + s.dc_table[0] && d.ac_tab == 4 * pl.file + 2 + s.ac_table[0]);
+        }
+      }
+      check_bytes(data, s0, s1, off, n, prev_end);
+      prev_end = off + n;
+    }
+  }
+  CHECK(isc == sc.size() && iiv == ivs.size());
+}
+
+int main(int argc, char** argv) {
+  if (argc < 3) {
+    fprintf(stderr, "usage: %s DIR lane_max [lane_max ...]\n", argv[0]);
+    return 2;
+  }
+  std::vector<int> lane_maxes;
+  for (int i = 2; i < argc; ++i) lane_maxes.push_back(atoi(argv[i]));
+  DIR* dir = opendir(argv[1]);
+  if (!dir) {
+    perror(argv[1]);
+    return 2;
+  }
+  long files = 0, parsed = 0, built = 0, refused = 0, descriptors = 0, lanes = 0, both_parsers = 0;
+  while (dirent* e = readdir(dir)) {
+    if (e->d_name[0] == '.') continue;
+    const std::string path = std::string(argv[1]) + "/" + e->d_name;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) continue;
+    fseek(f, 0, SEEK_END);
+    const long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    // exactly n bytes on the heap: the sanitizer's red zone starts at data + n
+    uint8_t* data = (uint8_t*)malloc(n > 0 ? (size_t)n : 1);
+    if (!data || (n > 0 && fread(data, 1, (size_t)n, f) != (size_t)n)) {
+      fclose(f);
+      free(data);
+      continue;
+    }
+    fclose(f);
+    ++files;
+    g_file = e->d_name;
+    g_lane_max = 0;
+    const bool must = strncmp(e->d_name, "ok_", 3) == 0;
+    jds_jpeg_info info;
+    char msg[256];
+    const bool ok = hd_jpeg_parse(data, n, &info, msg, sizeof msg) == JDS_OK;
+    CHECK(ok || !must);
+    if (ok) {
+      ++parsed;
+      jds_jfif_info fi;
+      const bool own = hd_parse(data, n, &fi, false, msg, sizeof msg) == JDS_OK;
+      both_parsers += own;
+      const DecJobFile jf = dec_jobs_of(&info);
+      for (int lane_max : lane_maxes) {
+        g_lane_max = lane_max;
+        const FilePlace p0{0, 0, 0, 0}, p1{3, 1000, 6400, 77};
+        std::vector<DecScan> sc0, sc1, scf;
+        std::vector<RstIv> iv0, iv1, ivf;
+        msg[0] = 0;
+        const DecJobsResult r0 = dec_jobs_build(data, jf, p0, lane_max, sc0, iv0, msg, sizeof msg);
+        const DecJobsResult r1 = dec_jobs_build(data, jf, p1, lane_max, sc1, iv1, nullptr, 0);
+        CHECK(r0 == r1);
+        if (own) {  // the other filler: the same facts
+          CHECK(dec_jobs_build(data, dec_jobs_of(&fi), p0, lane_max, scf, ivf, nullptr, 0) == r0);
+          CHECK(scf.size() == sc0.size() && ivf.size() == iv0.size());
+          for (size_t k = 0; k < sc0.size(); ++k) CHECK(same(scf[k], sc0[k]));
+          for (size_t k = 0; k < iv0.size(); ++k) CHECK(same(ivf[k], iv0[k]));
+        }
+        if (r0 != DEC_JOBS_OK) {
+          CHECK(!must && msg[0] != 0);
+          ++refused;
+          continue;
+        }
+        ++built;
+        descriptors += (long)sc0.size();
+        lanes += (long)iv0.size();
+        check_result(data, info, p0, lane_max, sc0, iv0);
+        check_result(data, info, p1, lane_max, sc1, iv1);
+        // placement: the place's amounts and nothing else
+        CHECK(sc1.size() == sc0.size() && iv1.size() == iv0.size());
+        for (size_t k = 0; k < sc0.size(); ++k) {
+          DecScan d = sc0[k];
+          d.data_off += p1.data_off;
+          d.frame = d.file = p1.file;
+          if (info.interleaved) {
+            d.dcs_off += p1.dcs_off;
+          } else {
+            d.coef_off += p1.coef_off;
+            d.dc_tab += 4 * p1.file;
+            d.ac_tab += 4 * p1.file;
+          }
+          CHECK(same(d, sc1[k]));
+        }
+        for (size_t k = 0; k < iv0.size(); ++k) {
+          RstIv v = iv0[k];
+          v.data_off += p1.data_off;
+          v.frame = v.file = p1.file;
+          if (!info.interleaved) v.coef_off += p1.coef_off;
+          CHECK(same(v, iv1[k]));
+        }
+      }
+    }
+    free(data);
+  }
+  closedir(dir);
+  printf("%ld files, %ld parsed (%ld by both parsers), %ld built, %ld refused, %ld descriptors, %ld lanes\n", files,
+         parsed, both_parsers, built, refused, descriptors, lanes);
+  return 0;
+}
