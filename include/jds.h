@@ -905,6 +905,16 @@ int jds_selftest_inv_fast(int32_t subsampling, const int16_t* coeffs, const doub
 int jds_selftest_inv_fast16(int32_t subsampling, const int16_t* coeffs, const double* qtable, int64_t H, int64_t W,
                             int32_t fuse, double* values, uint8_t* bytes);
 
+/* Test-only, host only: the rows of tile row ty of the tiled 8x8 inverse
+ * (k_inv_fast, k_inv2) for an H-row frame, from the kernels' own geometry
+ * (csrc/jds_inv_common.hpp InvRows; 4:2:0 tiles start 8 luma rows higher where
+ * that adds no tile row).  out[8] = the offset (0 or 8), the number of tile
+ * rows, the tile's first luma row and its luma rows, its first chroma block
+ * row and its chroma block rows, the first sample row of its chroma window and
+ * the window's sample rows.  need (nullable): out[5] x 8 flags, whether the
+ * tile computes row r of chroma block row out[4] + i into the window. */
+int jds_selftest_inv_rows(int32_t subsampling, int64_t H, int32_t ty, int32_t* out, uint8_t* need);
+
 /* Test-only: the host-built cv2 INTER_AREA table of one axis (OpenCV
  * computeResizeAreaTab, used by the odd-size path) for src -> dst samples:
  * per destination index its tap count n[d] (<= 4) and taps si[4d..], a[4d..].

@@ -272,6 +272,9 @@ static int make_geo(const jds_params* p, int64_t H, int64_t W, Geo* g, int* mode
   // cv2.resize: inv_scale = dst/src, scale = 1/inv_scale
   G.up_sy = 1.0 / ((double)H / (double)G.hc);
   G.up_sx = 1.0 / ((double)W / (double)G.wc);
+  // the tiled 8x8 inverses (k_inv_fast, k_inv2) raise their 4:2:0 tiles by a
+  // luma block row where that adds no tile row
+  G.inv_yoff = (B == 8 && !gen) ? inv_tile_yoff(mode, (int)H) : 0;
   if (mode_out) *mode_out = mode;
   if (pf_out) *pf_out = mode != JDS_SS_444 && p->prefilter != 0;
   return JDS_OK;
@@ -1749,6 +1752,18 @@ int jds_selftest_area_tab(int32_t src, int32_t dst, int32_t* n, int32_t* si, dou
     }
   }
   free(t);
+  return JDS_OK;
+}
+
+int jds_selftest_inv_rows(int32_t subsampling, int64_t H, int32_t ty, int32_t* out, uint8_t* need) {
+  if (!out || H < 1 || H > 65536 || ty < 0 || subsampling < JDS_SS_444 || subsampling > JDS_SS_420)
+    return fail(JDS_EINVAL, "bad argument");
+  int o[8];
+  inv_rows(subsampling, (int)H, ty, o);
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  if (need)
+    for (int i = 0; i < o[5]; ++i)
+      for (int r = 0; r < 8; ++r) need[8 * i + r] = (uint8_t)inv_rows_need(subsampling, (int)H, ty, o[4] + i, r);
   return JDS_OK;
 }
 

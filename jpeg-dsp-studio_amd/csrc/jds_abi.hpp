@@ -25,6 +25,8 @@ hipError_t launch_codec(int mode, bool pf, const Geo& g, int n, const uint8_t* r
                         int sel_blk, hipStream_t s, hipEvent_t* ev, int phases, int in_div, const GenBufs* gb,
                         const InvFix* fx = nullptr);
 int inv_tiles(int mode, int H, int W);
+void inv_rows(int mode, int H, int ty, int* out);
+int inv_rows_need(int mode, int H, int ty, int by, int r);
 int area_tab_build(int src, int dst, AreaTap* tab);
 size_t gen_sub_doubles(const Geo& g);
 size_t gen_rec_doubles(const Geo& g);

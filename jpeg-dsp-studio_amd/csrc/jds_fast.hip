@@ -390,8 +390,8 @@ k_fwd32(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coef
       if (i < WN) {
         float R, G, B;
         unpack32(s_rgb[i], R, G, B);
-        s_cb[i] = cb32(R, G, B);
-        s_cr[i] = cr32(R, G, B);
+        s_cb[i] = cb32m(R, G, B);
+        s_cr[i] = cr32m(R, G, B);
       }
     }
     __syncthreads();
@@ -434,7 +434,7 @@ k_fwd32(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coef
         const int sy = reflect_pad(gy * 8 + i, g.H) - y0 + 1;
         float R, G, B;
         unpack32(s_rgb[sy * WC + sx], R, G, B);
-        v[i] = (plane == 0 ? luma32(R, G, B) : (plane == 1 ? cb32(R, G, B) : cr32(R, G, B))) - 128.0f;
+        v[i] = plane == 0 ? luma32(R, G, B) - 128.0f : (plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B));
       }
     } else if constexpr (CPLANE) {
       // pair sums of the sample's column on window rows (pixel row + 1)
@@ -447,9 +447,9 @@ k_fwd32(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coef
         const int wr0 = C::SY * reflect_pad(gy * 8 + i, g.hc) - y0 + 1;  // window row of the first pixel row
         const float* col = s_pl + wr0 * HW;
         if constexpr (C::SY == 2)
-          v[i] = fmaf(k2, col[2 * HW], fmaf(gk32[4], col[HW], fmaf(gk32[3], col[0], k0 * col[-HW]))) * 0.25f - 128.0f;
+          v[i] = fmaf(k2, col[2 * HW], fmaf(gk32[4], col[HW], fmaf(gk32[3], col[0], k0 * col[-HW]))) * 0.25f;
         else
-          v[i] = fmaf(k0, col[HW] + col[-HW], k1 * col[0]) * 0.5f - 128.0f;
+          v[i] = fmaf(k0, col[HW] + col[-HW], k1 * col[0]) * 0.5f;
       }
     } else {
       const float* s_pl = s_u + (plane == 1 ? 0 : WN);
@@ -468,14 +468,14 @@ k_fwd32(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coef
             {  // unfiltered chroma
               float R, G, B;
               unpack32(s_rgb[w], R, G, B);
-              s[a][b] = plane == 1 ? cb32(R, G, B) : cr32(R, G, B);
+              s[a][b] = plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B);
             }
           }
         }
         if constexpr (C::SY == 2)
-          v[i] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f - 128.0f;
+          v[i] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f;
         else
-          v[i] = (s[0][0] + s[0][1]) * 0.5f - 128.0f;
+          v[i] = (s[0][0] + s[0][1]) * 0.5f;
       }
     }
     fdct8_f32(v);
@@ -612,8 +612,8 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
       for (int k = 0; k < 8; ++k) {
         const float R = (float)byte_at(w, 3 * k), G = (float)byte_at(w, 3 * k + 1), B = (float)byte_at(w, 3 * k + 2);
         yy[k] = luma32m(R, G, B);
-        cb[k] = cb32(R, G, B);
-        cr[k] = cr32(R, G, B);
+        cb[k] = cb32m(R, G, B);
+        cr[k] = cr32m(R, G, B);
       }
       const int o = (r - 1) * TW + 8 * c;
       if (r >= 1 && r <= TH) {
@@ -624,11 +624,6 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
       }
       if constexpr (!SUB) {
         if (r >= 1 && r <= TH) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            cb[k] -= 128.0f;
-            cr[k] -= 128.0f;
-          }
           fdct8_f32(cb);
           fdct8_f32(cr);
           float4* db = reinterpret_cast<float4*>(s_cb + o);
@@ -646,13 +641,13 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
         float rb = dpp_f32<0x101>(cb[0]), rr = dpp_f32<0x101>(cr[0]);  // row_shl:1
         if (c == 0) {  // bytes 5..7 of the 8 before the segment; pixel 1 at the image edge
           const float R = (float)((ring.y >> 8) & 255u), G = (float)((ring.y >> 16) & 255u), B = (float)(ring.y >> 24);
-          lb = left_edge ? cb[1] : cb32(R, G, B);
-          lr = left_edge ? cr[1] : cr32(R, G, B);
+          lb = left_edge ? cb[1] : cb32m(R, G, B);
+          lr = left_edge ? cr[1] : cr32m(R, G, B);
         }
         if (c == SEG - 1) {  // bytes 0..2 of the 8 after the segment; pixel W-2 at the image edge
           const float R = (float)(ring.x & 255u), G = (float)((ring.x >> 8) & 255u), B = (float)((ring.x >> 16) & 255u);
-          rb = right_edge ? cb[6] : cb32(R, G, B);
-          rr = right_edge ? cr[6] : cr32(R, G, B);
+          rb = right_edge ? cb[6] : cb32m(R, G, B);
+          rr = right_edge ? cr[6] : cr32m(R, G, B);
         }
         // Gaussian row pass and the area's horizontal pair sum in one chain:
         // H_j = (k0, k0+k1, k1+k2, k2) . x_{2j-1 .. 2j+2} (fwd_input_error)
@@ -775,9 +770,9 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
           if constexpr (C::SY == 2)
-            v[jj] = fmaf(k2, R[3][jj], fmaf(gk32[4], R[2][jj], fmaf(gk32[3], R[1][jj], k0 * R[0][jj]))) * 0.25f - 128.0f;
+            v[jj] = fmaf(k2, R[3][jj], fmaf(gk32[4], R[2][jj], fmaf(gk32[3], R[1][jj], k0 * R[0][jj]))) * 0.25f;
           else
-            v[jj] = fmaf(k0, R[2][jj] + R[0][jj], k1 * R[1][jj]) * 0.5f - 128.0f;
+            v[jj] = fmaf(k0, R[2][jj] + R[0][jj], k1 * R[1][jj]) * 0.5f;
         }
       } else {
 #pragma unroll
@@ -806,9 +801,9 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
             }
           }
           if constexpr (C::SY == 2)
-            v[4 * h + jj] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f - 128.0f;
+            v[4 * h + jj] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f;
           else
-            v[4 * h + jj] = (s[0][0] + s[0][1]) * 0.5f - 128.0f;
+            v[4 * h + jj] = (s[0][0] + s[0][1]) * 0.5f;
         }
       }
       }
@@ -836,8 +831,8 @@ k_fwd32i(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
 // no prefilter: a block reads only its own 8 x 8 pixels) without the tile
 // staging.  A wave owns 8 blocks in raster order, each lane one 8-pixel row of
 // its block: 24-byte RGB load (np.pad reflect rows / columns at the padded
-// edge, engines/block_processor.py), fp32 colour (luma32m, cb32 - 128,
-// cr32 - 128: fwd_input_error's chains), then per plane the row DCT in
+// edge, engines/block_processor.py), fp32 colour (luma32m, cb32m, cr32m:
+// fwd_input_error's chains), then per plane the row DCT in
 // registers, the block's column pass through its own LDS slot (the 8 lanes of a
 // block are one wave's, whose LDS operations execute in order: no workgroup
 // barrier), certified quantisation, the in-place int16 transpose and 16-byte
@@ -910,7 +905,7 @@ k_fwd444w(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ co
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float R = (float)byte_at(w, 3 * k), G = (float)byte_at(w, 3 * k + 1), B = (float)byte_at(w, 3 * k + 2);
-      v[k] = p == 0 ? luma32m(R, G, B) : (p == 1 ? cb32(R, G, B) - 128.0f : cr32(R, G, B) - 128.0f);
+      v[k] = p == 0 ? luma32m(R, G, B) : (p == 1 ? cb32m(R, G, B) : cr32m(R, G, B));
     }
     fdct8_f32(v);  // axis 1 of row lv
     float4* d4 = reinterpret_cast<float4*>(slot + lv * 8);
@@ -1706,37 +1701,47 @@ double fwd_input_error(int plane, int mode, bool pf, const double* gk, int chain
   // luma32: fmaf(kb, B, fmaf(kg, G, kr*R)); constants in fp32; then -128
   const double dkl = fabs((double)0.299f - 0.299) + fabs((double)0.587f - 0.587) + fabs((double)0.114f - 0.114);
   if (plane == 0) return 255 * dkl + u * 255 * (0.299 + 0.886 + 1.0) + u * 128 + 1e-12;
-  // cb32 / cr32: fmaf(k1, ., fmaf(k2, ., fmaf(0.5f, ., 128))); 0.5x+128 exact
+  // cb32m / cr32m: fmaf(k1, ., fmaf(k2, ., 0.5f * .)), the level-shifted sample
+  // itself: 0.5x exact, then two roundings of magnitude <= 127.5
   const double dkb = fabs((double)-0.168736f + 0.168736) + fabs((double)-0.331264f + 0.331264);
   const double dkr = fabs((double)-0.081312f + 0.081312) + fabs((double)-0.418688f + 0.418688);
-  const double ec = 255 * (dkb > dkr ? dkb : dkr) + 2 * u * 256 + 1e-12;  // before -128
+  const double ec = 255 * (dkb > dkr ? dkb : dkr) + 2 * u * 128 + 1e-12;
   double e = ec;
   double e_comb = 0.0;  // k_fwd32i's combined-tap chain (prefiltered chroma)
+  double e_sum = 0.0;   // the taps' sum against 1 (prefiltered chroma)
   if (mode != M444 && pf) {
     const double k0 = gk[0], k1 = gk[1], k2 = gk[2];
     const double k0f = (float)k0, k1f = (float)k1, k2f = (float)k2;
     const double dk = fabs(k0f - k0) + fabs(k1f - k1) + fabs(k2f - k2);
-    // k_fwd32 (per pixel): row fmaf(k2, S1, fmaf(k1, S0, k0*S_1)); |S| <= 256, taps sum to 1
-    const double er = (k0f + k1f + k2f) * e + dk * 256 + u * 256 * (k0 + (k0 + k1) + 1.0) + 1e-12;
+    // The reference filters the unshifted plane and subtracts 128 after; the
+    // chains filter x - 128, so with exact taps they give sum(w x) - 128 sum(w)
+    // where the reference has sum(w x) - 128.  sum(w) = S^2 for both layouts (S
+    // the sum of the Gaussian's fp64 taps, each of the two passes weighs by S;
+    // the area mean's weights sum to 1 exactly), and S is 1 only to rounding
+    // (S formed here in fp64: 2 roundings, priced at 4 ulp of S^2).
+    const double S = (k0 + k1) + k2;
+    e_sum = 128 * (fabs(S * S - 1.0) + 0x1p-50);
+    // k_fwd32 (per pixel): row fmaf(k2, S1, fmaf(k1, S0, k0*S_1)); |S| <= 128, taps sum to 1
+    const double er = (k0f + k1f + k2f) * e + dk * 128 + u * 128 * (k0 + (k0 + k1) + 1.0) + 1e-12;
     // column: fmaf(k0, T+1 + T-1, k1*T0)
-    e = (k1f + 2 * k0f) * er + dk * 512 + u * (512 + k1 * 256 + 256) + 1e-12;
+    e = (k1f + 2 * k0f) * er + dk * 256 + u * (256 + k1 * 128 + 128) + 1e-12;
     // k_fwd32i, k_fwd32 and k_fwd16f: horizontal pair sums H =
     // combined chain over 4 chroma samples
-    // (|H| <= 512), then 4:2:0: the combined chain down 4 rows of H (|.| <= 1024)
+    // (|H| <= 256), then 4:2:0: the combined chain down 4 rows of H (|.| <= 512)
     // and *0.25 (exact); 4:2:2: the column form over H (magnitudes doubled) and
     // *0.5 (exact)
-    const double eh = combined_chain_error(gk, 256, ec);
+    const double eh = combined_chain_error(gk, 128, ec);
     if (mode == M420)
-      e_comb = combined_chain_error(gk, 512, eh) / 4;
+      e_comb = combined_chain_error(gk, 256, eh) / 4;
     else
-      e_comb = ((k1f + 2 * k0f) * eh + dk * 1024 + u * (1024 + k1 * 512 + 512) + 1e-12) / 2;
+      e_comb = ((k1f + 2 * k0f) * eh + dk * 512 + u * (512 + k1 * 256 + 256) + 1e-12) / 2;
   }
-  if (mode == M420) e = e + u * (512 + 768 + 1024) / 4;  // ((a+b)+c)+d, *0.25 exact
-  if (mode == M422) e = e + u * 512 / 2;                  // (a+b), *0.5 exact
+  if (mode == M420) e = e + u * (256 + 384 + 512) / 4;  // ((a+b)+c)+d, *0.25 exact
+  if (mode == M422) e = e + u * 256 / 2;                  // (a+b), *0.5 exact
   // the bound covers the chains named (every certified forward kernel now
   // uses the combined taps: callers pass 2)
   if (mode != M444 && pf) e = (chains & 1) ? ((chains & 2) && e_comb > e ? e_comb : e) : e_comb;
-  return e + u * 128;                                     // -128
+  return e + e_sum;  // (no trailing -128: the samples are level-shifted from the start)
 }
 
 // E[p][k][l] (p: 0 luma, 1 chroma): the rigorous bound on |c_fp32 - c_exact|
@@ -1789,7 +1794,7 @@ void fast_fwd_thresholds(const double* Q, int mode, bool pf, const double* gk, f
 // ---------------------------------------------- host: the fp32 chain (tests) --
 //
 // The forward kernels' fp32 arithmetic restated on the host, expression for
-// expression (k_fwd32i / k_fwd32: luma32m, cb32 / cr32, the prefilter's row
+// expression (k_fwd32i / k_fwd32: luma32m, cb32m / cr32m, the prefilter's row
 // then column FMA chains with BORDER_REFLECT_101, the area average, fdct8_f32
 // along both axes in either order), so the CPU test suite can check the bound
 // above against the exact reference on adversarial inputs.  Test-only.
@@ -1808,9 +1813,9 @@ int fwd32_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
   if (ph % 8 || pw % 8) return -1;
   const float k0 = (float)gk[0], k1 = (float)gk[1], k2 = (float)gk[2];
   auto px = [&](int y, int x, int c) { return (float)rgb[((size_t)y * W + x) * 3 + c]; };
-  auto chroma = [&](int y, int x) {  // full-resolution chroma sample (not shifted)
+  auto chroma = [&](int y, int x) {  // full-resolution chroma sample, level-shifted
     const float R = px(y, x, 0), G = px(y, x, 1), B = px(y, x, 2);
-    return plane == 1 ? cb32(R, G, B) : cr32(R, G, B);
+    return plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B);
   };
   auto rowf = [&](int y, int x) {  // prefilter row pass at (y, x)
     const float bl = chroma(y, refl101(x - 1, W)), c = chroma(y, x), br = chroma(y, refl101(x + 1, W));
@@ -1825,14 +1830,14 @@ int fwd32_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
   };
   auto sample = [&](int y, int x) -> float {  // plane sample (y, x), level-shifted
     if (plane == 0) return luma32m(px(y, x, 0), px(y, x, 1), px(y, x, 2));
-    if (mode == M444) return chroma(y, x) - 128.0f;
+    if (mode == M444) return chroma(y, x);
     if (pf && comb) {  // k_fwd32i
       if (sy == 2) {
         const float r0 = pairf(refl101(2 * y - 1, H), x), r1 = pairf(2 * y, x), r2 = pairf(2 * y + 1, x),
                     r3 = pairf(refl101(2 * y + 2, H), x);
-        return fmaf(h[2], r3, fmaf(h[4], r2, fmaf(h[3], r1, h[0] * r0))) * 0.25f - 128.0f;
+        return fmaf(h[2], r3, fmaf(h[4], r2, fmaf(h[3], r1, h[0] * r0))) * 0.25f;
       }
-      return fmaf(k0, pairf(refl101(y + 1, H), x) + pairf(refl101(y - 1, H), x), k1 * pairf(y, x)) * 0.5f - 128.0f;
+      return fmaf(k0, pairf(refl101(y + 1, H), x) + pairf(refl101(y - 1, H), x), k1 * pairf(y, x)) * 0.5f;
     }
     float s[2][2];
     for (int a = 0; a < sy; ++a)
@@ -1843,8 +1848,8 @@ int fwd32_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
         else
           s[a][b] = chroma(yy, xx);
       }
-    if (sy == 2) return (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f - 128.0f;
-    return (s[0][0] + s[0][1]) * 0.5f - 128.0f;
+    if (sy == 2) return (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f;
+    return (s[0][0] + s[0][1]) * 0.5f;
   };
   const int nbx = pw / 8;
   for (int by = 0; by < ph / 8; ++by)

@@ -323,21 +323,21 @@ k_fwd16f(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
         for (int j = 0; j < 16; ++j) {
           float R, G, B;
           rgbf(px[j], R, G, B);
-          cb[j] = cb32(R, G, B);
-          cr[j] = cr32(R, G, B);
+          cb[j] = cb32m(R, G, B);
+          cr[j] = cr32m(R, G, B);
         }
         float lb = __shfl_up(cb[15], 1, SEGS), lr = __shfl_up(cr[15], 1, SEGS);
         float rb = __shfl_down(cb[0], 1, SEGS), rr = __shfl_down(cr[0], 1, SEGS);
         if (c == 0) {  // pixel x0 - 1; pixel 1 at the image edge (BORDER_REFLECT_101)
           const float R = (float)((ring.w >> 8) & 255u), G = (float)((ring.w >> 16) & 255u), B = (float)(ring.w >> 24);
-          lb = x0 == 0 ? cb[1] : cb32(R, G, B);
-          lr = x0 == 0 ? cr[1] : cr32(R, G, B);
+          lb = x0 == 0 ? cb[1] : cb32m(R, G, B);
+          lr = x0 == 0 ? cr[1] : cr32m(R, G, B);
         }
         if (c == SEGS - 1) {  // pixel x0 + TW; pixel W - 2 at the image edge
           const float R = (float)(ring.x & 255u), G = (float)((ring.x >> 8) & 255u), B = (float)((ring.x >> 16) & 255u);
           const bool edge = x0 + C::TW == g.W;
-          rb = edge ? cb[14] : cb32(R, G, B);
-          rr = edge ? cr[14] : cr32(R, G, B);
+          rb = edge ? cb[14] : cb32m(R, G, B);
+          rr = edge ? cr[14] : cr32m(R, G, B);
         }
         // the Gaussian row pass and the area's horizontal pair sum as one chain
         // (k_fwd32i's combined taps, fwd_input_error): TW / 2 pair sums per row
@@ -393,8 +393,8 @@ k_fwd16f(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
           float R, G, B;
           rgbf(s_rgb[i], R, G, B);
           const int r = i / WC, c = i - r * WC;
-          s_cb[cidx(r, c)] = cb32(R, G, B);
-          s_cr[cidx(r, c)] = cr32(R, G, B);
+          s_cb[cidx(r, c)] = cb32m(R, G, B);
+          s_cr[cidx(r, c)] = cr32m(R, G, B);
         }
       }
       __syncthreads();
@@ -455,7 +455,7 @@ k_fwd16f(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
         const int sy = (INT ? gy * 16 + i : reflect_pad(gy * 16 + i, g.H)) - y0 + 1;
         float R, G, B;
         rgbf(s_rgb[sy * WC + sx], R, G, B);
-        v[i] = plane == 0 ? luma32m(R, G, B) : (plane == 1 ? cb32(R, G, B) : cr32(R, G, B)) - 128.0f;
+        v[i] = plane == 0 ? luma32m(R, G, B) : (plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B));
       }
     } else if (CPLANE) {
       // pair sums of window rows 2r-1 .. 2r+2 (4:2:0: the combined taps, *0.25)
@@ -470,9 +470,9 @@ k_fwd16f(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
         const int wr0 = C::SY * sr - y0 + 1;  // window row of the sample's first pixel row
         const float* col = s_pl + wr0 * HW;
         if constexpr (C::SY == 2)
-          v[i] = fmaf(k2, col[2 * HW], fmaf(h2, col[HW], fmaf(h1, col[0], k0 * col[-HW]))) * 0.25f - 128.0f;
+          v[i] = fmaf(k2, col[2 * HW], fmaf(h2, col[HW], fmaf(h1, col[0], k0 * col[-HW]))) * 0.25f;
         else
-          v[i] = fmaf(k0, col[HW] + col[-HW], k1 * col[0]) * 0.5f - 128.0f;
+          v[i] = fmaf(k0, col[HW] + col[-HW], k1 * col[0]) * 0.5f;
       }
     } else {
       // INTER_AREA mean of the unfiltered full-resolution chroma
@@ -489,13 +489,13 @@ k_fwd16f(const Geo g, const uint8_t* __restrict__ rgb, int16_t* __restrict__ coe
           for (int b = 0; b < 2; ++b) {  // unfiltered chroma
             float R, G, B;
             rgbf(s_rgb[(wr0 + a) * WC + wc0 + b], R, G, B);
-            s[a][b] = plane == 1 ? cb32(R, G, B) : cr32(R, G, B);
+            s[a][b] = plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B);
           }
         }
         if constexpr (C::SY == 2)
-          v[i] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f - 128.0f;
+          v[i] = (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f;
         else
-          v[i] = (s[0][0] + s[0][1]) * 0.5f - 128.0f;
+          v[i] = (s[0][0] + s[0][1]) * 0.5f;
       }
     }
   };
@@ -1026,7 +1026,7 @@ int fwd16_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
   auto px = [&](int y, int x, int c) { return (float)rgb[((size_t)y * W + x) * 3 + c]; };
   auto chroma = [&](int y, int x) {
     const float R = px(y, x, 0), G = px(y, x, 1), B = px(y, x, 2);
-    return plane == 1 ? cb32(R, G, B) : cr32(R, G, B);
+    return plane == 1 ? cb32m(R, G, B) : cr32m(R, G, B);
   };
   auto rowf = [&](int y, int x) {
     return fmaf(k2, chroma(y, refl(x + 1, W)), fmaf(k1, chroma(y, x), k0 * chroma(y, refl(x - 1, W))));
@@ -1039,13 +1039,13 @@ int fwd16_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
   };
   auto sample = [&](int y, int x) -> float {
     if (plane == 0) return luma32m(px(y, x, 0), px(y, x, 1), px(y, x, 2));
-    if (mode == M444) return chroma(y, x) - 128.0f;
+    if (mode == M444) return chroma(y, x);
     if (pf && comb) {
       if (sy == 2)
         return fmaf(h[2], pairf(refl(2 * y + 2, H), x),
                     fmaf(h[4], pairf(2 * y + 1, x), fmaf(h[3], pairf(2 * y, x), h[0] * pairf(refl(2 * y - 1, H), x)))) *
-                   0.25f - 128.0f;
-      return fmaf(k0, pairf(refl(y + 1, H), x) + pairf(refl(y - 1, H), x), k1 * pairf(y, x)) * 0.5f - 128.0f;
+                   0.25f;
+      return fmaf(k0, pairf(refl(y + 1, H), x) + pairf(refl(y - 1, H), x), k1 * pairf(y, x)) * 0.5f;
     }
     float s[2][2];
     for (int a = 0; a < sy; ++a)
@@ -1054,8 +1054,8 @@ int fwd16_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
         s[a][b] = pf ? fmaf(k0, rowf(refl(yy + 1, H), xx) + rowf(refl(yy - 1, H), xx), k1 * rowf(yy, xx))
                      : chroma(yy, xx);
       }
-    if (sy == 2) return (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f - 128.0f;
-    return (s[0][0] + s[0][1]) * 0.5f - 128.0f;
+    if (sy == 2) return (((s[0][0] + s[0][1]) + s[1][0]) + s[1][1]) * 0.25f;
+    return (s[0][0] + s[0][1]) * 0.5f;
   };
   const int nbx = pw / 16;
   for (int by = 0; by < ph / 16; ++by)

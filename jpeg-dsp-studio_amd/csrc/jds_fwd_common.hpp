@@ -26,11 +26,16 @@ __host__ __device__ __forceinline__ float luma32(float R, float G, float B) {
 __host__ __device__ __forceinline__ float luma32m(float R, float G, float B) {
   return fmaf(0.114f, B, fmaf(0.587f, G, fmaf(0.299f, R, -128.0f)));
 }
-__host__ __device__ __forceinline__ float cb32(float R, float G, float B) {
-  return fmaf(-0.168736f, R, fmaf(-0.331264f, G, fmaf(0.5f, B, 128.0f)));
+// Cb - 128 and Cr - 128: the reference's +128 and the block's level shift
+// cancel, so the chroma chains (prefilter, area average) run on |x| <= 128 and
+// end without a subtraction: every rounding fwd_input_error prices has half the
+// magnitude, and the Gaussian's taps, which sum to 1 only to rounding, add
+// 128 |S^2 - 1| there.  0.5 * x is exact.
+__host__ __device__ __forceinline__ float cb32m(float R, float G, float B) {
+  return fmaf(-0.168736f, R, fmaf(-0.331264f, G, 0.5f * B));
 }
-__host__ __device__ __forceinline__ float cr32(float R, float G, float B) {
-  return fmaf(-0.081312f, B, fmaf(-0.418688f, G, fmaf(0.5f, R, 128.0f)));
+__host__ __device__ __forceinline__ float cr32m(float R, float G, float B) {
+  return fmaf(-0.081312f, B, fmaf(-0.418688f, G, 0.5f * R));
 }
 
 // ---- exact fp64 recomputation of one block column from global memory ----

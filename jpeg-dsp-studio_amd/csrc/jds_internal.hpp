@@ -29,7 +29,20 @@ struct Geo {
                         // the general-geometry kernels of jds_gen.hip run instead of the tiled ones
   int afx, afy;         // gen: cv2's integer-scale INTER_AREA window (e.g. 3 x 2 for a 3-row 4:2:0
                         // frame), 0 when the fractional tables apply (area_fast_scales)
+  int inv_yoff;         // luma rows the inverse's 4:2:0 tiles start above 64 ty (inv_tile_yoff): 0 or 8
 };
+
+// The inverse's 4:2:0 tiles (64 x 128 luma, jds_inv_common.hpp) read a chroma
+// window of 34 sample rows: aligned to 64 ty those rows come from six block
+// rows (the top and bottom ring blocks give one row each).  Tiles that start
+// one luma block row higher, at 64 ty - 8, need rows [32 ty - 5, 32 ty + 28]:
+// five block rows (rows 3..7 of the top one, 0..4 of the bottom one), a sixth
+// of the chroma block tasks less.  Taken only when the raised tiles still
+// cover the frame with the same number of tile rows (1080 = 56 + 16 x 64: yes;
+// 64, 128: no); block row -1 of the first tile row does not exist.
+__host__ __device__ inline int inv_tile_yoff(int mode, int H) {
+  return mode == M420 && (H + 8 + 63) / 64 == (H + 63) / 64 ? 8 : 0;
+}
 
 // One destination index of cv2's fractional INTER_AREA table on one axis
 // (OpenCV computeResizeAreaTab): up to 4 source indices and their float

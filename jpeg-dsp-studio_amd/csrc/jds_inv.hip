@@ -8,7 +8,8 @@
 // NumPy colour expressions), FP contraction off: bytes are bit-identical.
 //
 // Work decomposition (one workgroup per TH x TW pixel tile, tiles laid from the
-// top-left corner):
+// top-left corner; 4:2:0 tiles start 8 luma rows higher where that adds no
+// tile row, so their chroma window takes five block rows, not six: InvRows):
 //   1. chroma, both planes: the tile's chroma blocks plus the ring the
 //      bilinear upsample reaches into.  Column (axis-0) passes run one thread
 //      per block column, straight from the int16 coefficients in HBM/L2 into
@@ -83,6 +84,34 @@ int inv_tiles(int mode, int H, int W) {
   int tx;
   return mode == M420 ? inv_tiles_t<M420>(H, W, &tx)
                       : (mode == M422 ? inv_tiles_t<M422>(H, W, &tx) : inv_tiles_t<M444>(H, W, &tx));
+}
+
+// The rows of tile row ty of an H-row frame as the tile bodies take them
+// (InvRows with inv_tile_yoff's offset; jds_selftest_inv_rows): out = yoff,
+// tile rows, first luma row, luma rows, first chroma block row, chroma block
+// rows, the window's first sample row, its sample rows.
+template <int MODE>
+static void inv_rows_t(int H, int ty, int* out) {
+  const int yoff = inv_tile_yoff(MODE, H);
+  const InvRows<MODE> r(ty, yoff);
+  out[0] = yoff;
+  out[1] = (H + Inv<MODE>::TH - 1) / Inv<MODE>::TH;
+  out[2] = r.y0;
+  out[3] = Inv<MODE>::TH;
+  out[4] = r.cby0;
+  out[5] = r.ncbr;
+  out[6] = r.cwy0;
+  out[7] = Inv<MODE>::CWR;
+}
+void inv_rows(int mode, int H, int ty, int* out) {
+  if (mode == M420) inv_rows_t<M420>(H, ty, out);
+  else if (mode == M422) inv_rows_t<M422>(H, ty, out);
+  else inv_rows_t<M444>(H, ty, out);
+}
+int inv_rows_need(int mode, int H, int ty, int by, int r) {
+  const int yoff = inv_tile_yoff(mode, H);
+  return mode == M420 ? InvRows<M420>(ty, yoff).need(by, r)
+                      : (mode == M422 ? InvRows<M422>(ty, yoff).need(by, r) : InvRows<M444>(ty, yoff).need(by, r));
 }
 
 template <int MODE>

@@ -34,6 +34,29 @@ struct Inv {
   static_assert(NCB * 8 <= NT && NROW <= NT && NYB % RB == 0, "one round per chroma plane");
 };
 
+// Rows of tile row ty whose tiles start `yoff` luma rows above ty * TH
+// (Geo::inv_yoff: 0, or 8 at 4:2:0, see inv_tile_yoff): the first luma row
+// (block row y0 / 8 may be -1: no such blocks), the first chroma block row and
+// the number of chroma block rows whose samples the window holds, and the
+// window's first sample row.  A block's row r is in the window when
+// need(by, r); with yoff = 0 that is the last row of the top ring blocks, the
+// first of the bottom ones and everything between, with yoff = 8 rows 3..7 of
+// the top block row and 0..4 of the bottom one.
+template <int MODE>
+struct InvRows {
+  int y0, cby0, ncbr, cwy0;
+  __host__ __device__ __forceinline__ InvRows(int ty, int yoff) {
+    using I = Inv<MODE>;
+    y0 = ty * I::TH - yoff;
+    cby0 = ty * (I::TH / (8 * I::SY)) - I::RY;
+    ncbr = I::CBR - (yoff ? 1 : 0);
+    cwy0 = y0 / I::SY - I::RY;  // (y0 is a multiple of 8: exact for y0 = -8 too)
+  }
+  __host__ __device__ __forceinline__ bool need(int by, int r) const {
+    return !Inv<MODE>::RY || (unsigned)(by * 8 + r - cwy0) < (unsigned)Inv<MODE>::CWR;
+  }
+};
+
 constexpr int MS = 72;  // doubles per block in the transpose buffer (64 + 8: conflict-free column writes)
 
 // Transpose-buffer slot of element (r, c) of a block: the 16-B pair c/2 of row r

@@ -200,26 +200,28 @@ __device__ __forceinline__ void inv2_tile(InvShared<MODE, XTRA>& sh, const Geo& 
 
   const int tid = threadIdx.x, lv = tid & 7, lb = tid >> 3;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int Y0 = ty * I::TH, X0 = tx * I::TW;
+  const InvRows<MODE> rows(ty, g.inv_yoff);
+  const int Y0 = rows.y0, X0 = tx * I::TW;
   const int16_t* cf = coeffs + (size_t)frame * g.cpf;
   if (tid < 64) s_q[tid] = (int)fq[frame].q[tid];  // Q is an integer in [1, 255]
   if (XTRA && tid == 0) s_sse = 0ull;
   __syncthreads();
 
   // ---- 1. chroma window ----------------------------------------------------
-  const int cby0 = Y0 / (8 * I::SY) - I::RY, cbx0 = X0 / (8 * I::SX) - I::RX;
-  const int cwy0 = Y0 / I::SY - I::RY, cwx0 = X0 / I::SX - I::RX;
+  const int cby0 = rows.cby0, cbx0 = X0 / (8 * I::SX) - I::RX;
+  const int cwy0 = rows.cwy0, cwx0 = X0 / I::SX - I::RX;
   // Each block's column pass and row pass run on the same 8 lanes (one wave),
   // whose LDS operations execute in order: no workgroup barrier until the
   // window is complete.  A top (bottom) ring block contributes only its last
-  // (first) row.
+  // (first) row; in tiles raised by a luma block row (InvRows) the top and
+  // bottom block rows contribute five rows each.
   // luma round 0's coefficients are requested before any chroma math
   auto luma_blk = [&](int r, int& by, int& bx) {
     const int blk = r * I::RB + lb;
     const int bi = blk / I::YBC, bj = blk - bi * I::YBC;
     by = Y0 / 8 + bi;
     bx = X0 / 8 + bj;
-    return by < g.nby && bx < g.nbx;
+    return by >= 0 && by < g.nby && bx < g.nbx;
   };
   Col16 lq;
   {
@@ -227,11 +229,11 @@ __device__ __forceinline__ void inv2_tile(InvShared<MODE, XTRA>& sh, const Geo& 
     const bool ok = luma_blk(0, by, bx);
     lq = load_col(cf, ((long long)by * g.nbx + bx) * 64, lv, ok);
   }
-  if (tid < I::NCB * 8) {
+  if (lb < rows.ncbr * I::CBC) {
     const int i = lb / I::CBC, j = lb - i * I::CBC;
     const int by = cby0 + i, bx = cbx0 + j;
     const bool bvalid = by >= 0 && bx >= 0 && by < g.ncy && bx < g.ncx;
-    const bool need = !I::RY || (i == 0 ? lv == 7 : (i == I::CBR - 1 ? lv == 0 : true));
+    const bool need = rows.need(by, lv);
     const long long boff = ((long long)by * g.ncx + bx) * 64;
     Col16 cq = load_col(cf + g.off_cb, boff, lv, bvalid);
 #pragma unroll 1

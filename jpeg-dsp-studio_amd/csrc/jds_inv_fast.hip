@@ -40,7 +40,9 @@
 //
 // Work decomposition and LDS layout are k_inv2's (jds_inv_common.hpp): one
 // workgroup per tile, chroma window (with the ring the upsample reaches into)
-// in LDS, Y in registers, one lane per 8-pixel row, 24-byte stores.
+// in LDS, Y in registers, one lane per 8-pixel row, 24-byte stores.  4:2:0
+// tiles start 8 luma rows above 64 ty where that adds no tile row (InvRows,
+// Geo::inv_yoff): five chroma block rows per window instead of six.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -352,21 +354,22 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   __shared__ unsigned long long s_sse;
   const int tid = threadIdx.x, lv = tid & 7, lb = tid >> 3;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int Y0 = ty * I::TH, X0 = tx * I::TW;
+  const InvRows<MODE> rows(ty, g.inv_yoff);
+  const int Y0 = rows.y0, X0 = tx * I::TW;
   const int16_t* cf = coeffs + (size_t)frame * g.cpf;
   // the tile's first coefficient loads are issued before the table set-up and
   // its barrier, so their latency overlaps it
   int qhi = 0, qlo = 0;  // max / min q this lane read (max |q| = max(qhi, -qlo))
 
   // ---- 1. chroma window: (clip(IDCT) - 128) of the blocks the tile reaches --
-  const int cby0 = Y0 / (8 * I::SY) - I::RY, cbx0 = X0 / (8 * I::SX) - I::RX;
-  const int cwy0 = Y0 / I::SY - I::RY, cwx0 = X0 / I::SX - I::RX;
+  const int cby0 = rows.cby0, cbx0 = X0 / (8 * I::SX) - I::RX;
+  const int cwy0 = rows.cwy0, cwx0 = X0 / I::SX - I::RX;
   auto luma_blk = [&](int r, int& by, int& bx) {
     const int blk = r * I::RB + lb;
     const int bi = blk / I::YBC, bj = blk - bi * I::YBC;
     by = Y0 / 8 + bi;
     bx = X0 / 8 + bj;
-    return by < g.nby && bx < g.nbx;
+    return by >= 0 && by < g.nby && bx < g.nbx;
   };
   auto table_setup = [&]() {
     if (tid < 64) {
@@ -390,9 +393,11 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     lq = load_col(cf, ((long long)by * g.nbx + bx) * 64, lv, ok);
   }
   // one chroma block task: column pass, and for the rows the tile needs the row
-  // pass, clip and window stores (plane p, block row i of the window)
-  auto chroma_task = [&](const int p, const int i, const int by, const int bx, const Col16& cur) {
-    const bool need = !I::RY || (i == 0 ? lv == 7 : (i == I::CBR - 1 ? lv == 0 : true));
+  // pass, clip and window stores (plane p; InvRows::need: a raised 4:2:0 tile
+  // takes five rows of its top and bottom block rows, an aligned one a single
+  // row of its ring blocks)
+  auto chroma_task = [&](const int p, const int by, const int bx, const Col16& cur) {
+    const bool need = rows.need(by, lv);
     fast_col(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
     if (need) {
       double c[8];
@@ -444,16 +449,16 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
 #pragma unroll 1
     for (int tt = lb; tt < NTASK; tt += I::RB) {  // (uniform per wave: RB lane groups, 8 per wave)
       const Col16 cur = cq;
-      const int pc = pp, ic = ii, byc = by, bxc = bx;
+      const int pc = pp, byc = by, bxc = bx;
       const bool okc = ok;
       if (tt + I::RB < NTASK) {
         off = tinfo(tt + I::RB, pp, ii, by, bx, ok);
         cq = load_col(cf + (pp ? g.off_cr : g.off_cb), off, lv, ok);
       }
-      if (okc) chroma_task(pc, ic, byc, bxc, cur);
+      if (okc) chroma_task(pc, byc, bxc, cur);
     }
   } else {
-    const bool ctask = tid < I::NCB * 8;
+    const bool ctask = lb < rows.ncbr * I::CBC;
     const int ci = lb / I::CBC, cj = lb - ci * I::CBC;
     const int cby = cby0 + ci, cbx = cbx0 + cj;
     const bool cvalid = ctask && cby >= 0 && cbx >= 0 && cby < g.ncy && cbx < g.ncx;
@@ -466,7 +471,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
       for (int p = 0; p < 2; ++p) {
         const Col16 cur = cq;
         if (p == 0) cq = load_col(cf + g.off_cr, cboff, lv, cvalid);
-        if (cvalid) chroma_task(p, ci, cby, cbx, cur);
+        if (cvalid) chroma_task(p, cby, cbx, cur);
       }
     }
   }
@@ -1000,9 +1005,11 @@ k_inv6_fix(const Geo g, const int tiles_x, const int16_t* __restrict__ coeffs, c
            uint8_t* __restrict__ rgb_out, const unsigned* __restrict__ fixcount, const uint2* __restrict__ fixlist) {
   __shared__ __attribute__((aligned(16))) InvShared<M420, 0> sh;
   const unsigned n = *fixcount;
+  Geo g0 = g;
+  g0.inv_yoff = 0;  // k_inv_fast6 lists tiles aligned to 64 ty (W6)
   for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {  // (uniform)
     const uint2 e = fixlist[i];
-    inv2_tile<M420, 0>(sh, g, tiles_x, 0, (int)e.x, (int)e.y, coeffs, fq, nullptr, rgb_out, nullptr, nullptr,
+    inv2_tile<M420, 0>(sh, g0, tiles_x, 0, (int)e.x, (int)e.y, coeffs, fq, nullptr, rgb_out, nullptr, nullptr,
                        nullptr, nullptr, 1);
     __syncthreads();  // the next tile reuses the shared arrays
   }

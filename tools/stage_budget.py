@@ -227,7 +227,7 @@ def fwd_budget():
     luma_line = at('column(s_y + by_t * 8 * TW', col1)
     chroma0 = luma_line + 1
     chroma1 = at('column(s_cd + (blk - C::NYB) * BS32', chroma0)
-    fcommon = func_ranges(os.path.join(CSRC, 'jds_fwd_common.hpp'), ['luma32m', 'cb32', 'cr32'])
+    fcommon = func_ranges(os.path.join(CSRC, 'jds_fwd_common.hpp'), ['luma32m', 'cb32m', 'cr32m'])
 
     def within(line, name, ranges=fr):
         a, b = ranges.get(name, (0, -1))
@@ -236,7 +236,7 @@ def fwd_budget():
     def stage_of(loc, bb):
         f, line = loc
         if f == 'jds_fwd_common.hpp':
-            return 'colour (luma32m / cb32 / cr32)'
+            return 'colour (luma32m / cb32m / cr32m)'
         if f == 'jds_device.hpp':
             return 'statistics flush (row sums)'
         if f != 'jds_fast.hip':
