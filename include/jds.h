@@ -852,7 +852,7 @@ int jds_selftest_coef_transform_dev(jds_ctx* ctx, const jds_jpeg_info* info, int
                                     int16_t* coeffs_out);
 
 /* Test-only: the whole decode on the host with the kernels' shared core
- * (csrc/jds_huffdec.hpp) and subsequences of subseq_bits bits (a multiple of 8,
+ * (csrc/jds_huffdec.hpp; the host model: csrc/jds_jpeg_parse.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation
  * rule.  coeffs: coeffs_cap int16 entries; rounds_out[3]: decode rounds of the
  * Y, Cb, Cr scans (0 for a scan with restart intervals).  No GPU. */

@@ -1539,18 +1539,17 @@ extern "C++" int inverse_of_decoded(jds_ctx* c, const jds_params* prm, int64_t H
   return rc;
 }
 
-// The plan's decode tables, built once from the DHT segments of its own header (hl bytes).
-static int plan_dec_tables(jds_plan* p, int hl) {
+// The plan's decode tables ([0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1), built once: its header
+// template carries the Annex K tables (ent_std_table: 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma).
+static int plan_dec_tables(jds_plan* p) {
   if (p->dec_tab.p) return JDS_OK;
-  std::vector<uint8_t> h((size_t)hl);
-  jds_jfif_info hi;
-  if (ent_header(p->qt, p->mode, p->g.H, p->g.W, h.data()) != hl ||
-      hd_parse(h.data(), hl, &hi, true, g_err, sizeof g_err) != JDS_OK)
-    return fail(JDS_EINVAL, "entropy decode: the plan's header template does not parse");
   HuffDecTab tabs[4];
-  for (int i = 0; i < 4; ++i)
-    if (!hi.huff[i].defined || hd_build(hi.huff[i].bits, hi.huff[i].vals, &tabs[i]) < 0)
-      return fail(JDS_EINVAL, "entropy decode: the plan's header template lacks a Huffman table");
+  const int std_idx[4] = {0, 2, 1, 3};
+  for (int i = 0; i < 4; ++i) {
+    const uint8_t *bits, *vals;
+    (void)ent_std_table(std_idx[i], &bits, &vals);
+    if (hd_build(bits, vals, &tabs[i]) < 0) return fail(JDS_EINVAL, "entropy decode: Annex K table %d does not build", i);
+  }
   HIP_TRY(p->dec_tab.ensure(sizeof tabs));
   HIP_TRY(hipMemcpy(p->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice));
   return JDS_OK;
@@ -1570,7 +1569,7 @@ int jds_plan_entropy_decode(jds_plan* p, const uint8_t* files, int64_t stride, c
   size_t sz[8];
   ent_sizes(p->g, p->n, sz);
   const int hl = (int)(sz[6] / (size_t)p->n);
-  if (int rc = plan_dec_tables(p, hl)) return rc;
+  if (int rc = plan_dec_tables(p)) return rc;
   const int n = p->n;
   if (n > 65535) return fail(JDS_ENOTSUP, "entropy decode: at most 65535 frames per call");
   HIP_TRY(p->dec_info.ensure(dec_hdr_bytes(n)));
@@ -1629,7 +1628,7 @@ int jds_plan_entropy_decode_rst(jds_plan* p, int32_t interval, const uint8_t* fi
   size_t sz[8];
   ent_sizes(p->g, n, sz);
   const int hl0 = (int)(sz[6] / (size_t)n), hl = hl0 + 6;
-  if (int rc = plan_dec_tables(p, hl0)) return rc;
+  if (int rc = plan_dec_tables(p)) return rc;
   if (p->rst_hdr_interval != interval) {
     std::vector<uint8_t> h((size_t)hl * (size_t)n);
     for (int i = 0; i < n; ++i)

@@ -10,18 +10,35 @@
 #include "jds_dec_jobs.hpp"
 #include "jds_entropy_mcu_dev.hpp"
 #include "jds_jpeg_ljt.hpp"
+#include "jds_jpeg_parse.hpp"
 #include "jds_xform_dev.hpp"
 
 extern "C" {
 
 // ------------------------------------------------------ entropy decoding --
 
-int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out) {
-  const int rc = hd_parse(data, len, out, false, g_err, sizeof g_err);
+// Parse under a profile (jds_jpeg_parse.hpp: HD_OWN is jds_jfif_parse's, HD_ANY
+// jds_jpeg_parse's), then the size the buffers' index arithmetic is made for.
+static int parse_file(const uint8_t* data, int64_t len, HdProfile prof, jds_jpeg_info* out) {
+  const int rc = hd_walk(data, len, prof, out, g_err, sizeof g_err);
   if (rc) return rc;
   if (out->H * out->W > (int64_t)1 << 28)
     return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
   return JDS_OK;
+}
+
+int jds_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out) { return parse_file(data, len, HD_ANY, out); }
+
+// The _jfif calls: the file parses under the own profile, the work runs on the
+// general info (the bodies of the _jpeg calls below), and the caller's struct
+// is that info's view (jfif_info_of), status and rounds included.
+int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out) {
+  if (!out) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info j;
+  const int rc = parse_file(data, len, HD_OWN, &j);
+  memset(out, 0, sizeof *out);
+  if (rc == JDS_OK) jfif_info_of(&j, out);
+  return rc;
 }
 
 static int check_coef_cap(const int16_t* coeffs, int64_t cap, int64_t needed) {
@@ -39,18 +56,42 @@ int jds_entropy_decode_info(int32_t* subseq_bits, int32_t* subseq_per_group) {
   return JDS_OK;
 }
 
-int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
-                         int32_t* rounds_out) {
+static int selftest_args(const int16_t* coeffs, const int32_t* rounds_out, int32_t subseq_bits) {
   if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
   if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
-  jds_jfif_info info;
-  int rc = jds_jfif_parse(data, len, &info);
+  return JDS_OK;
+}
+
+// A parsed file through the host model; rounds[3]: per scan in file order.
+static int host_decode_parsed(const uint8_t* data, const jds_jpeg_info* info, int32_t subseq_bits, int16_t* coeffs,
+                              int64_t coeffs_cap, int32_t* rounds) {
+  const int rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed);
   if (rc) return rc;
-  if ((rc = check_coef_cap(coeffs, coeffs_cap, info.coeffs_needed))) return rc;
-  rounds_out[0] = rounds_out[1] = rounds_out[2] = 0;
-  const uint32_t st = hd_host_decode(data, &info, subseq_bits, coeffs, rounds_out);
+  int lane_max;
+  rst_constants(&lane_max);
+  const uint32_t st = hd_jpeg_host_decode(data, info, subseq_bits, lane_max, coeffs, rounds);
   if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
   return JDS_OK;
+}
+
+int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  jds_jpeg_info info;
+  int rc;
+  if ((rc = selftest_args(coeffs, rounds_out, subseq_bits)) || (rc = parse_file(data, len, HD_ANY, &info))) return rc;
+  return host_decode_parsed(data, &info, subseq_bits, coeffs, coeffs_cap, rounds_out);
+}
+
+// rounds_out: per component (Y, Cb, Cr); an own-profile file may carry its scans in any order.
+int jds_selftest_huffdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
+                         int32_t* rounds_out) {
+  jds_jpeg_info info;
+  int rc;
+  if ((rc = selftest_args(coeffs, rounds_out, subseq_bits)) || (rc = parse_file(data, len, HD_OWN, &info))) return rc;
+  int32_t rounds[3] = {0, 0, 0};
+  rc = host_decode_parsed(data, &info, subseq_bits, coeffs, coeffs_cap, rounds);
+  for (int i = 0; i < 3; ++i) rounds_out[info.scan[i].component[0] - 1] = rounds[i];
+  return rc;
 }
 
 // A file's four decode tables ([0] DC 0, [1] DC 1, [2] AC 0, [3] AC 1; an
@@ -123,50 +164,6 @@ static int decode_dev(jds_ctx* c, const uint8_t* data, int64_t len, const jds_jf
   return JDS_OK;
 }
 
-// A parsed file of this library's profile into c->ent_cf.
-static int decode_jfif_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jfif_info* info) {
-  return decode_dev(c, data, len, info->huff, dec_jobs_of(info), nullptr, info->coeffs_needed, &info->status,
-                    &info->rounds);
-}
-
-int jds_decode_jfif(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
-                    jds_jfif_info* info) {
-  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
-  int rc = jds_jfif_parse(data, len, info);
-  if (rc) return rc;
-  if ((rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jfif_dev(c, data, len, info))) return rc;
-  HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
-  return JDS_OK;
-}
-
-// ------------------------------------------ files of either scan form --
-
-int jds_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out) {
-  const int rc = hd_jpeg_parse(data, len, out, g_err, sizeof g_err);
-  if (rc) return rc;
-  if (out->H * out->W > (int64_t)1 << 28)
-    return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)out->H, (long long)out->W);
-  return JDS_OK;
-}
-
-int jds_selftest_jpegdec(const uint8_t* data, int64_t len, int32_t subseq_bits, int16_t* coeffs, int64_t coeffs_cap,
-                         int32_t* rounds_out) {
-  if (!coeffs || !rounds_out) return fail(JDS_EINVAL, "null argument");
-  if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
-  jds_jpeg_info info;
-  int rc = jds_jpeg_parse(data, len, &info);
-  if (rc) return rc;
-  if ((rc = check_coef_cap(coeffs, coeffs_cap, info.coeffs_needed))) return rc;
-  int lane_max;
-  rst_constants(&lane_max);
-  const uint32_t st = hd_jpeg_host_decode(data, &info, subseq_bits, lane_max, coeffs, rounds_out);
-  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
-  return JDS_OK;
-}
-
-
 // A parsed file of either scan form into c->ent_cf.
 static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
   const HdMcu m = hd_jpeg_mcu(info);
@@ -174,16 +171,33 @@ static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpe
                     info->coeffs_needed, &info->status, &info->rounds);
 }
 
-int jds_decode_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
-                    jds_jpeg_info* info) {
-  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
-  int rc = jds_jpeg_parse(data, len, info);
-  if (rc) return rc;
+// jds_decode_jpeg / _jfif once the file is parsed.
+static int decode_parsed(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                         jds_jpeg_info* info) {
+  int rc;
   if ((rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
   HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
   return JDS_OK;
+}
+
+int jds_decode_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jpeg_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  const int rc = parse_file(data, len, HD_ANY, info);
+  return rc ? rc : decode_parsed(c, data, len, coeffs, coeffs_cap, info);
+}
+
+int jds_decode_jfif(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                    jds_jfif_info* info) {
+  if (!c || !data || !info) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info j;
+  int rc = parse_file(data, len, HD_OWN, &j);
+  if (rc) return rc;
+  rc = decode_parsed(c, data, len, coeffs, coeffs_cap, &j);
+  jfif_info_of(&j, info);  // (also where the coefficient buffer is too small)
+  return rc;
 }
 
 // The parameter block of the plan's inverse for a file of 8x8 blocks with one quantisation table.
@@ -197,11 +211,9 @@ static jds_params params_of_file(int32_t subsampling, const double* qtable) {
   return prm;
 }
 
-int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
-                        int16_t* coeffs, jds_jpeg_info* info) {
-  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
-  int rc = jds_jpeg_parse(data, len, info);
-  if (rc) return rc;
+// jds_decompress_jpeg / _jfif once the file is parsed (an own-profile file passes the first two checks).
+static int decompress_parsed(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                             int16_t* coeffs, jds_jpeg_info* info) {
   if (info->subsampling == JDS_SS_GRAY)
     return fail(JDS_ENOTSUP, "the plan's inverse takes three components: this is a grayscale file "
                              "(jds_jpeg_to_rgb reconstructs it)");
@@ -212,10 +224,29 @@ int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* r
   const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
   if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
   const jds_params prm = params_of_file(info->subsampling, info->qtable[0]);
+  int rc;
   if ((rc = check_tables(&prm))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
   return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
+}
+
+int jds_decompress_jpeg(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jpeg_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  const int rc = parse_file(data, len, HD_ANY, info);
+  return rc ? rc : decompress_parsed(c, data, len, rgb_out, rgb_cap, coeffs, info);
+}
+
+int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                        int16_t* coeffs, jds_jfif_info* info) {
+  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info j;
+  int rc = parse_file(data, len, HD_OWN, &j);
+  if (rc) return rc;
+  rc = decompress_parsed(c, data, len, rgb_out, rgb_cap, coeffs, &j);
+  jfif_info_of(&j, info);
+  return rc;
 }
 
 // ----------------------------------- foreign files to pixels (k_jpeg_inv) --
@@ -1144,13 +1175,11 @@ int jds_selftest_jpeg_transcode(const uint8_t* data, int64_t len, int32_t optimi
   McuJob job;
   if ((rc = mcu_job_geo(&info, 0, &job))) return rc;
   if ((rc = mcu_job_splice(data, len, &job))) return rc;
-  int lane_max, sb, spg;
-  rst_constants(&lane_max);
+  int sb, spg;
   dec_constants(&sb, &spg);
   std::vector<int16_t> cf((size_t)info.coeffs_needed);
   int32_t rounds[3];
-  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
-  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  if ((rc = host_decode_parsed(data, &info, sb, cf.data(), info.coeffs_needed, rounds))) return rc;
   McuStdTabs std_tabs;
   mcu_std_tabs(&std_tabs);
   std::vector<uint8_t> file;
@@ -1168,13 +1197,11 @@ int jds_selftest_jpeg_transform(const uint8_t* data, int64_t len, int32_t op, in
   if ((rc = xf_prepare(data, len, &info, op, &x))) return rc;
   McuJob job;
   if ((rc = mcu_job_geo(x.op == JDS_XF_NONE ? &info : &x.plan.dst, 0, &job))) return rc;
-  int lane_max, sb, spg;
-  rst_constants(&lane_max);
+  int sb, spg;
   dec_constants(&sb, &spg);
   std::vector<int16_t> cf((size_t)info.coeffs_needed);
   int32_t rounds[3];
-  const uint32_t st = hd_jpeg_host_decode(data, &info, sb, lane_max, cf.data(), rounds);
-  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
+  if ((rc = host_decode_parsed(data, &info, sb, cf.data(), info.coeffs_needed, rounds))) return rc;
   if (x.op != JDS_XF_NONE) {
     std::vector<int16_t> dst((size_t)x.plan.dst.coeffs_needed);
     xf_host(x.plan.rec, cf.data(), dst.data());
@@ -1217,20 +1244,6 @@ int jds_selftest_jpeg_hist_dev(jds_ctx* c, const jds_jpeg_info* info, const int1
   // (the counters open the file's frame)
   HIP_TRY(hipMemcpy(counts, r.d.of, sizeof(uint32_t) * 2 * OPT_BINS, hipMemcpyDeviceToHost));
   return JDS_OK;
-}
-
-int jds_decompress_jfif(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
-                        int16_t* coeffs, jds_jfif_info* info) {
-  if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
-  int rc = jds_jfif_parse(data, len, info);
-  if (rc) return rc;
-  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
-  if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
-  const jds_params prm = params_of_file(info->subsampling, info->qtable);
-  if ((rc = check_tables(&prm))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jfif_dev(c, data, len, info))) return rc;
-  return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // jds_dec_jobs.hpp — from a parsed file to the decode kernels' work lists.
 //
-// Host only and HIP-free (plain C++, like the host side of jds_huffdec.hpp):
+// Host only and HIP-free (plain C++, like jds_jpeg_parse.hpp):
 // the index arithmetic that decides which bytes every decode workgroup reads
 // and where its blocks go.  The drivers in jds_abi_jpeg.hip call it for single
 // files and batches; tools/dec_jobs_san.cpp runs it under the host sanitizers.
@@ -11,7 +11,7 @@
 
 #include <vector>
 
-#include "jds_huffdec.hpp"
+#include "jds_jpeg_parse.hpp"
 
 namespace jds {
 
@@ -23,18 +23,6 @@ struct FilePlace {
   long long coef_off;  // its first coefficient, from the coeffs base
   long long dcs_off;   // interleaved: its first entry in the DC staging array
 };
-
-// The next RSTm marker of n bytes of scan data at or after byte a (n: none).
-inline long long next_rst(const uint8_t* d, long long a, long long n) {
-  while (a < n) {
-    const uint8_t* p = (const uint8_t*)memchr(d + a, 0xFF, (size_t)(n - a));
-    if (!p) break;
-    const long long e = p - d;
-    if (e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7) return e;
-    a = e + 1;
-  }
-  return n;
-}
 
 // What the builder reads of a parsed file.  A non-interleaved scan holds its
 // component's T.81 grid (A.2.2): coef_off is the component's plane within the
@@ -53,19 +41,6 @@ struct DecJobFile {
   int n_scans;
   DecJobScan scan[3];
 };
-
-inline DecJobFile dec_jobs_of(const jds_jfif_info* info) {
-  DecJobFile f{};
-  f.n_scans = info->n_scans;
-  for (int i = 0; i < info->n_scans; ++i) {
-    const jds_jfif_scan& s = info->scan[i];
-    const int comp = s.component - 1;
-    f.scan[i] = {s.dc_table, s.ac_table, s.restart_interval, s.restart_interval, s.offset, s.length,
-                 comp ? info->c_blocks : info->y_blocks,
-                 comp == 0 ? 0 : 64 * (info->y_blocks + (comp - 1) * info->c_blocks)};
-  }
-  return f;
-}
 
 inline DecJobFile dec_jobs_of(const jds_jpeg_info* info) {
   DecJobFile f{};
@@ -99,7 +74,7 @@ enum DecJobsResult {
 // an interval of at most lane_max blocks every interval goes to a lane of
 // k_dec_rst; with a larger one every interval is a descriptor of its own (byte
 // range, block count, destination), whose DC sum is the interval's.  On
-// anything but DEC_JOBS_OK msg holds the reason (hd_parse's convention) and the
+// anything but DEC_JOBS_OK msg holds the reason (hd_walk's convention) and the
 // vectors may hold part of the file's entries.
 inline DecJobsResult dec_jobs_build(const uint8_t* data, const DecJobFile& file, const FilePlace& pl, int lane_max,
                                     std::vector<DecScan>& sc, std::vector<RstIv>& ivs, char* msg, size_t cap) {

@@ -41,6 +41,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "jds_huffdec.hpp"
 #include "jds_internal.hpp"
 

@@ -1,8 +1,8 @@
-// jds_huffdec.hpp — baseline JFIF parsing and the Huffman decode core of the
-// self-synchronising entropy decoder (jds_entropy_dec.hip; DESIGN.md "Entropy
-// decode").  Compiles for host and device: the GPU lanes, the host model behind
-// jds_selftest_huffdec and the stand-alone sanitizer program
-// (tools/jfif_host_san.cpp) run this same code.  No HIP types here.  Scans
+// jds_huffdec.hpp — the Huffman decode core of the self-synchronising entropy
+// decoder (jds_entropy_dec.hip; DESIGN.md "Entropy decode").  Compiles for
+// host and device: the GPU lanes, the host model behind jds_selftest_huffdec
+// (jds_jpeg_parse.hpp, with the header parser) and the stand-alone sanitizer
+// program (tools/jfif_host_san.cpp) run this same code.  No HIP types here.  Scans
 // with restart intervals (DRI) decode one interval per lane (hd_rst_lane).
 //
 // Stream positions are bit positions in the STUFFED scan bytes: the reader
@@ -12,12 +12,8 @@
 // the block's index within its MCU (always 0 in a non-interleaved scan, whose
 // MCU is one block), packed as p << 16 | slot << 8 | k.
 #pragma once
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
-
-#include <vector>
 
 #include "jds.h"
 
@@ -41,6 +37,12 @@ enum : uint32_t {
   HD_DC_RANGE = JDS_DEC_DC_RANGE,
   HD_RESTART = JDS_DEC_RESTART
 };
+
+// row-major index of the k-th zigzag coefficient (the host model's sinks, the parser's tables)
+static const uint8_t HD_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                  58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // Decode table of one Huffman table: codes of up to 8 bits resolve through
 // lut[next 8 bits] = length << 8 | symbol (0: longer code); longer ones by the
@@ -468,693 +470,5 @@ struct HdIlRstSink {
     if (dst) dst[zz[k]] = (int16_t)v;
   }
 };
-
-// ------------------------------------------------------------- host side --
-
-static const uint8_t HD_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                  58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-inline int hd_fail(char* msg, size_t cap, int code, const char* fmt, ...) {
-  if (msg && cap) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-  }
-  return code;
-}
-
-// Block counts of the reference's planes (floor-sized chroma) for a baseline
-// frame; JDS_ENOTSUP where T.81's ceil-sized chroma gives another block grid
-// (mirrors ent_prepare, jds_abi.hip).
-inline int hd_block_counts(int64_t H, int64_t W, int mode, int64_t* ny, int64_t* nc, char* msg, size_t cap) {
-  const int64_t sy = mode == JDS_SS_420 ? 2 : 1, sx = mode == JDS_SS_444 ? 1 : 2;
-  const int64_t hc = H / sy, wc = W / sx;
-  if (hc < 1 || wc < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "%lldx%lld: empty subsampled chroma plane", (long long)H, (long long)W);
-  const int64_t ncy = (hc + 7) / 8, ncx = (wc + 7) / 8;
-  const int64_t jh = (H + sy - 1) / sy, jw = (W + sx - 1) / sx;
-  if ((jh + 7) / 8 != ncy || (jw + 7) / 8 != ncx)
-    return hd_fail(msg, cap, JDS_ENOTSUP, "%lldx%lld: the chroma block grid (%lldx%lld) differs from baseline JPEG's (%lldx%lld)",
-                   (long long)H, (long long)W, (long long)ncy, (long long)ncx, (long long)((jh + 7) / 8),
-                   (long long)((jw + 7) / 8));
-  *ny = ((H + 7) / 8) * ((W + 7) / 8);
-  *nc = ncy * ncx;
-  return JDS_OK;
-}
-
-// Parse a baseline JFIF of the profile this library writes (include/jds.h:
-// jds_jfif_parse), with or without restart intervals.  headers_only: stop without error where the data ends once
-// SOF0 and the four Huffman tables are known (the plan's header template).
-// Never reads outside [data, data + len).
-inline int hd_parse(const uint8_t* data, int64_t len, jds_jfif_info* out, bool headers_only, char* msg, size_t cap) {
-  if (!data || !out || len < 0) return hd_fail(msg, cap, JDS_EINVAL, "null argument");
-  memset(out, 0, sizeof *out);
-  if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return hd_fail(msg, cap, JDS_EINVAL, "not a JPEG file: SOI missing");
-  uint8_t qt[4][64];
-  bool qdef[4] = {false, false, false, false};
-  int tq = -1;
-  bool sof = false, seen[4] = {false, false, false, false};
-  int ri = 0;  // the restart interval in effect (DRI), 0: none
-  int64_t p = 2;
-  for (;;) {
-    if (p + 2 > len) {
-      if (headers_only && sof) break;
-      return hd_fail(msg, cap, JDS_EINVAL, "truncated file: EOI missing");
-    }
-    if (data[p] != 0xFF) return hd_fail(msg, cap, JDS_EINVAL, "marker expected at byte %lld", (long long)p);
-    const int m = data[p + 1];
-    if (m == 0xFF) {  // fill byte
-      ++p;
-      continue;
-    }
-    if (m == 0xD9) break;  // EOI
-    if (m >= 0xD0 && m <= 0xD7)
-      return hd_fail(msg, cap, JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
-    if (m == 0xD8 || m == 0x01 || m == 0x00)
-      return hd_fail(msg, cap, JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
-    if (p + 4 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
-    const int64_t ln = ((int64_t)data[p + 2] << 8) | data[p + 3];
-    if (ln < 2 || p + 2 + ln > len)
-      return hd_fail(msg, cap, JDS_EINVAL, "segment 0x%02X at byte %lld: length %lld reaches past the end of the file", m,
-                     (long long)p, (long long)ln);
-    const uint8_t* s = data + p + 4;
-    const int64_t sl = ln - 2;
-    if (m == 0xC0) {
-      if (sof) return hd_fail(msg, cap, JDS_EINVAL, "second SOF0");
-      if (sl < 6) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 too short");
-      if (s[0] != 8) return hd_fail(msg, cap, JDS_ENOTSUP, "sample precision %d (12-bit and other depths are not supported)", s[0]);
-      out->H = (s[1] << 8) | s[2];
-      out->W = (s[3] << 8) | s[4];
-      const int nf = s[5];
-      if (nf == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "grayscale files (one component) are not supported");
-      if (nf != 3) return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (three are supported)", nf);
-      if (sl != 6 + 3 * nf) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 length does not match its component count");
-      if (out->H < 1 || out->W < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
-      for (int c = 0; c < 3; ++c)
-        if (s[6 + 3 * c] != c + 1) return hd_fail(msg, cap, JDS_ENOTSUP, "component ids other than 1, 2, 3");
-      const int ys = s[7];
-      if (ys != 0x11 && ys != 0x21 && ys != 0x22)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "luma sampling %dx%d (1x1, 2x1 and 2x2 are supported)", ys >> 4, ys & 15);
-      if (s[10] != 0x11 || s[13] != 0x11) return hd_fail(msg, cap, JDS_ENOTSUP, "subsampled or oversampled chroma factors");
-      out->subsampling = ys == 0x11 ? JDS_SS_444 : (ys == 0x21 ? JDS_SS_422 : JDS_SS_420);
-      if (s[8] != s[11] || s[8] != s[14])
-        return hd_fail(msg, cap, JDS_ENOTSUP, "two quantisation tables in use (one is supported)");
-      tq = s[8];
-      if (tq > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", tq);
-      sof = true;
-    } else if ((m >= 0xC1 && m <= 0xCF) && m != 0xC4 && m != 0xC8) {
-      if (m == 0xCC || m >= 0xC9) return hd_fail(msg, cap, JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", m);
-      return hd_fail(msg, cap, JDS_ENOTSUP, "%s (SOF%d) is not supported: baseline SOF0 only", m == 0xC2 ? "progressive JPEG" : "this frame type", m - 0xC0);
-    } else if (m == 0xDD) {
-      if (ln != 4) return hd_fail(msg, cap, JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
-      ri = (s[0] << 8) | s[1];
-    } else if (m == 0xDB) {
-      int64_t q = 0;
-      while (q < sl) {
-        const int pq = s[q] >> 4, id = s[q] & 15;
-        if (pq == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "16-bit DQT is not supported");
-        if (pq != 0 || id > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DQT table header 0x%02X", s[q]);
-        if (q + 65 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DQT");
-        memcpy(qt[id], s + q + 1, 64);
-        qdef[id] = true;
-        q += 65;
-      }
-    } else if (m == 0xC4) {
-      int64_t q = 0;
-      while (q < sl) {
-        if (q + 17 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
-        const int tc = s[q] >> 4, th = s[q] & 15;
-        if (tc > 1 || th > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DHT table header 0x%02X", s[q]);
-        if (th > 1) return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table id %d (baseline has 0 and 1)", th);
-        int nv = 0;
-        for (int i = 0; i < 16; ++i) nv += s[q + 1 + i];
-        if (nv > 256) return hd_fail(msg, cap, JDS_EINVAL, "DHT: BITS sum to %d symbols (more than 256)", nv);
-        if (q + 17 + nv > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
-        jds_jfif_huff* h = &out->huff[2 * tc + th];
-        if (out->n_scans && h->defined)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table redefined between scans");
-        memset(h, 0, sizeof *h);
-        memcpy(h->bits, s + q + 1, 16);
-        memcpy(h->vals, s + q + 17, (size_t)nv);
-        h->n_vals = nv;
-        HuffDecTab t;
-        if (hd_build(h->bits, h->vals, &t) < 0)
-          return hd_fail(msg, cap, JDS_EINVAL, "DHT %d/%d: BITS over-subscribe the code space", tc, th);
-        h->defined = 1;
-        q += 17 + nv;
-      }
-    } else if (m == 0xDA) {
-      if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
-      if (sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
-      const int ns = s[0];
-      if (ns != 1) return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan (Ns = %d): non-interleaved scans only", ns);
-      if (sl != 6) return hd_fail(msg, cap, JDS_EINVAL, "SOS length does not match its component count");
-      const int comp = s[1], td = s[2] >> 4, ta = s[2] & 15;
-      if (comp < 1 || comp > 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d", comp);
-      if (seen[comp]) return hd_fail(msg, cap, JDS_ENOTSUP, "component %d has a second scan", comp);
-      if (s[3] != 0 || s[4] != 63 || s[5] != 0)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "spectral selection / successive approximation (progressive scan parameters)");
-      if (td > 1 || ta > 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS table ids %d/%d", td, ta);
-      if (!out->huff[td].defined || !out->huff[2 + ta].defined)
-        return hd_fail(msg, cap, JDS_EINVAL, "SOS refers to a Huffman table the file has not defined");
-      if (!qdef[tq]) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", tq);
-      if (out->n_scans >= 3) return hd_fail(msg, cap, JDS_EINVAL, "more than three scans");
-      seen[comp] = true;
-      int64_t e = p + 2 + ln;
-      // entropy-coded segment: up to the next marker (0xFF, then neither 0x00 nor a fill 0xFF);
-      // with a restart interval in effect its RSTm markers belong to it, m = i & 7 for the i-th
-      int64_t nm = 0;
-      for (;;) {
-        if (e + 1 >= len) return hd_fail(msg, cap, JDS_EINVAL, "truncated scan data: EOI missing");
-        if (data[e] == 0xFF && data[e + 1] != 0x00) {
-          const int r = data[e + 1] - 0xD0;
-          if (r < 0 || r > 7) break;
-          if (!ri)
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)",
-                           out->n_scans, r);
-          if (r != (int)(nm & 7))
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)",
-                           out->n_scans, r, (int)(nm & 7), ri);
-          ++nm;
-          e += 2;
-          continue;
-        }
-        ++e;
-      }
-      if (ri) {
-        int64_t ny = 0, nc = 0;
-        const int brc = hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, msg, cap);
-        if (brc) return brc;
-        const int64_t nb = comp == 1 ? ny : nc, need = (nb + ri - 1) / ri - 1;
-        if (nm != need)
-          return hd_fail(msg, cap, JDS_EINVAL, "scan %d: %lld restart markers where DRI %d needs %lld", out->n_scans,
-                         (long long)nm, ri, (long long)need);
-        if (data[e + 1] == 0xFF)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "scan %d: fill bytes (FF FF) in scan data with a restart interval (DRI %d)",
-                         out->n_scans, ri);
-      }
-      jds_jfif_scan* sc = &out->scan[out->n_scans++];
-      sc->component = comp;
-      sc->dc_table = td;
-      sc->ac_table = ta;
-      sc->restart_interval = ri;
-      sc->offset = p + 2 + ln;
-      sc->length = e - sc->offset;
-      p = e;
-      continue;
-    }
-    // APPn, COM and anything else with a length: skipped
-    p += 2 + ln;
-  }
-  if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
-  if (!headers_only && out->n_scans != 3) return hd_fail(msg, cap, JDS_EINVAL, "%d scans (one per component expected)", out->n_scans);
-  if (tq >= 0 && qdef[tq])
-    for (int k = 0; k < 64; ++k) out->qtable[HD_ZZ[k]] = (double)qt[tq][k];
-  else if (!headers_only)
-    return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", tq);
-  int64_t ny = 0, nc = 0;
-  const int rc = hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, msg, cap);
-  if (rc) return rc;
-  out->y_blocks = ny;
-  out->c_blocks = nc;
-  out->coeffs_needed = 64 * (ny + 2 * nc);
-  return JDS_OK;
-}
-
-inline const char* hd_status_text(uint32_t st) {
-  if (st & HD_BAD_HEADER) return "header mismatch or empty file";
-  if (st & HD_RESTART) return "restart markers differ from what the geometry and the restart interval require";
-  if (st & HD_BAD_CODE) return "invalid Huffman code in the scan data";
-  if (st & HD_K63) return "coefficient index beyond 63 in the scan data";
-  if (st & HD_OVERRUN) return "scan data overrun: the scan ends inside a symbol";
-  if (st & HD_COUNT) return "block count mismatch: the scan does not hold exactly its blocks";
-  if (st & HD_DC_RANGE) return "DC value outside int16";
-  return "ok";
-}
-
-struct HdHostSink {
-  int16_t* out;
-  void operator()(int64_t blk, int k, int v) const { out[blk * 64 + HD_ZZ[k]] = (int16_t)v; }
-};
-
-// One scan on the host, a loop standing in for the lanes: subsequences of S
-// bits, the propagation rule of the kernels (entry[i + 1] <- exit[i], changed
-// entries decode again), block prefix, write pass, DC prefix sum.  out:
-// nblocks x 64, zeroed here.  *rounds = decode rounds run.  Returns status bits.
-template <class TC, class Sink>
-inline uint32_t hd_host_sync(const uint8_t* d, int64_t n, const TC& tc, int64_t S, int64_t nblocks, Sink&& sink,
-                             int32_t* rounds);
-
-inline uint32_t hd_host_scan(const uint8_t* d, int64_t n, const HuffDecTab* dc, const HuffDecTab* ac, int64_t S,
-                             int64_t nblocks, int16_t* out, int32_t* rounds) {
-  memset(out, 0, sizeof(int16_t) * 64 * (size_t)nblocks);
-  uint32_t st = hd_host_sync(d, n, HdPlain{dc, ac}, S, nblocks, HdHostSink{out}, rounds);
-  int32_t acc = 0;
-  for (int64_t b = 0; b < nblocks; ++b) {
-    acc += out[64 * b];
-    if (acc < -32768 || acc > 32767) st |= HD_DC_RANGE;
-    out[64 * b] = (int16_t)acc;
-  }
-  return st;
-}
-
-// The rounds and the write pass of hd_host_scan for any table choice and sink
-// (the caller zeroes the output and sums the DC differences).
-template <class TC, class Sink>
-inline uint32_t hd_host_sync(const uint8_t* d, int64_t n, const TC& tc, int64_t S, int64_t nblocks, Sink&& sink,
-                             int32_t* rounds) {
-  const HdMemSrc src{d, n};
-  const int64_t nbits = 8 * n;
-  const int64_t nsub = nbits ? (nbits + S - 1) / S : 1;
-  std::vector<uint64_t> entry((size_t)nsub), exitv((size_t)nsub, HD_NONE);
-  std::vector<uint32_t> nblk((size_t)nsub, 0u);
-  std::vector<char> need((size_t)nsub, 1);
-  for (int64_t i = 0; i < nsub; ++i) entry[(size_t)i] = i ? hd_guess(src, i * S) : 0;
-  int32_t r = 0;
-  for (;;) {
-    bool any = false;
-    for (int64_t i = 0; i < nsub; ++i)
-      if (need[(size_t)i]) {
-        exitv[(size_t)i] = hd_sync_lane(src, tc, entry[(size_t)i], (uint64_t)((i + 1) * S), nblk[(size_t)i]);
-        any = true;
-      }
-    if (!any) break;
-    ++r;
-    if (r > nsub) break;  // cannot happen: entries 0..r are settled after round r
-    for (int64_t i = nsub - 1; i >= 1; --i) {
-      const uint64_t c = exitv[(size_t)i - 1];
-      need[(size_t)i] = c != HD_NONE && c != entry[(size_t)i];
-      if (need[(size_t)i]) entry[(size_t)i] = c;
-    }
-    need[0] = 0;
-  }
-  *rounds = r;
-  uint32_t st = 0;
-  int64_t b0 = 0;
-  for (int64_t i = 0; i < nsub; ++i) {
-    st |= hd_write_lane(src, tc, entry[(size_t)i], (uint64_t)((i + 1) * S), b0, nblocks, i == nsub - 1, sink);
-    b0 += nblk[(size_t)i];
-  }
-  return st;
-}
-
-// DC differences -> values inside the lane of one restart interval, judged
-// against int16 (the prediction starts from 0 at every interval).
-struct HdRstHostSink {
-  int16_t* out;
-  int32_t acc = 0;
-  bool bad = false;
-  void operator()(int64_t blk, int k, int v) {
-    if (k == 0) {
-      acc += v;
-      bad = bad || acc < -32768 || acc > 32767;
-      v = acc;
-    }
-    out[blk * 64 + HD_ZZ[k]] = (int16_t)v;
-  }
-};
-
-// One scan with restart interval ri on the host, a loop standing in for the
-// lanes of k_dec_rst: the parser checked the markers' number and order, so
-// interval i lies between markers i - 1 and i.  out: nblocks x 64, zeroed here.
-inline uint32_t hd_host_scan_rst(const uint8_t* d, int64_t n, const HuffDecTab* dc, const HuffDecTab* ac, int64_t ri,
-                                 int64_t nblocks, int16_t* out) {
-  memset(out, 0, sizeof(int16_t) * 64 * (size_t)nblocks);
-  uint32_t st = 0;
-  int64_t a = 0, blk0 = 0;
-  while (blk0 < nblocks) {
-    int64_t e = a;
-    while (e < n && !(d[e] == 0xFF && e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
-    const int64_t nb = nblocks - blk0 < ri ? nblocks - blk0 : ri;
-    HdRstHostSink sink{out};
-    st |= hd_rst_lane(HdMemSrc{d + a, e - a}, HdPlain{dc, ac}, blk0, nb, sink);
-    if (sink.bad) st |= HD_DC_RANGE;
-    blk0 += nb;
-    if (e >= n) break;
-    a = e + 2;
-  }
-  if (blk0 < nblocks) st |= HD_RESTART;  // (the parser's marker count rules this out)
-  return st;
-}
-
-// A whole parsed file on the host (jds_selftest_huffdec, tools/jfif_host_san.cpp).
-// coeffs: info->coeffs_needed int16 in the reference layout.  rounds[3]: per
-// component (Y, Cb, Cr).
-inline uint32_t hd_host_decode(const uint8_t* data, const jds_jfif_info* info, int64_t S, int16_t* coeffs,
-                               int32_t* rounds) {
-  uint32_t st = 0;
-  for (int i = 0; i < info->n_scans; ++i) {
-    const jds_jfif_scan& sc = info->scan[i];
-    HuffDecTab dc, ac;
-    if (hd_build(info->huff[sc.dc_table].bits, info->huff[sc.dc_table].vals, &dc) < 0 ||
-        hd_build(info->huff[2 + sc.ac_table].bits, info->huff[2 + sc.ac_table].vals, &ac) < 0)
-      return HD_BAD_HEADER;
-    const int c = sc.component - 1;
-    const int64_t nb = c ? info->c_blocks : info->y_blocks;
-    const int64_t off = c == 0 ? 0 : 64 * (info->y_blocks + (c - 1) * info->c_blocks);
-    if (sc.restart_interval > 0) {  // every interval a stream of its own: no propagation rounds
-      st |= hd_host_scan_rst(data + sc.offset, sc.length, &dc, &ac, sc.restart_interval, nb, coeffs + off);
-      rounds[c] = 0;
-    } else {
-      st |= hd_host_scan(data + sc.offset, sc.length, &dc, &ac, S, nb, coeffs + off, rounds + c);
-    }
-  }
-  return st;
-}
-
-// --------------------------------------------------- interleaved files --
-
-// Parse a baseline JPEG of either scan form (include/jds.h: jds_jpeg_parse).
-// Never reads outside [data, data + len).
-inline int hd_jpeg_parse(const uint8_t* data, int64_t len, jds_jpeg_info* out, char* msg, size_t cap) {
-  if (!data || !out || len < 0) return hd_fail(msg, cap, JDS_EINVAL, "null argument");
-  memset(out, 0, sizeof *out);
-  if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return hd_fail(msg, cap, JDS_EINVAL, "not a JPEG file: SOI missing");
-  uint8_t qt[4][64];
-  bool qdef[4] = {false, false, false, false};
-  bool sof = false, seen[4] = {false, false, false, false};
-  int ri = 0;
-  int ncomp = 3, gray_id = 0;  // a one-component frame: its component id as written (the SOS must name it)
-  int64_t p = 2;
-  for (;;) {
-    if (p + 2 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated file: EOI missing");
-    if (data[p] != 0xFF) return hd_fail(msg, cap, JDS_EINVAL, "marker expected at byte %lld", (long long)p);
-    const int m = data[p + 1];
-    if (m == 0xFF) {  // fill byte
-      ++p;
-      continue;
-    }
-    if (m == 0xD9) break;  // EOI
-    if (m >= 0xD0 && m <= 0xD7)
-      return hd_fail(msg, cap, JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
-    if (m == 0xD8 || m == 0x01 || m == 0x00)
-      return hd_fail(msg, cap, JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
-    if (p + 4 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
-    const int64_t ln = ((int64_t)data[p + 2] << 8) | data[p + 3];
-    if (ln < 2 || p + 2 + ln > len)
-      return hd_fail(msg, cap, JDS_EINVAL, "segment 0x%02X at byte %lld: length %lld reaches past the end of the file", m,
-                     (long long)p, (long long)ln);
-    const uint8_t* s = data + p + 4;
-    const int64_t sl = ln - 2;
-    if (m == 0xC0) {
-      if (sof) return hd_fail(msg, cap, JDS_EINVAL, "second SOF0");
-      if (sl < 6) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 too short");
-      if (s[0] != 8) return hd_fail(msg, cap, JDS_ENOTSUP, "sample precision %d (12-bit and other depths are not supported)", s[0]);
-      out->H = (s[1] << 8) | s[2];
-      out->W = (s[3] << 8) | s[4];
-      const int nf = s[5];
-      if (nf != 1 && nf != 3) return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (one or three are supported)", nf);
-      if (sl != 6 + 3 * nf) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 length does not match its component count");
-      if (out->H < 1 || out->W < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
-      if (nf == 1) {
-        // grayscale: any component id; the sampling byte is checked and then ignored, since a
-        // one-component scan is never interleaved and holds ceil(W/8) x ceil(H/8) blocks (T.81 A.2.2)
-        const int h1 = s[7] >> 4, v1 = s[7] & 15;
-        if (h1 < 1 || h1 > 4 || v1 < 1 || v1 > 4)
-          return hd_fail(msg, cap, JDS_EINVAL, "sampling factors %dx%d (1..4 each)", h1, v1);
-        if (s[8] > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", s[8]);
-        ncomp = 1;
-        gray_id = s[6];
-        out->subsampling = JDS_SS_GRAY;
-        out->tq[0] = s[8];
-        out->hs[0] = out->vs[0] = 1;
-        out->grid_cols[0] = out->mcu_cols = (out->W + 7) / 8;
-        out->grid_rows[0] = out->mcu_rows = (out->H + 7) / 8;
-        out->coeffs_needed = 64 * out->grid_cols[0] * out->grid_rows[0];
-        out->single_table = 1;
-        out->blocks_per_mcu = 1;
-        sof = true;
-        p += 2 + ln;
-        continue;
-      }
-      for (int c = 0; c < 3; ++c)
-        if (s[6 + 3 * c] != c + 1) return hd_fail(msg, cap, JDS_ENOTSUP, "component ids other than 1, 2, 3");
-      const int ys = s[7];
-      if (ys != 0x11 && ys != 0x21 && ys != 0x22)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "luma sampling %dx%d (1x1, 2x1 and 2x2 are supported)", ys >> 4, ys & 15);
-      if (s[10] != 0x11 || s[13] != 0x11) return hd_fail(msg, cap, JDS_ENOTSUP, "subsampled or oversampled chroma factors");
-      out->subsampling = ys == 0x11 ? JDS_SS_444 : (ys == 0x21 ? JDS_SS_422 : JDS_SS_420);
-      const int hmax = ys >> 4, vmax = ys & 15;
-      for (int c = 0; c < 3; ++c) {
-        out->tq[c] = s[8 + 3 * c];
-        if (out->tq[c] > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", out->tq[c]);
-        out->hs[c] = c ? 1 : hmax;
-        out->vs[c] = c ? 1 : vmax;
-        const int64_t xc = (out->W * out->hs[c] + hmax - 1) / hmax, yc = (out->H * out->vs[c] + vmax - 1) / vmax;
-        out->grid_cols[c] = (xc + 7) / 8;
-        out->grid_rows[c] = (yc + 7) / 8;
-        out->coeffs_needed += 64 * out->grid_cols[c] * out->grid_rows[c];
-      }
-      out->single_table = out->tq[0] == out->tq[1] && out->tq[0] == out->tq[2];
-      out->blocks_per_mcu = hmax * vmax + 2;
-      out->mcu_cols = (out->W + 8 * hmax - 1) / (8 * hmax);
-      out->mcu_rows = (out->H + 8 * vmax - 1) / (8 * vmax);
-      int64_t ny = 0, nc = 0;
-      out->reference_grid = hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, nullptr, 0) == JDS_OK;
-      sof = true;
-    } else if ((m >= 0xC1 && m <= 0xCF) && m != 0xC4 && m != 0xC8) {
-      if (m == 0xCC || m >= 0xC9) return hd_fail(msg, cap, JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", m);
-      return hd_fail(msg, cap, JDS_ENOTSUP, "%s (SOF%d) is not supported: baseline SOF0 only", m == 0xC2 ? "progressive JPEG" : "this frame type", m - 0xC0);
-    } else if (m == 0xDD) {
-      if (ln != 4) return hd_fail(msg, cap, JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
-      ri = (s[0] << 8) | s[1];
-    } else if (m == 0xDB) {
-      int64_t q = 0;
-      while (q < sl) {
-        const int pq = s[q] >> 4, id = s[q] & 15;
-        if (pq == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "16-bit DQT is not supported");
-        if (pq != 0 || id > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DQT table header 0x%02X", s[q]);
-        if (q + 65 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DQT");
-        memcpy(qt[id], s + q + 1, 64);
-        qdef[id] = true;
-        q += 65;
-      }
-    } else if (m == 0xC4) {
-      int64_t q = 0;
-      while (q < sl) {
-        if (q + 17 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
-        const int tc = s[q] >> 4, th = s[q] & 15;
-        if (tc > 1 || th > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DHT table header 0x%02X", s[q]);
-        if (th > 1) return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table id %d (baseline has 0 and 1)", th);
-        int nv = 0;
-        for (int i = 0; i < 16; ++i) nv += s[q + 1 + i];
-        if (nv > 256) return hd_fail(msg, cap, JDS_EINVAL, "DHT: BITS sum to %d symbols (more than 256)", nv);
-        if (q + 17 + nv > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
-        jds_jfif_huff* h = &out->huff[2 * tc + th];
-        if (out->n_scans && h->defined)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table redefined between scans");
-        memset(h, 0, sizeof *h);
-        memcpy(h->bits, s + q + 1, 16);
-        memcpy(h->vals, s + q + 17, (size_t)nv);
-        h->n_vals = nv;
-        HuffDecTab t;
-        if (hd_build(h->bits, h->vals, &t) < 0)
-          return hd_fail(msg, cap, JDS_EINVAL, "DHT %d/%d: BITS over-subscribe the code space", tc, th);
-        h->defined = 1;
-        q += 17 + nv;
-      }
-    } else if (m == 0xDA) {
-      if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
-      if (sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
-      const int ns = s[0];
-      if (ncomp == 1 && ns != 1)
-        return hd_fail(msg, cap, JDS_EINVAL, "scan of %d components in a grayscale (one-component) frame", ns);
-      if (ncomp == 1 && out->n_scans)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "a second scan in a grayscale (one-component) file");
-      if (ns == 2)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan of two components (Ns = 2): one scan of three or three of one only");
-      if (ns != 1 && ns != 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS with %d components", ns);
-      if (sl != 4 + 2 * ns) return hd_fail(msg, cap, JDS_EINVAL, "SOS length does not match its component count");
-      if (out->interleaved || (ns == 3 && out->n_scans))
-        return hd_fail(msg, cap, JDS_ENOTSUP, "a mix of interleaved and non-interleaved scans");
-      if (out->n_scans >= 3) return hd_fail(msg, cap, JDS_EINVAL, "more than three scans");
-      jds_jpeg_scan* sc = &out->scan[out->n_scans];
-      memset(sc, 0, sizeof *sc);
-      for (int i = 0; i < ns; ++i) {
-        int comp = s[1 + 2 * i];
-        const int td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
-        if (ncomp == 1) {
-          if (comp != gray_id)
-            return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d, the grayscale frame's component is %d", comp, gray_id);
-          comp = 1;  // (the info counts components from 1; the file's own id stays in its header)
-        }
-        if (comp < 1 || comp > 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d", comp);
-        if (ns == 3 && comp != i + 1)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan whose components are not 1, 2, 3 in that order");
-        if (seen[comp]) return hd_fail(msg, cap, JDS_ENOTSUP, "component %d has a second scan", comp);
-        if (td > 1 || ta > 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS table ids %d/%d", td, ta);
-        if (!out->huff[td].defined || !out->huff[2 + ta].defined)
-          return hd_fail(msg, cap, JDS_EINVAL, "SOS refers to a Huffman table the file has not defined");
-        if (!qdef[out->tq[comp - 1]])
-          return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", out->tq[comp - 1]);
-        seen[comp] = true;
-        sc->component[i] = comp;
-        sc->dc_table[i] = td;
-        sc->ac_table[i] = ta;
-      }
-      const uint8_t* t = s + 1 + 2 * ns;
-      if (t[0] != 0 || t[1] != 63 || t[2] != 0)
-        return hd_fail(msg, cap, JDS_ENOTSUP, "spectral selection / successive approximation (progressive scan parameters)");
-      int64_t e = p + 2 + ln;
-      int64_t nm = 0;
-      for (;;) {
-        if (e + 1 >= len) return hd_fail(msg, cap, JDS_EINVAL, "truncated scan data: EOI missing");
-        if (data[e] == 0xFF && data[e + 1] != 0x00) {
-          const int r = data[e + 1] - 0xD0;
-          if (r < 0 || r > 7) break;
-          if (!ri)
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)",
-                           out->n_scans, r);
-          if (r != (int)(nm & 7))
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)",
-                           out->n_scans, r, (int)(nm & 7), ri);
-          ++nm;
-          e += 2;
-          continue;
-        }
-        ++e;
-      }
-      if (ri) {
-        const int c0 = sc->component[0] - 1;
-        const int64_t nmcu = ns == 3 ? out->mcu_cols * out->mcu_rows : out->grid_cols[c0] * out->grid_rows[c0];
-        const int64_t need = (nmcu + ri - 1) / ri - 1;
-        if (nm != need)
-          return hd_fail(msg, cap, JDS_EINVAL, "scan %d: %lld restart markers where DRI %d needs %lld", out->n_scans,
-                         (long long)nm, ri, (long long)need);
-        if (data[e + 1] == 0xFF)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "scan %d: fill bytes (FF FF) in scan data with a restart interval (DRI %d)",
-                         out->n_scans, ri);
-      }
-      sc->n_components = ns;
-      sc->restart_interval = ri;
-      sc->offset = p + 2 + ln;
-      sc->length = e - sc->offset;
-      out->interleaved = ns == 3;
-      ++out->n_scans;
-      p = e;
-      continue;
-    }
-    // APPn, COM and anything else with a length: skipped
-    p += 2 + ln;
-  }
-  if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
-  if (out->n_scans != (out->interleaved || ncomp == 1 ? 1 : 3))
-    return hd_fail(msg, cap, JDS_EINVAL, "%d scans (one interleaved scan or one per component expected)", out->n_scans);
-  for (int c = 0; c < ncomp; ++c)
-    for (int k = 0; k < 64; ++k) out->qtable[c][HD_ZZ[k]] = (double)qt[out->tq[c]][k];
-  return JDS_OK;
-}
-
-// The MCU descriptor of a parsed file's interleaved scan.
-inline HdMcu hd_jpeg_mcu(const jds_jpeg_info* info) {
-  HdMcu m;
-  memset(&m, 0, sizeof m);
-  m.bpm = info->blocks_per_mcu;
-  m.mcu_cols = (int32_t)info->mcu_cols;
-  m.mcu_rows = (int32_t)info->mcu_rows;
-  int slot = 0;
-  int64_t off = 0;
-  for (int c = 0; c < 3; ++c) {
-    m.hs[c] = info->hs[c];
-    m.vs[c] = info->vs[c];
-    m.gw[c] = (int32_t)info->grid_cols[c];
-    m.gh[c] = (int32_t)info->grid_rows[c];
-    m.first[c] = slot;
-    m.off[c] = off;
-    off += 64 * info->grid_cols[c] * info->grid_rows[c];
-    for (int j = 0; j < m.hs[c] * m.vs[c]; ++j, ++slot) {
-      m.comp[slot] = (uint8_t)c;
-      m.bx[slot] = (uint8_t)(j % m.hs[c]);
-      m.by[slot] = (uint8_t)(j / m.hs[c]);
-      m.dct[slot] = (uint8_t)info->scan[0].dc_table[c];
-      m.act[slot] = (uint8_t)(2 + info->scan[0].ac_table[c]);
-    }
-  }
-  return m;
-}
-
-// DC differences of an interleaved scan -> values (the host's k_dec_dc_mcu):
-// per component a running sum over the staging array in scan order, padding
-// blocks included, from 0 at blocks [b0, b1) (whole MCUs: a scan, or one
-// restart interval); kept blocks get their value.
-inline uint32_t hd_host_dc_mcu(const HdMcu* m, const int16_t* dcs, int64_t b0, int64_t b1, int16_t* coeffs) {
-  int32_t acc[3] = {0, 0, 0};
-  uint32_t st = 0;
-  for (int64_t n = b0; n < b1; ++n) {
-    int c;
-    int16_t* dst = hd_il_place(m, coeffs, n, c);
-    acc[c] += dcs[n];
-    if (acc[c] < -32768 || acc[c] > 32767) st |= HD_DC_RANGE;
-    if (dst) dst[0] = (int16_t)acc[c];
-  }
-  return st;
-}
-
-// A whole parsed file on the host (jds_selftest_jpegdec, tools/jfif_host_san.cpp):
-// non-interleaved scans as hd_host_decode over the T.81 grids, an interleaved
-// one with the lanes' rules: intervals of at most lane_max blocks one lane
-// each, longer ones (and a scan without intervals) through the rounds.
-// coeffs: info->coeffs_needed int16.  rounds[3]: per scan in file order.
-inline uint32_t hd_jpeg_host_decode(const uint8_t* data, const jds_jpeg_info* info, int64_t S, int64_t lane_max,
-                                    int16_t* coeffs, int32_t* rounds) {
-  uint32_t st = 0;
-  HuffDecTab tabs[4];
-  for (int i = 0; i < 4; ++i) {
-    memset(&tabs[i], 0, sizeof tabs[i]);
-    if (info->huff[i].defined && hd_build(info->huff[i].bits, info->huff[i].vals, &tabs[i]) < 0) return HD_BAD_HEADER;
-  }
-  rounds[0] = rounds[1] = rounds[2] = 0;
-  if (!info->interleaved) {
-    for (int i = 0; i < info->n_scans; ++i) {
-      const jds_jpeg_scan& sc = info->scan[i];
-      const int c = sc.component[0] - 1;
-      int64_t off = 0;
-      for (int j = 0; j < c; ++j) off += 64 * info->grid_cols[j] * info->grid_rows[j];
-      const int64_t nb = info->grid_cols[c] * info->grid_rows[c];
-      const HuffDecTab *dc = &tabs[sc.dc_table[0]], *ac = &tabs[2 + sc.ac_table[0]];
-      if (sc.restart_interval > 0)
-        st |= hd_host_scan_rst(data + sc.offset, sc.length, dc, ac, sc.restart_interval, nb, coeffs + off);
-      else
-        st |= hd_host_scan(data + sc.offset, sc.length, dc, ac, S, nb, coeffs + off, rounds + i);
-    }
-    return st;
-  }
-  const HdMcu m = hd_jpeg_mcu(info);
-  const HdIl tc{tabs, &m};
-  const jds_jpeg_scan& sc = info->scan[0];
-  const uint8_t* d = data + sc.offset;
-  const int64_t n = sc.length, nblocks = (int64_t)m.bpm * m.mcu_cols * m.mcu_rows;
-  memset(coeffs, 0, sizeof(int16_t) * (size_t)info->coeffs_needed);
-  std::vector<int16_t> dcs((size_t)nblocks, 0);
-  if (sc.restart_interval == 0) {
-    st |= hd_host_sync(d, n, tc, S, nblocks, HdIlSink{&m, coeffs, dcs.data(), HD_ZZ, 0}, rounds);
-    st |= hd_host_dc_mcu(&m, dcs.data(), 0, nblocks, coeffs);
-    return st;
-  }
-  const int64_t rib = (int64_t)sc.restart_interval * m.bpm;
-  int64_t a = 0, blk0 = 0;
-  while (blk0 < nblocks) {
-    int64_t e = a;
-    while (e < n && !(d[e] == 0xFF && e + 1 < n && d[e + 1] >= 0xD0 && d[e + 1] <= 0xD7)) ++e;
-    const int64_t nb = nblocks - blk0 < rib ? nblocks - blk0 : rib;
-    if (rib <= lane_max) {
-      HdIlRstSink sink{&m, coeffs, HD_ZZ, blk0};
-      st |= hd_rst_lane(HdMemSrc{d + a, e - a}, tc, 0, nb, sink);
-      if (sink.bad) st |= HD_DC_RANGE;
-    } else {
-      int32_t r = 0;
-      st |= hd_host_sync(d + a, e - a, tc, S, nb, HdIlSink{&m, coeffs, dcs.data(), HD_ZZ, blk0}, &r);
-      st |= hd_host_dc_mcu(&m, dcs.data(), blk0, blk0 + nb, coeffs);
-      rounds[0] = r > rounds[0] ? r : rounds[0];
-    }
-    blk0 += nb;
-    if (e >= n) break;
-    a = e + 2;
-  }
-  if (blk0 < nblocks) st |= HD_RESTART;
-  return st;
-}
 
 }  // namespace jds

@@ -235,3 +235,35 @@ def test_gpu_one_context_alternates_scan_forms():
         exp = (entropy.host_decode_jfif if jfif else entropy.host_decode_jpeg)(data)[0]
         assert np.array_equal(cf, exp)
     assert np.array_equal(got[0], got[-1])
+
+
+def test_gpu_own_profile_files_through_both_decode_calls():
+    """jds_decode_jfif runs on the general info like jds_decode_jpeg: a file with its scans in
+    the order Cr, Y, Cb (the component-to-plane mapping) and one with restart intervals give,
+    on one context, the host model's coefficients, status 0 and the same rounds through both
+    calls; decompress_jfif and decompress_jpeg return the same bytes."""
+    import ctypes as C
+    from jds import _abi, codec, entropy
+    from test_entropy_decode_cpu import codec_file
+    data, _, _ = codec_file(33, 47, '4:4:4', 50)
+    sos = data.index(b'\xff\xda')
+    parts = [data[s['offset'] - 10:s['offset'] + s['length']] for s in entropy.parse_jfif(data)['scans']]
+    shuffled = data[:sos] + parts[2] + parts[0] + parts[1] + b'\xff\xd9'
+    assert [s['component'] for s in entropy.parse_jfif(shuffled)['scans']] == [3, 1, 2]
+    ny, nc = rr.counts(40, 56, '4:2:0')
+    cf = np.random.default_rng(4056).integers(-20, 21, (ny + 2 * nc) * 64).astype(np.int16)
+    rst = rr.encode_jfif_rst(cf, 40, 56, '4:2:0', Q50, 7)[0]
+    assert np.array_equal(entropy.host_decode_jfif(rst)[0], cf)
+    with _abi.lease(0) as ctx:
+        for f in (shuffled, rst):
+            exp = entropy.host_decode_jfif(f)[0]
+            a, p, n = entropy._bytes_arg(f)
+            fi, ji = _abi.JfifInfo(), _abi.JpegInfo()
+            got_f, got_j = np.empty(exp.size, np.int16), np.empty(exp.size, np.int16)
+            _abi.check(_abi.lib().jds_decode_jfif(ctx.handle, p, n, got_f.ctypes.data, got_f.size, C.byref(fi)))
+            _abi.check(_abi.lib().jds_decode_jpeg(ctx.handle, p, n, got_j.ctypes.data, got_j.size, C.byref(ji)))
+            assert np.array_equal(got_f, exp) and np.array_equal(got_j, exp)
+            assert fi.status == 0 and ji.status == 0 and fi.rounds == ji.rounds
+            assert int(fi.coeffs_needed) == int(ji.coeffs_needed) == exp.size
+    for f in (shuffled, rst):
+        assert np.array_equal(codec.decompress_jfif(f), codec.decompress_jpeg(f))

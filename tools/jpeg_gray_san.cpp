@@ -11,7 +11,7 @@
 // every value 0x11..0x44 and the component id to several values, and drives --
 // every input in a heap block of exactly its length, every coefficient and
 // pixel array of exactly its size --
-//   * the parser (hd_jpeg_parse): the one-component fields of jds_jpeg_info;
+//   * the parser (csrc/jds_jpeg_parse.hpp: hd_jpeg_parse): the one-component fields of jds_jpeg_info;
 //   * the host decode model (hd_jpeg_host_decode): the written coefficients;
 //   * mcu_file_of / mcu_coeffs, jinv_args and the host tile loop of the gray
 //     inverse (jinv_host_image<JDS_SS_GRAY>);
@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "jds_entropy_mcu.hpp"
-#include "jds_huffdec.hpp"
+#include "jds_jpeg_parse.hpp"
 #include "jds_jpeg_inv.hpp"
 #include "jds_xform.hpp"
 

@@ -1,6 +1,6 @@
 // jpeg_splice_san.cpp — stand-alone host program over the transcode's header
 // splicer (csrc/jds_entropy_mcu.hpp: mcu_splice) and the parser beside it
-// (csrc/jds_huffdec.hpp: hd_jpeg_parse), for sanitizer runs:
+// (csrc/jds_jpeg_parse.hpp: hd_jpeg_parse), for sanitizer runs:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -Iinclude -Ijpeg-dsp-studio_amd/csrc tools/jpeg_splice_san.cpp -o jpeg_splice_san
@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "jds_entropy_mcu.hpp"
-#include "jds_huffdec.hpp"
+#include "jds_jpeg_parse.hpp"
 
 static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
 static uint32_t rnd() {
