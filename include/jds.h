@@ -851,6 +851,76 @@ int jds_selftest_jpeg_transform(const uint8_t* data, int64_t len, int32_t op, in
 int jds_selftest_coef_transform_dev(jds_ctx* ctx, const jds_jpeg_info* info, int32_t op, const int16_t* coeffs,
                                     int16_t* coeffs_out);
 
+/* The libjpeg encoding (DESIGN.md "libjpeg encoding"; definition:
+ * tests/libjpeg_fwd_ref.py): pixels -> the file libjpeg (libjpeg-turbo, hence
+ * Pillow's Image.save(quality=Q, subsampling=S, optimize=O)) writes with its
+ * default settings, byte for byte -- jccolor's 16-bit fixed-point RGB ->
+ * YCbCr, jcsample's h2v1 / h2v2 box downsampling (bias 0, 1, 0, 1, .. / 1, 2,
+ * 1, 2, .. by chroma column), level shift, the ISLOW forward DCT (jfdctint),
+ * division by 8 q rounded half away from zero, jpeg_set_quality's tables
+ * (luma id 0; Cb and Cr share id 1), then the transcode's writer above with its
+ * default prefix.  One kernel (k_jpeg_fwd / k_jpeg_fwd_batch,
+ * csrc/jds_jpeg_fwd.hip) writes the coefficients in jds_decode_jpeg's layout
+ * and the writer reads them there: they never leave the device.
+ *
+ * Edges: only the blocks of the T.81 grids are computed (the writer pads to
+ *   whole MCUs with its dummy blocks, as jccoefct does).  A sample beyond the
+ *   image is the image's edge pixel, with one exception: libjpeg pads the image
+ *   to an even number of rows only, downsamples, and then replicates the last
+ *   DOWNSAMPLED row, so the rows of a 4:2:0 chroma plane below row
+ *   ceil(H / 2) - 1 repeat that row.
+ * Scope: ISLOW, no smoothing, 8 bits, one interleaved scan without restart
+ *   intervals, JFIF 1.01 header with density 1 x 1; 4:4:4, 4:2:2, 4:2:0 and
+ *   grayscale (an H x W one-channel image; SOF0 with Nf = 1, id 1, 0x11).
+ * Image bytes: packed, rows H * W * 3 (gray: H * W) with no padding; the
+ *   pointer needs no alignment.  A device image is read by aligned words that
+ *   each hold at least one byte of the image, and nothing else outside it.
+ *
+ * jds_jpeg_quality_info: host only.  Fills H, W, subsampling, the sampling
+ *   factors, grids, MCU fields, tq = (0, 1, 1), qtable and coeffs_needed of an
+ *   image encoded at `quality`; scans and Huffman tables stay zero.  quality
+ *   outside 1..100, H or W outside 1..65535 (or H * W above 2^28), or an unknown
+ *   subsampling: JDS_EINVAL naming the argument.
+ * jds_jpeg_forward_dev: one asynchronous launch on `stream`; nothing is uploaded
+ *   or read back.  jds_jpeg_render_dev's checks of tables (integers in
+ *   [1, 255], any: not only jds_jpeg_quality_info's) and grids.  rgb_dev: the
+ *   image; coeffs_dev: coeffs_needed int16, 16-byte aligned (JDS_EINVAL
+ *   otherwise); nothing else is written.
+ * jds_rgb_to_jpeg: one image from host memory or (rgb_on_device != 0) memory of
+ *   the context's device -> the file in host memory.  *out_len and the
+ *   too-small-buffer contract are jds_encode_jpeg's.  Synchronous.
+ * jds_rgb_batch_to_jpeg: image i is bytes [rgb_off, rgb_off + H * W * 3 (gray:
+ *   H * W)) of rgb_base (any offset: what jds_jpeg_batch_to_rgb reports as
+ *   rgb_off serves) with its own size, quality and subsampling.  The forward
+ *   launches, one per mode present, then one set of writer launches over all
+ *   images.  items_out, the packing at multiples of 256, out_cap / *out_bytes and
+ *   out_on_device: jds_jpeg_batch_transcode's contract (status is always 0,
+ *   interleaved 1 except for grayscale).  An item with a bad argument
+ *   (jds_jpeg_quality_info's checks, a negative rgb_off) gets rc JDS_EINVAL,
+ *   takes no space and no other file depends on it; jds_last_error names the
+ *   first.  n == 0 is valid.
+ * jds_selftest_jpeg_forward: test-only, host only: the tile core
+ *   (csrc/jds_jpeg_fwd.hpp) in a host tile loop; coeffs_out: coeffs_needed
+ *   int16, 16-byte aligned.  jds_selftest_jpeg_fwd_quant: the core's
+ *   division-free quantiser at table entry q for c = 0 .. n - 1 (out[c]) and
+ *   -c (out[n + c]); *bound = the |c| its identity is proved for. */
+typedef struct {
+  int64_t rgb_off;   /* the image's first byte from rgb_base */
+  int64_t H, W;
+  int32_t quality;   /* 1..100 */
+  int32_t subsampling; /* JDS_SS_*; JDS_SS_GRAY: one byte per pixel */
+} jds_rgb_item;
+int jds_jpeg_quality_info(int32_t quality, int32_t subsampling, int64_t H, int64_t W, jds_jpeg_info* out);
+int jds_jpeg_forward_dev(jds_ctx* ctx, const jds_jpeg_info* info, const uint8_t* rgb_dev, int16_t* coeffs_dev,
+                         void* stream);
+int jds_rgb_to_jpeg(jds_ctx* ctx, const uint8_t* rgb, int32_t rgb_on_device, int64_t H, int64_t W, int32_t quality,
+                    int32_t subsampling, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len);
+int jds_rgb_batch_to_jpeg(jds_ctx* ctx, const uint8_t* rgb_base, int32_t rgb_on_device, const jds_rgb_item* items_in,
+                          int32_t n, int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                          jds_jpeg_transcode_item* items_out, int64_t* out_bytes);
+int jds_selftest_jpeg_forward(const jds_jpeg_info* info, const uint8_t* rgb, int16_t* coeffs_out);
+int jds_selftest_jpeg_fwd_quant(int32_t q, int32_t n, int32_t* out, int32_t* bound);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp; the host model: csrc/jds_jpeg_parse.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

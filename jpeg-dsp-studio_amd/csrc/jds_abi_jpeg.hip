@@ -1,14 +1,17 @@
 // jds_abi_jpeg.hip — the C-ABI's foreign-file half (include/jds.h): parse and
 // decode of files of either scan form, rendering, batches, the lossless
-// transcode and transforms, and their host models (jds_selftest_*).
+// transcode and transforms, the libjpeg encoding, and their host models
+// (jds_selftest_*).
 //
 // Host side only: descriptors (jds_dec_jobs.hpp), uploads and launches.
 #include <algorithm>
+#include <functional>
 #include <string>
 
 #include "jds_abi.hpp"
 #include "jds_dec_jobs.hpp"
 #include "jds_entropy_mcu_dev.hpp"
+#include "jds_jpeg_fwd.hpp"
 #include "jds_jpeg_ljt.hpp"
 #include "jds_jpeg_parse.hpp"
 #include "jds_xform_dev.hpp"
@@ -944,6 +947,53 @@ static int xf_prepare(const uint8_t* data, int64_t len, const jds_jpeg_info* inf
   return JDS_OK;
 }
 
+// The writer over a batch's jobs, whose coefficients are in c->ent_cf (job k is
+// item job_item[k]): its launches, the files packed in job order at multiples
+// of 256 into out (jds_jpeg_batch_transcode's contract) with out_off / out_len
+// of their items, and rc for a job that is not baseline-codable, of which
+// bad(item, message) hears.  Synchronous.
+static int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int>& job_item, int32_t optimize,
+                           const XfSet* xf, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                           jds_jpeg_transcode_item* items, int64_t* out_bytes,
+                           const std::function<void(int, const char*)>& bad) {
+  hipStream_t s = c->stream;
+  McuRun r;
+  int rc;
+  if ((rc = mcu_code(c, jobs, optimize, &r, xf))) return rc;
+  std::vector<long long> fout(jobs.size(), -1ll);
+  int64_t cur = 0;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    const int i = job_item[k];
+    if (r.len[k] == 0) {
+      items[i].rc = fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
+      bad(i, MCU_NOT_CODABLE);
+      continue;
+    }
+    fout[k] = cur;
+    items[i].out_off = cur;
+    items[i].out_len = r.len[k];
+    cur = (cur + r.len[k] + 255) & ~(int64_t)255;
+  }
+  *out_bytes = cur;
+  if (cur > 0 && (!out || out_cap < cur))
+    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)cur);
+  if (cur > 0) {
+    uint8_t* dst = out;
+    if (!out_on_device) {
+      HIP_TRY(c->ent_out.ensure((size_t)cur));
+      dst = (uint8_t*)c->ent_out.p;
+    }
+    if ((rc = mcu_emit(c, r, fout, dst))) return rc;
+    if (!out_on_device)  // file by file: the gaps of the caller's buffer stay as they are
+      for (size_t k = 0; k < jobs.size(); ++k)
+        if (fout[k] >= 0)
+          HIP_TRY(hipMemcpyAsync(out + fout[k], dst + fout[k], (size_t)r.len[k], hipMemcpyDeviceToHost, s));
+    kmark(s, "(transcode download)");
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return JDS_OK;
+}
+
 // jds_jpeg_batch_transcode, and with `xform` jds_jpeg_batch_transform: the same
 // launches with per-file transformed records handed to the writer's driver.
 static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, bool xform,
@@ -1023,44 +1073,15 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
     batch_note(bp);
     return JDS_OK;
   }
-  hipStream_t s = c->stream;
-  const CtxMarkScope marks_(c, s);
-  McuRun r;
-  if ((rc = mcu_code(c, jobs, optimize, &r, xs.files.empty() ? nullptr : &xs))) return rc;
-  std::vector<long long> fout(jobs.size(), -1ll);
-  int64_t cur = 0;
-  for (size_t k = 0; k < jobs.size(); ++k) {
-    const int i = job_file[k];
-    if (r.len[k] == 0) {
-      items[i].rc = fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
-      if (bp.first_bad < 0 || i < bp.first_bad) {
-        bp.first_bad = i;
-        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", MCU_NOT_CODABLE);
-      }
-      continue;
-    }
-    fout[k] = cur;
-    items[i].out_off = cur;
-    items[i].out_len = r.len[k];
-    cur = (cur + r.len[k] + 255) & ~(int64_t)255;
-  }
-  *out_bytes = cur;
-  if (cur > 0 && (!out || out_cap < cur))
-    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)cur);
-  if (cur > 0) {
-    uint8_t* dst = out;
-    if (!out_on_device) {
-      HIP_TRY(c->ent_out.ensure((size_t)cur));
-      dst = (uint8_t*)c->ent_out.p;
-    }
-    if ((rc = mcu_emit(c, r, fout, dst))) return rc;
-    if (!out_on_device)  // file by file: the gaps of the caller's buffer stay as they are
-      for (size_t k = 0; k < jobs.size(); ++k)
-        if (fout[k] >= 0)
-          HIP_TRY(hipMemcpyAsync(out + fout[k], dst + fout[k], (size_t)r.len[k], hipMemcpyDeviceToHost, s));
-    kmark(s, "(transcode download)");
-    HIP_TRY(hipStreamSynchronize(s));
-  }
+  const CtxMarkScope marks_(c, c->stream);
+  rc = mcu_write_batch(c, jobs, job_file, optimize, xs.files.empty() ? nullptr : &xs, out, out_cap, out_on_device, items,
+                       out_bytes, [&](int i, const char* m) {
+                         if (bp.first_bad < 0 || i < bp.first_bad) {
+                           bp.first_bad = i;
+                           snprintf(bp.first_msg, sizeof bp.first_msg, "%s", m);
+                         }
+                       });
+  if (rc) return rc;
   batch_note(bp);
   return JDS_OK;
 }
@@ -1244,6 +1265,207 @@ int jds_selftest_jpeg_hist_dev(jds_ctx* c, const jds_jpeg_info* info, const int1
   // (the counters open the file's frame)
   HIP_TRY(hipMemcpy(counts, r.d.of, sizeof(uint32_t) * 2 * OPT_BINS, hipMemcpyDeviceToHost));
   return JDS_OK;
+}
+
+// --------------------------------------------------- libjpeg encoding --
+// (DESIGN.md "libjpeg encoding"; kernel: jds_jpeg_fwd.hip; tile core: jds_jpeg_fwd.hpp)
+
+static int quality_check(int32_t quality, int32_t ss, int64_t H, int64_t W) {
+  if (quality < 1 || quality > 100) return fail(JDS_EINVAL, "quality %d outside [1, 100]", (int)quality);
+  if (ss != JDS_SS_444 && ss != JDS_SS_422 && ss != JDS_SS_420 && ss != JDS_SS_GRAY)
+    return fail(JDS_EINVAL, "unknown subsampling %d (JDS_SS_444, _422, _420 or _GRAY)", (int)ss);
+  if (H < 1 || H > 65535) return fail(JDS_EINVAL, "H = %lld outside [1, 65535]", (long long)H);
+  if (W < 1 || W > 65535) return fail(JDS_EINVAL, "W = %lld outside [1, 65535]", (long long)W);
+  if (H * W > (int64_t)1 << 28) return fail(JDS_EINVAL, "H x W = %lldx%lld: above 2^28 pixels", (long long)H, (long long)W);
+  return JDS_OK;
+}
+
+int jds_jpeg_quality_info(int32_t quality, int32_t subsampling, int64_t H, int64_t W, jds_jpeg_info* out) {
+  if (!out) return fail(JDS_EINVAL, "null argument");
+  const int rc = quality_check(quality, subsampling, H, W);
+  if (rc) return rc;
+  jf_quality_info(quality, subsampling, H, W, out);
+  int64_t ny = 0, nc = 0;
+  out->reference_grid =
+      subsampling != JDS_SS_GRAY && hd_block_counts(H, W, subsampling, &ny, &nc, nullptr, 0) == JDS_OK;
+  return JDS_OK;
+}
+
+// The launch arguments of an info: jpeg_inv_args' checks of tables and grids.
+static int jpeg_fwd_args(const jds_jpeg_info* info, JInvArgs* a) {
+  const int rc = jinv_args(info, a);
+  if (rc == -1000)
+    return fail(JDS_EINVAL, "jpeg forward: %lldx%lld with these grids is not a T.81 geometry of subsampling %d",
+                (long long)info->H, (long long)info->W, info->subsampling);
+  if (rc < 0) {
+    const int c = (-rc - 1) / 64, i = (-rc - 1) % 64;
+    return fail(JDS_EINVAL, "qtable[%d][%d] = %g is not an integer in [1, 255]", c, i, info->qtable[c][i]);
+  }
+  return JDS_OK;
+}
+
+static inline size_t rgb_image_bytes(const JInvArgs& a) {
+  return (size_t)a.H * (size_t)a.W * (a.ss == JDS_SS_GRAY ? 1u : 3u);
+}
+
+int jds_jpeg_forward_dev(jds_ctx* c, const jds_jpeg_info* info, const uint8_t* rgb_dev, int16_t* coeffs_dev,
+                         void* stream) {
+  if (!info) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  int rc;
+  if ((rc = jpeg_fwd_args(info, &a))) return rc;
+  if (!c || !rgb_dev || !coeffs_dev) return fail(JDS_EINVAL, "null argument");
+  if ((uintptr_t)coeffs_dev & 15u) return fail(JDS_EINVAL, "coeffs_dev must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_jpeg_fwd(a, rgb_dev, coeffs_dev, (hipStream_t)stream));
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_forward(const jds_jpeg_info* info, const uint8_t* rgb, int16_t* coeffs_out) {
+  if (!info || !rgb || !coeffs_out) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  const int rc = jpeg_fwd_args(info, &a);
+  if (rc) return rc;
+  if ((uintptr_t)coeffs_out & 15u) return fail(JDS_EINVAL, "coeffs_out must be 16-byte aligned");
+  jpeg_fwd_host_image(a, rgb, coeffs_out);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_fwd_quant(int32_t q, int32_t n, int32_t* out, int32_t* bound) {
+  if (!out || !bound || q < 1 || q > 255 || n < 0) return fail(JDS_EINVAL, "bad argument");
+  *bound = JF_CBOUND;
+  const uint32_t r = jf_recip(q);
+  for (int32_t i = 0; i < n; ++i) {
+    out[i] = jf_quant(i, q, r);
+    out[n + i] = jf_quant(-i, q, r);
+  }
+  return JDS_OK;
+}
+
+int jds_rgb_to_jpeg(jds_ctx* c, const uint8_t* rgb, int32_t rgb_on_device, int64_t H, int64_t W, int32_t quality,
+                    int32_t subsampling, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len) {
+  if (!c || !rgb || !out_len) return fail(JDS_EINVAL, "null argument");
+  jds_jpeg_info info;
+  int rc;
+  if ((rc = jds_jpeg_quality_info(quality, subsampling, H, W, &info))) return rc;
+  JInvArgs a;
+  if ((rc = jpeg_fwd_args(&info, &a))) return rc;
+  McuJob job;
+  if ((rc = mcu_job_geo(&info, 0, &job))) return rc;
+  if ((rc = mcu_job_prefix(&info, nullptr, 0, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(c->ent_cf.ensure((size_t)info.coeffs_needed * sizeof(int16_t)));
+  const uint8_t* src = rgb;
+  if (!rgb_on_device) {
+    HIP_TRY(c->rgb.ensure(rgb_image_bytes(a)));
+    HIP_TRY(hipMemcpyAsync(c->rgb.p, rgb, rgb_image_bytes(a), hipMemcpyHostToDevice, c->stream));
+    src = (const uint8_t*)c->rgb.p;
+  }
+  HIP_TRY(launch_jpeg_fwd(a, src, (int16_t*)c->ent_cf.p, c->stream));
+  return mcu_single(c, job, optimize, out, out_cap, out_len);
+}
+
+int jds_rgb_batch_to_jpeg(jds_ctx* c, const uint8_t* rgb_base, int32_t rgb_on_device, const jds_rgb_item* items_in,
+                          int32_t n, int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                          jds_jpeg_transcode_item* items, int64_t* out_bytes) {
+  if (!c || !out_bytes || n < 0 || (n > 0 && (!items_in || !items || !rgb_base))) return fail(JDS_EINVAL, "null argument");
+  *out_bytes = 0;
+  int first_bad = -1;
+  char first_msg[400] = "";
+  auto note = [&](int i, const char* m) {
+    if (first_bad < 0 || i < first_bad) {
+      first_bad = i;
+      snprintf(first_msg, sizeof first_msg, "%s", m);
+    }
+  };
+  auto finish = [&]() {
+    if (first_bad >= 0)
+      fail(0, "image %d: %s", first_bad, first_msg);
+    else
+      g_err[0] = 0;
+    return JDS_OK;
+  };
+  // the images that take part: records in batch order, coefficients end to end
+  std::vector<JInvRec> recs;
+  std::vector<McuJob> jobs;
+  std::vector<int> job_item;
+  int64_t coef_entries = 0, span = 0;
+  for (int i = 0; i < n; ++i) {
+    const jds_rgb_item& in = items_in[i];
+    jds_jpeg_transcode_item& it = items[i];
+    memset(&it, 0, sizeof it);
+    it.out_off = -1;
+    jds_jpeg_info info;
+    JInvRec r;
+    memset(&r, 0, sizeof r);
+    McuJob j;
+    int rc = in.rgb_off < 0 ? fail(JDS_EINVAL, "rgb_off %lld", (long long)in.rgb_off)
+                            : jds_jpeg_quality_info(in.quality, in.subsampling, in.H, in.W, &info);
+    if (rc == JDS_OK) rc = jpeg_fwd_args(&info, &r.a);
+    if (rc == JDS_OK) rc = mcu_job_geo(&info, coef_entries, &j);
+    if (rc == JDS_OK) rc = mcu_job_prefix(&info, nullptr, 0, &j);
+    it.rc = rc;
+    if (rc != JDS_OK) {
+      note(i, g_err);
+      continue;
+    }
+    it.H = in.H;
+    it.W = in.W;
+    it.subsampling = in.subsampling;
+    it.interleaved = info.interleaved;
+    r.coef_off = coef_entries;
+    r.rgb_off = in.rgb_off;
+    r.st = (int)recs.size();
+    coef_entries += info.coeffs_needed;
+    const int64_t end = in.rgb_off + (int64_t)rgb_image_bytes(r.a);
+    span = end > span ? end : span;
+    recs.push_back(r);
+    jobs.push_back(std::move(j));
+    job_item.push_back(i);
+  }
+  if (recs.empty()) return finish();
+  const int nv = (int)recs.size();
+  std::vector<JInvMap> map[JI_MODES];
+  if (coef_entries / 64 > 0x7fffffffll || !jinv_batch_maps(recs.data(), nv, map))
+    return fail(JDS_ENOTSUP, "batch of %d images: too many blocks or tiles for one set of launches", (int)n);
+  int map_off[JI_MODES], nmap[JI_MODES], tiles[JI_MODES], nm = 0;
+  for (int m = 0; m < JI_MODES; ++m) {
+    map_off[m] = nm;
+    nmap[m] = (int)map[m].size() - 1;
+    tiles[m] = map[m].back().tile0;
+    nm += (int)map[m].size();
+  }
+  const size_t o_map = (sizeof(JInvRec) * (size_t)nv + 255) & ~(size_t)255, total = o_map + sizeof(JInvMap) * (size_t)nm;
+  std::vector<char> h(total, 0);
+  memcpy(h.data(), recs.data(), sizeof(JInvRec) * (size_t)nv);
+  for (int m = 0; m < JI_MODES; ++m)
+    memcpy(h.data() + o_map + sizeof(JInvMap) * (size_t)map_off[m], map[m].data(), sizeof(JInvMap) * map[m].size());
+  hipStream_t s = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(c->bat.ensure(total));
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)coef_entries));
+  const uint8_t* src = rgb_base;
+  const CtxMarkScope marks_(c, s);
+  // h and the caller's images are copied asynchronously: whichever way this call
+  // returns, an error among them, the stream has drained before they go
+  struct Settle {
+    hipStream_t s;
+    ~Settle() { (void)hipStreamSynchronize(s); }
+  } const settle_{s};
+  if (!rgb_on_device) {  // image by image, at the caller's offsets
+    HIP_TRY(c->rgb.ensure((size_t)span));
+    for (int k = 0; k < nv; ++k)
+      HIP_TRY(hipMemcpyAsync((char*)c->rgb.p + recs[(size_t)k].rgb_off, rgb_base + recs[(size_t)k].rgb_off,
+                             rgb_image_bytes(recs[(size_t)k].a), hipMemcpyHostToDevice, s));
+    src = (const uint8_t*)c->rgb.p;
+  }
+  HIP_TRY(hipMemcpyAsync(c->bat.p, h.data(), total, hipMemcpyHostToDevice, s));
+  kmark(s, "(batch upload)");
+  HIP_TRY(launch_jpeg_fwd_batch((const JInvRec*)c->bat.p, (const JInvMap*)((const char*)c->bat.p + o_map), map_off, nmap,
+                                tiles, src, (int16_t*)c->ent_cf.p, s));
+  const int rc = mcu_write_batch(c, jobs, job_item, optimize, nullptr, out, out_cap, out_on_device, items, out_bytes, note);
+  if (rc) return rc;
+  return finish();
 }
 
 }  // extern "C"

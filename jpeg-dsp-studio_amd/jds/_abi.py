@@ -122,6 +122,11 @@ class JpegTranscodeItem(C.Structure):
                 ('out_len', C.c_int64)]
 
 
+class RgbItem(C.Structure):
+    _fields_ = [('rgb_off', C.c_int64), ('H', C.c_int64), ('W', C.c_int64), ('quality', C.c_int32),
+                ('subsampling', C.c_int32)]
+
+
 # lossless transform operations (include/jds.h JDS_XF_*)
 XF_OPS = {'none': 0, 'hflip': 1, 'vflip': 2, 'transpose': 3, 'transverse': 4, 'rot90': 5, 'rot180': 6, 'rot270': 7,
           'auto': 8}
@@ -247,6 +252,14 @@ _SIGS = {
     'jds_selftest_jpeg_transform': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64,
                                               C.POINTER(C.c_int64)]),
     'jds_selftest_coef_transform_dev': (C.c_int, [_P, C.POINTER(JpegInfo), C.c_int32, _P, _P]),
+    'jds_jpeg_quality_info': (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(JpegInfo)]),
+    'jds_jpeg_forward_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P, _P]),
+    'jds_rgb_to_jpeg': (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
+                                  C.c_int64, C.POINTER(C.c_int64)]),
+    'jds_rgb_batch_to_jpeg': (C.c_int, [_P, _P, C.c_int32, C.POINTER(RgbItem), C.c_int32, C.c_int32, _P, C.c_int64,
+                                        C.c_int32, C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
+    'jds_selftest_jpeg_forward': (C.c_int, [C.POINTER(JpegInfo), _P, _P]),
+    'jds_selftest_jpeg_fwd_quant': (C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     'jds_selftest_dct16x16': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),

@@ -547,6 +547,220 @@ def jpeg_batch_transform(files, ops='auto', trim: bool = False, optimize: bool =
     return _batch_transcode(files, optimize, out, errors, device, ctx, [_abi.xf_code(o, trim) for o in names])
 
 
+# ----------------------------------------------------------- libjpeg encoding --
+# (DESIGN.md "libjpeg encoding"; definition: tests/libjpeg_fwd_ref.py)
+
+def _ss_code(subsampling) -> int:
+    if subsampling not in _abi.JPEG_MODE_CODES:
+        raise ValueError(f'unknown subsampling {subsampling!r}: one of {", ".join(_abi.JPEG_MODE_CODES)}')
+    return _abi.JPEG_MODE_CODES[subsampling]
+
+
+def _quality_info(quality, code: int, H: int, W: int) -> _abi.JpegInfo:
+    info = _abi.JpegInfo()
+    check(lib().jds_jpeg_quality_info(int(quality), code, int(H), int(W), C.byref(info)))
+    return info
+
+
+def libjpeg_tables(quality: int) -> np.ndarray:
+    """jpeg_set_quality(quality, force_baseline)'s tables: (2, 64) float64, luma and chroma,
+    row-major.  ValueError for a quality outside 1..100."""
+    info = _quality_info(quality, _abi.SS_444, 8, 8)
+    return np.ctypeslib.as_array(info.qtable).astype(np.float64).reshape(3, 64)[:2].copy()
+
+
+def _is_tensor(x) -> bool:
+    return hasattr(x, 'data_ptr') and hasattr(x, 'is_contiguous')
+
+
+def _image_arg(image, device: int = 0):
+    """(keep-alive object, pointer, on_device, H, W, gray) of an HxWx3 or HxW uint8 NumPy array or
+    contiguous torch tensor on GPU `device` (ValueError for one on another GPU)."""
+    if _is_tensor(image):
+        if image.is_cuda and image.device.index != int(device):
+            raise ValueError(f'the image is on {image.device}, the call runs on device {int(device)}')
+        shape = tuple(int(v) for v in image.shape)
+        if image.element_size() != 1 or 'uint8' not in str(image.dtype):
+            raise ValueError(f'images must be uint8 (got {image.dtype})')
+        if not image.is_contiguous():
+            raise ValueError('a device image must be a contiguous tensor')
+        if not image.is_cuda:
+            image = image.numpy()
+    if not _is_tensor(image):
+        a = np.asarray(image)
+        if a.dtype != np.uint8:
+            raise ValueError(f'images must be uint8 (got {a.dtype})')
+        shape = a.shape
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)) or 0 in shape:
+        raise ValueError(f'an image is HxWx3 or HxW (grayscale), got shape {tuple(shape)}')
+    if _is_tensor(image):
+        return image, int(image.data_ptr()), 1, shape[0], shape[1], len(shape) == 2
+    a = np.ascontiguousarray(a)
+    return a, a.ctypes.data, 0, shape[0], shape[1], len(shape) == 2
+
+
+def _torch_settled(device: int) -> None:
+    """The context's stream does not wait for torch's: what torch has queued for the images ends first."""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _aligned_i16(n: int) -> np.ndarray:
+    """n int16 entries starting at a 16-byte boundary."""
+    raw = np.empty(2 * n + 16, np.uint8)
+    o = (-raw.ctypes.data) % 16
+    return raw[o:o + 2 * n].view(np.int16)
+
+
+def host_rgb_forward(image, quality: int = 75, subsampling: str = '4:2:0'):
+    """Test aid (jds_selftest_jpeg_forward): k_jpeg_fwd's tile core in a host tile loop -> (planar
+    int16 coefficients in decode_jpeg's layout, info dict: 'H', 'W', 'mode', 'grids', 'qtables', 'tq',
+    ... as parse_jpeg gives them) -- entropy.encode_jpeg's arguments.  A 2-D image is grayscale
+    whatever `subsampling` says.  No GPU."""
+    from . import entropy
+    keep, p, on_dev, H, W, gray = _image_arg(image)
+    if on_dev:
+        raise ValueError('host_rgb_forward takes a host array')
+    info = _quality_info(quality, _abi.SS_GRAY if gray else _ss_code(subsampling), H, W)
+    cf = _aligned_i16(int(info.coeffs_needed))
+    check(lib().jds_selftest_jpeg_forward(C.byref(info), p, cf.ctypes.data))
+    return cf, entropy._jpeg_dict(info)
+
+
+def rgb_forward_dev(info: dict, rgb_ptr: int, coeffs_ptr: int, stream=None, device: int = 0) -> None:
+    """jds_jpeg_forward_dev: H*W*3 RGB bytes on the device (info['mode'] 'gray': H*W) -> the quantised
+    coefficients libjpeg's compressor gives, in decode_jpeg's layout (int16, 16-byte aligned) on the
+    device: one asynchronous launch of k_jpeg_fwd on `stream` (None: the null stream).  info: 'H',
+    'W', 'mode', 'grids', 'qtables' (any integer tables in [1, 255]) as host_rgb_forward returns."""
+    st = _jpeg_info_struct(info['H'], info['W'], info['mode'], info['qtables'], info['grids'])
+    with lease(device) as ctx:
+        check(lib().jds_jpeg_forward_dev(ctx.handle, C.byref(st), C.c_void_p(int(rgb_ptr)),
+                                         C.c_void_p(int(coeffs_ptr)), C.c_void_p(int(stream or 0))))
+
+
+def rgb_to_jpeg(image, quality: int = 75, subsampling: str = '4:2:0', optimize: bool = False, device: int = 0) -> bytes:
+    """jds_rgb_to_jpeg: an HxWx3 (or HxW: grayscale) uint8 image -- a NumPy array or a contiguous
+    torch tensor on `device` -- -> the baseline JPEG PIL.Image.save(quality=, subsampling=,
+    optimize=) writes, byte for byte (DESIGN.md "libjpeg encoding"): k_jpeg_fwd, then the
+    transcode's writer; the coefficients never leave the device.  ValueError for another dtype or
+    shape, a non-contiguous tensor, a quality outside 1..100 or a side above 65535."""
+    from . import entropy
+    keep, p, on_dev, H, W, gray = _image_arg(image, device)
+    code = _abi.SS_GRAY if gray else _ss_code(subsampling)
+    if on_dev:
+        _torch_settled(device)
+    with lease(device) as ctx:
+        return entropy._grown(lambda o, cap, m: lib().jds_rgb_to_jpeg(
+            ctx.handle, C.c_void_p(p), on_dev, H, W, int(quality), code, int(bool(optimize)), o.ctypes.data, cap,
+            C.byref(m)), H * W * (1 if gray else 3) + 4096)      # (noise at a high quality comes close to the image's own size)
+
+
+def _per_item(v, n: int, what: str) -> list:
+    if isinstance(v, (str, int, np.integer)):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f'{len(v)} {what} values for {n} images')
+    return v
+
+
+def rgb_batch_to_jpeg(images, quality=75, subsampling='4:2:0', optimize: bool = False, out=None, errors: str = 'raise',
+                      device: int = 0, ctx=None):
+    """jds_rgb_batch_to_jpeg: images -> each one's rgb_to_jpeg file, by one forward launch per
+    subsampling mode present and one set of writer launches.  images: a sequence of uint8 arrays
+    (HxWx3 or HxW), a sequence of contiguous device tensors (views into one allocation -- e.g.
+    jpeg_batch_to_rgb(out='device')'s -- are passed by offset, anything else is gathered into one
+    buffer first), or an NxHxWx3 device tensor; any mix of sizes.  quality, subsampling: one value or
+    one per image (a 2-D image is grayscale whatever its entry says).  out, errors, ctx and the
+    return shape as jpeg_batch_transcode: an image with a bad argument (quality 0, ...) does not stop
+    the others and no other file's bytes depend on it."""
+    if errors not in ('raise', 'items'):
+        raise ValueError("errors must be 'raise' or 'items'")
+    own = out is None or isinstance(out, str)
+    if isinstance(out, str) and out != 'device':
+        raise ValueError("out must be None, 'device' or a 1-D uint8 device tensor")
+    if not own and (out.dim() != 1 or out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError('out must be a contiguous 1-D uint8 device tensor')
+    if _is_tensor(images):
+        if images.dim() != 4:
+            raise ValueError(f'a batch tensor is NxHxWx3, got shape {tuple(images.shape)}')
+        if not images.is_contiguous():
+            raise ValueError('a device image must be a contiguous tensor')
+        images = [images[i] for i in range(int(images.shape[0]))]
+    args = [_image_arg(im, device) for im in images]
+    n = len(args)
+    qs, modes = _per_item(quality, n, 'quality'), _per_item(subsampling, n, 'subsampling')
+    codes = [_abi.SS_GRAY if a[5] else _ss_code(m) for a, m in zip(args, modes)]
+    sizes = [a[3] * a[4] * (1 if a[5] else 3) for a in args]
+    if n and all(a[2] for a in args):
+        bases = {int(a[0].untyped_storage().data_ptr()) for a in args}
+        if len(bases) == 1:                      # views into one allocation: by offset
+            base, keep = bases.pop(), [a[0] for a in args]
+            offs = [a[1] - base for a in args]
+        else:                                    # gathered on the device
+            import torch
+            keep = torch.cat([a[0].reshape(-1) for a in args])
+            base, offs = int(keep.data_ptr()), [0] + list(np.cumsum(sizes[:-1]))
+        on_dev = 1
+        _torch_settled(device)
+    else:                                        # host arrays (a device tensor among them comes to the host)
+        offs = [0] + list(np.cumsum([-(-s // 256) * 256 for s in sizes[:-1]])) if n else []
+        keep = np.zeros(max(sum(-(-s // 256) * 256 for s in sizes), 1), np.uint8)
+        for a, o, s in zip(args, offs, sizes):
+            src = a[0].cpu().numpy() if a[2] else a[0]
+            keep[o:o + s] = src.reshape(-1)
+        base, on_dev = keep.ctypes.data, 0
+    items_in = (_abi.RgbItem * max(n, 1))()
+    for i, (a, o) in enumerate(zip(args, offs)):
+        items_in[i].rgb_off, items_in[i].H, items_in[i].W = int(o), a[3], a[4]
+        items_in[i].quality, items_in[i].subsampling = int(qs[i]), codes[i]
+    items = (_abi.JpegTranscodeItem * max(n, 1))()
+    need = C.c_int64(0)
+    cap = sum(-(-(s + 4096) // 256) * 256 for s in sizes) if own else int(out.numel())     # (rgb_to_jpeg's guess)
+
+    def alloc(cap):
+        if out is None:
+            return np.empty(max(cap, 1), np.uint8)
+        if isinstance(out, str):
+            import torch
+            return torch.empty(max(cap, 1), dtype=torch.uint8, device=f'cuda:{device}')
+        return out
+
+    def run(c, buf, cap):
+        dst, dev_out = (buf.ctypes.data, 0) if out is None else (int(buf.data_ptr()), 1)
+        return lib().jds_rgb_batch_to_jpeg(c.handle, C.c_void_p(base), on_dev, items_in, n, int(bool(optimize)),
+                                           C.c_void_p(dst), cap, dev_out, items, C.byref(need))
+
+    def attempt(c):
+        nonlocal cap
+        buf = alloc(cap)
+        rc = run(c, buf, cap)
+        if rc == _abi.JDS_EINVAL and own and need.value > cap:
+            cap = int(need.value)
+            buf = alloc(cap)
+            rc = run(c, buf, cap)
+        check(rc)
+        return buf
+
+    if ctx is not None:
+        buf = attempt(ctx)
+    else:
+        with lease(device) as c:
+            buf = attempt(c)
+    info = [_transcode_item_dict(items[i]) for i in range(n)]
+    first = _batch_first_error(info)
+    if first and errors == 'raise':
+        raise ValueError(first)
+    outs = []
+    for it in info:
+        if it['rc'] != 0:
+            outs.append(None)
+            continue
+        v = buf[it['out_off']:it['out_off'] + it['out_len']]
+        outs.append(v.tobytes() if out is None else v)
+    return outs if errors == 'raise' else (outs, info)
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

@@ -39,7 +39,10 @@ and call: the median time, the per-kernel times from the context's launch marks,
 the rounds; four outputs of each call compared with the single call.  Writes
 profiles/gray_probe.json (or --out FILE).
 --render N (default 64) instead: the two renderings ('reference', 'libjpeg') side by side, see
-render_main.  Writes profiles/jpeg_render_probe.json (or --out FILE)."""
+render_main.  Writes profiles/jpeg_render_probe.json (or --out FILE).
+--encode N (default 64) instead: the way back, pixels to files: N 1080p pictures in a device tensor
+through rgb_batch_to_jpeg against N rgb_to_jpeg calls, see encode_main.  Writes
+profiles/jpeg_encode_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -576,7 +579,74 @@ def render_main():
     return 0 if all(r['libjpeg_equals_pillow'] for r in rows) else 1
 
 
+def encode_main():
+    """--encode [N]: N (default 64) 1080p noise pictures in one device tensor through
+    rgb_batch_to_jpeg (4:2:0, quality 75, out='device'), plain and optimize=True, against N
+    rgb_to_jpeg calls on the same tensor's images in the same process (whole calls by the host
+    clock: median of 30 after 3 warm-ups, the two alternating); k_jpeg_fwd_batch and the writer's
+    kernels from the context's launch marks (events), and beside them, in the same profiled loop,
+    k_jpeg_ljt_batch decoding the files just written (the same geometry in the other direction);
+    the output bytes; the first file against Pillow's and four against the single call.  Writes
+    profiles/jpeg_encode_probe.json (or --out FILE)."""
+    import torch
+    from jds import _abi
+    i = sys.argv.index('--encode')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    pics = [np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8) for k in range(n)]
+    stack = torch.stack([torch.from_numpy(p) for p in pics]).cuda()
+    ctx = _abi.Context(0)
+    rows = []
+    for optimize in (False, True):
+        row = {'leg': 'batch_rgb_q75_420_1080p_' + ('optimize' if optimize else 'plain'), 'n': n, 'H': H, 'W': W,
+               'rgb_bytes_total': int(stack.numel())}
+        outs = codec.rgb_batch_to_jpeg(stack, 75, '4:2:0', optimize, out='device', ctx=ctx)
+        files = [o.cpu().numpy().tobytes() for o in outs]
+        row['file_bytes_total'] = int(sum(len(f) for f in files))
+        row['first_file_equals_pillow'] = files[0] == pillow_file(pics[0], quality=75, subsampling=2, optimize=optimize)
+        some = range(0, n, max(1, n // 4))
+        row['batch_equals_single'] = all(files[k] == codec.rgb_to_jpeg(stack[k], 75, '4:2:0', optimize) for k in some)
+        t = {'batch': [], 'sequence': []}
+        for r in range(3 + 30):
+            t0 = time.perf_counter()
+            codec.rgb_batch_to_jpeg(stack, 75, '4:2:0', optimize, out='device', ctx=ctx)
+            t1 = time.perf_counter()
+            for k in range(n):
+                codec.rgb_to_jpeg(stack[k], 75, '4:2:0', optimize)
+            t2 = time.perf_counter()
+            if r >= 3:
+                t['batch'].append((t1 - t0) * 1e3)
+                t['sequence'].append((t2 - t1) * 1e3)
+        row['ms_per_batch'] = {k: {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v)} for k, v in t.items()}
+        _, rgb_bytes, _ = codec.jpeg_batch_layout(files)
+        back = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+        views = codec.jpeg_batch_to_rgb(files, out=back, ctx=ctx, render='libjpeg')      # (warm-up of the decode side)
+        row['decoded_shape_ok'] = all(tuple(v.shape) == (H, W, 3) for v in views)
+        ctx.profile(True)
+        reps = 5
+        for _ in range(reps):
+            codec.rgb_batch_to_jpeg(stack, 75, '4:2:0', optimize, out='device', ctx=ctx)
+            codec.jpeg_batch_to_rgb(files, out=back, ctx=ctx, render='libjpeg')
+        kern, _ = ctx.profile_read()
+        ctx.profile(False)
+        row['kernels_ms_per_batch'] = {k: v[0] / reps for k, v in kern.items()
+                                       if k.startswith(('k_jpeg_fwd_batch', 'k_jpeg_ljt_batch', 'k_mcu_', 'k_ent_opt'))}
+        fwd = sum(v for k, v in row['kernels_ms_per_batch'].items() if k.startswith('k_jpeg_fwd_batch'))
+        ljt = sum(v for k, v in row['kernels_ms_per_batch'].items() if k.startswith('k_jpeg_ljt_batch'))
+        row['fwd_over_ljt'] = fwd / ljt if ljt else None
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    ctx.close()
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'jpeg_encode_probe.json')
+    with open(out, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r['first_file_equals_pillow'] and r['batch_equals_single'] for r in rows) else 1
+
+
 def main():
+    if '--encode' in sys.argv:
+        return encode_main()
     if '--render' in sys.argv:
         return render_main()
     if '--gray' in sys.argv:
