@@ -654,9 +654,11 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
  *
  * Scope: parity with libjpeg is stated for files it decodes as YCbCr (JFIF, or
  *   no Adobe marker with ordinary component ids) or as grayscale, and for its
- *   default settings only (ISLOW, fancy upsampling, no scaling, no block
- *   smoothing).  A file libjpeg would take as RGB (Adobe transform 0, or ids
- *   'R', 'G', 'B') is still treated as YCbCr here, as by every other call.
+ *   default settings only (ISLOW, fancy upsampling, no block smoothing), at
+ *   full size and, through the _scaled calls below, at libjpeg's scales 1/2,
+ *   1/4 and 1/8 (its other M/8 scales are not offered).  A file libjpeg would
+ *   take as RGB (Adobe transform 0, or ids 'R', 'G', 'B') is still treated as
+ *   YCbCr here, as by every other call.
  *   jds_decompress_jpeg, the transcode and the transforms have no rendering
  *   argument.
  * Arithmetic: 32-bit two's complement with wrap-around at every operation.
@@ -690,6 +692,66 @@ int jds_selftest_jpeg_render(const jds_jpeg_info* info, const int16_t* coeffs, u
 int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
                                    uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items,
                                    int32_t render);
+
+/* The scaled libjpeg rendering (DESIGN.md "Scaled libjpeg rendering";
+ * definition: tests/libjpeg_scaled_ref.py): the reduced-size decode libjpeg does
+ * inside the IDCT with scale_num / scale_denom = 1 / scale_denom -- Pillow's
+ * Image.draft and thumbnail, OpenCV's IMREAD_REDUCED_COLOR_2/4/8 -- byte for
+ * byte.  scale_denom is 1, 2, 4 or 8; anything else is JDS_EINVAL naming the
+ * value.  1 is the unscaled call: each _scaled call with it does exactly what
+ * its _render namesake does.  Another denominator needs JDS_RENDER_LIBJPEG
+ * (JDS_EINVAL with JDS_RENDER_REFERENCE: the reference has no scaled decode)
+ * and runs k_jpeg_ljs / k_jpeg_ljs_batch.
+ *
+ * The image is ceil(H / scale_denom) x ceil(W / scale_denom) x 3.  With
+ *   m = 8 / scale_denom, luma blocks go through jidctred's m-point inverse
+ *   (4 x 4, 2 x 2, 1 x 1); chroma through the s-point one, s being m doubled
+ *   while s < 8 and the luma's extent (Hmax m, Vmax m) is a multiple of 2 s --
+ *   4:2:0: 8, 4, 2 (one chroma sample per pixel, no upsampling); 4:2:2 and
+ *   4:4:4: m.  The chroma plane is cropped to ceil(H s / (8 Vmax)) x
+ *   ceil(W s / (8 Hmax)) before the h2v1 upsampling 4:2:2 keeps: fancy taps
+ *   when m > 1 and the plane is more than two samples wide, replication
+ *   otherwise.  Colour as at full size.  Arithmetic: 32-bit two's complement
+ *   with wrap-around; kernel, host core and the definition agree on every
+ *   int16 input.
+ * jds_jpeg_scaled_size: host only; the image's size at a denominator.
+ * jds_jpeg_render_scaled_dev: jds_jpeg_render_dev's
+ *   arguments, checks and contract; rgb holds out_h * out_w * 3 bytes.
+ * jds_jpeg_to_rgb_scaled: jds_jpeg_to_rgb_render's; rgb_cap >= out_h*out_w*3.
+ * jds_jpeg_batch_layout_scaled, jds_jpeg_batch_to_rgb_scaled: scale_denoms
+ *   (NULL: all 1) holds one denominator per file, and a batch may mix them.
+ *   The layout rule is unchanged with the OUTPUT sizes: images at multiples of
+ *   256 in batch order, the bytes between never written, zeros over the scaled
+ *   image of a file with defective scan data, item errors stay item errors.
+ *   items[i].H / .W stay the file's own; scaled (nullable) receives per file
+ *   its denominator and output size.  A bad denominator or a scaled reference
+ *   rendering fails the whole call before any work.
+ * jds_selftest_jpeg_render_scaled, jds_selftest_jpeg_batch_render_scaled:
+ *   test-only, host only: the tile core (csrc/jds_jpeg_ljs.hpp) in a host tile
+ *   loop. */
+typedef struct {
+  int32_t scale_denom, reserved;
+  int64_t out_h, out_w; /* ceil(H / scale_denom), ceil(W / scale_denom); 0 for a file with rc != 0 */
+} jds_jpeg_scaled_item;
+int jds_jpeg_scaled_size(int64_t H, int64_t W, int32_t scale_denom, int64_t* out_h, int64_t* out_w);
+int jds_jpeg_render_scaled_dev(jds_ctx* ctx, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb,
+                               void* stream, int32_t render, int32_t scale_denom);
+int jds_jpeg_to_rgb_scaled(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                           int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render,
+                           int32_t scale_denom);
+int jds_jpeg_batch_layout_scaled(const uint8_t* const* data, const int64_t* lens, int32_t n,
+                                 jds_jpeg_batch_item* items, int64_t* rgb_bytes, int64_t* coef_entries,
+                                 const int32_t* scale_denoms, jds_jpeg_scaled_item* scaled);
+int jds_jpeg_batch_to_rgb_scaled(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                                 uint8_t* rgb, int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs,
+                                 jds_jpeg_batch_item* items, uint32_t* rounds, int32_t render,
+                                 const int32_t* scale_denoms, jds_jpeg_scaled_item* scaled);
+int jds_selftest_jpeg_render_scaled(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out, int32_t render,
+                                    int32_t scale_denom);
+int jds_selftest_jpeg_batch_render_scaled(const uint8_t* const* data, const int64_t* lens, int32_t n,
+                                          int32_t subseq_bits, uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs,
+                                          jds_jpeg_batch_item* items, int32_t render, const int32_t* scale_denoms,
+                                          jds_jpeg_scaled_item* scaled);
 
 /* Lossless transcode (DESIGN.md "Transcode"; byte-for-byte definition:
  * tests/transcode_ref.py): the coefficients of jds_decode_jpeg written back as

@@ -138,6 +138,11 @@ hipError_t launch_jpeg_ljt(const JInvArgs& a, const int16_t* coeffs, uint8_t* rg
 hipError_t launch_jpeg_ljt_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
                                  const int nmap[JI_MODES], const int tiles[JI_MODES], const uint32_t* status,
                                  const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+// the scaled libjpeg rendering (jds_jpeg_ljs.hip): denom 2, 4 or 8; the batch's arrays are per mode and denominator index
+hipError_t launch_jpeg_ljs(const JInvArgs& a, int denom, const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+hipError_t launch_jpeg_ljs_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES][3],
+                                 const int nmap[JI_MODES][3], const int tiles[JI_MODES][3], const uint32_t* status,
+                                 const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
 hipError_t launch_jpeg_fwd(const JInvArgs& a, const uint8_t* img, int16_t* coeffs, hipStream_t s);
 hipError_t launch_jpeg_fwd_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
                                  const int nmap[JI_MODES], const int tiles[JI_MODES], const uint8_t* img,

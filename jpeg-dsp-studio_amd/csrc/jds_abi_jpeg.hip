@@ -12,6 +12,7 @@
 #include "jds_dec_jobs.hpp"
 #include "jds_entropy_mcu_dev.hpp"
 #include "jds_jpeg_fwd.hpp"
+#include "jds_jpeg_ljs.hpp"
 #include "jds_jpeg_ljt.hpp"
 #include "jds_jpeg_parse.hpp"
 #include "jds_xform_dev.hpp"
@@ -271,6 +272,16 @@ static int render_check(int32_t render) {
   return JDS_OK;
 }
 
+// The denominator a _scaled call names: 1, 2, 4 or 8, and only the libjpeg
+// rendering scales.
+static int scale_check(int32_t render, int32_t denom) {
+  if (!ls_denom_ok(denom)) return fail(JDS_EINVAL, "scale_denom %d is not 1, 2, 4 or 8", (int)denom);
+  if (denom != 1 && render != JDS_RENDER_LIBJPEG)
+    return fail(JDS_EINVAL, "scale_denom %d needs JDS_RENDER_LIBJPEG: the reference rendering has no scaled decode",
+                (int)denom);
+  return JDS_OK;
+}
+
 // The launch arguments of a parsed file: its tables by check_tables' rule, its
 // grids T.81's for H x W, every tile's chroma window within the kernel's arrays.
 static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
@@ -305,6 +316,31 @@ int jds_jpeg_render_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* co
   return JDS_OK;
 }
 
+int jds_jpeg_scaled_size(int64_t H, int64_t W, int32_t scale_denom, int64_t* out_h, int64_t* out_w) {
+  if (!out_h || !out_w) return fail(JDS_EINVAL, "null argument");
+  if (!ls_denom_ok(scale_denom)) return fail(JDS_EINVAL, "scale_denom %d is not 1, 2, 4 or 8", (int)scale_denom);
+  if (H < 1 || W < 1) return fail(JDS_EINVAL, "bad size %lldx%lld", (long long)H, (long long)W);
+  long long oh, ow;
+  ls_scaled_size(H, W, scale_denom, &oh, &ow);
+  *out_h = oh;
+  *out_w = ow;
+  return JDS_OK;
+}
+
+int jds_jpeg_render_scaled_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream,
+                               int32_t render, int32_t scale_denom) {
+  int rc;
+  if ((rc = render_check(render)) || (rc = scale_check(render, scale_denom))) return rc;
+  if (scale_denom == 1) return jds_jpeg_render_dev(c, info, coeffs, rgb, stream, render);
+  if (!info) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  if (!c || !coeffs || !rgb) return fail(JDS_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(launch_jpeg_ljs(a, scale_denom, coeffs, rgb, (hipStream_t)stream));
+  return JDS_OK;
+}
+
 int jds_jpeg_inverse_dev(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb, void* stream) {
   return jds_jpeg_render_dev(c, info, coeffs, rgb, stream, JDS_RENDER_REFERENCE);
 }
@@ -316,12 +352,20 @@ int jds_jpeg_to_rgb(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_o
 
 int jds_jpeg_to_rgb_render(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
                            int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render) {
+  return jds_jpeg_to_rgb_scaled(c, data, len, rgb_out, rgb_cap, rgb_on_device, coeffs, info, render, 1);
+}
+
+int jds_jpeg_to_rgb_scaled(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                           int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_info* info, int32_t render,
+                           int32_t scale_denom) {
   int rc;
-  if ((rc = render_check(render))) return rc;
+  if ((rc = render_check(render)) || (rc = scale_check(render, scale_denom))) return rc;
   if (!c || !data || !info || !rgb_out) return fail(JDS_EINVAL, "null argument");
   rc = jds_jpeg_parse(data, len, info);
   if (rc) return rc;
-  const size_t nimg = (size_t)info->H * (size_t)info->W * 3;
+  long long oh, ow;
+  ls_scaled_size(info->H, info->W, scale_denom, &oh, &ow);
+  const size_t nimg = (size_t)oh * (size_t)ow * 3;
   if (rgb_cap < (int64_t)nimg) return fail(JDS_EINVAL, "image buffer too small: %zu bytes needed", nimg);
   JInvArgs a;
   if ((rc = jpeg_inv_args(info, &a))) return rc;
@@ -332,7 +376,10 @@ int jds_jpeg_to_rgb_render(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t
     HIP_TRY(c->out.ensure(nimg));
     dst = (uint8_t*)c->out.p;
   }
-  HIP_TRY(launch_render(render, a, (const int16_t*)c->ent_cf.p, dst, c->stream));
+  if (scale_denom == 1)
+    HIP_TRY(launch_render(render, a, (const int16_t*)c->ent_cf.p, dst, c->stream));
+  else
+    HIP_TRY(launch_jpeg_ljs(a, scale_denom, (const int16_t*)c->ent_cf.p, dst, c->stream));
   if (!rgb_on_device) HIP_TRY(hipMemcpyAsync(rgb_out, dst, nimg, hipMemcpyDeviceToHost, c->stream));
   if (coeffs)
     HIP_TRY(hipMemcpyAsync(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost,
@@ -351,6 +398,18 @@ int jds_selftest_jpeg_render(const jds_jpeg_info* info, const int16_t* coeffs, u
     jpeg_ljt_host_image(a, coeffs, rgb_out);
   else
     jpeg_inv_host(a, coeffs, rgb_out);
+  return JDS_OK;
+}
+
+int jds_selftest_jpeg_render_scaled(const jds_jpeg_info* info, const int16_t* coeffs, uint8_t* rgb_out, int32_t render,
+                                    int32_t scale_denom) {
+  int rc;
+  if ((rc = render_check(render)) || (rc = scale_check(render, scale_denom))) return rc;
+  if (scale_denom == 1) return jds_selftest_jpeg_render(info, coeffs, rgb_out, render);
+  if (!info || !coeffs || !rgb_out) return fail(JDS_EINVAL, "null argument");
+  JInvArgs a;
+  if ((rc = jpeg_inv_args(info, &a))) return rc;
+  jpeg_ljs_host_image(a, scale_denom, coeffs, rgb_out);
   return JDS_OK;
 }
 
@@ -376,7 +435,9 @@ struct BatchPlan {
   std::vector<int> rec_of;          // per file: its record, or -1
   std::vector<int> file_of;         // per record: its file
   std::vector<JInvRec> recs;
-  std::vector<JInvMap> map[JI_MODES];
+  std::vector<JInvMap> map[JI_MODES];          // the full-scale images
+  std::vector<JInvMap> smap[JI_MODES][LS_ND];  // the scaled ones, per denominator 2, 4, 8
+  bool any_scaled = false;
   int64_t rgb_bytes = 0, coef_entries = 0;
   int first_bad = -1;
   char first_msg[400] = "";
@@ -386,8 +447,14 @@ struct BatchPlan {
 // lay the outputs out: images JI_RGB_ALIGN apart at least, coefficients end to
 // end.  A file that fails takes no space and does not stop the batch.
 static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
-                        BatchPlan& bp) {
+                        BatchPlan& bp, int32_t render = JDS_RENDER_REFERENCE, const int32_t* denoms = nullptr,
+                        jds_jpeg_scaled_item* scaled = nullptr) {
   if (n < 0 || (n > 0 && (!data || !lens || !items))) return fail(JDS_EINVAL, "null argument");
+  for (int i = 0; denoms && i < n; ++i) {
+    if (!ls_denom_ok(denoms[i])) return fail(JDS_EINVAL, "file %d: scale_denom %d is not 1, 2, 4 or 8", i, (int)denoms[i]);
+    const int rc = scale_check(render, denoms[i]);
+    if (rc) return rc;
+  }
   bp.info.resize((size_t)n);
   bp.rec_of.assign((size_t)n, -1);
   std::vector<JInvRec> parsed((size_t)n);
@@ -427,7 +494,9 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
       continue;
     }
     long long rb = bp.rgb_bytes, ce = bp.coef_entries;
-    jinv_batch_place(r, (int)bp.recs.size(), info.coeffs_needed, &rb, &ce);
+    const int dn = denoms ? denoms[i] : 1;
+    ls_batch_place(r, (int)bp.recs.size(), dn, info.coeffs_needed, &rb, &ce);
+    bp.any_scaled = bp.any_scaled || dn != 1;
     bp.rgb_bytes = rb;
     bp.coef_entries = ce;
     it.rgb_off = r.rgb_off;
@@ -438,8 +507,17 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
     bp.recs.push_back(r);
   }
   // what the grids and the 32-bit indices of the kernels take
-  if (bp.coef_entries / 64 > 0x7fffffffll || !jinv_batch_maps(bp.recs.data(), (int)bp.recs.size(), bp.map))
+  if (bp.coef_entries / 64 > 0x7fffffffll || !ls_batch_maps(bp.recs.data(), (int)bp.recs.size(), bp.map, bp.smap))
     return fail(JDS_ENOTSUP, "batch of %d files: too many blocks or tiles for one set of launches", n);
+  for (int i = 0; scaled && i < n; ++i) {
+    memset(&scaled[i], 0, sizeof scaled[i]);
+    scaled[i].scale_denom = denoms ? denoms[i] : 1;
+    if (items[i].rc != JDS_OK) continue;
+    long long oh, ow;
+    ls_scaled_size(items[i].H, items[i].W, scaled[i].scale_denom, &oh, &ow);
+    scaled[i].out_h = oh;
+    scaled[i].out_w = ow;
+  }
   return JDS_OK;
 }
 
@@ -456,9 +534,15 @@ static void batch_note(const BatchPlan& bp) {
 
 int jds_jpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
                           int64_t* rgb_bytes, int64_t* coef_entries) {
+  return jds_jpeg_batch_layout_scaled(data, lens, n, items, rgb_bytes, coef_entries, nullptr, nullptr);
+}
+
+int jds_jpeg_batch_layout_scaled(const uint8_t* const* data, const int64_t* lens, int32_t n,
+                                 jds_jpeg_batch_item* items, int64_t* rgb_bytes, int64_t* coef_entries,
+                                 const int32_t* scale_denoms, jds_jpeg_scaled_item* scaled) {
   if (!rgb_bytes || !coef_entries) return fail(JDS_EINVAL, "null argument");
   BatchPlan bp;
-  const int rc = batch_layout(data, lens, n, items, bp);
+  const int rc = batch_layout(data, lens, n, items, bp, JDS_RENDER_LIBJPEG, scale_denoms, scaled);
   if (rc) return rc;
   *rgb_bytes = bp.rgb_bytes;
   *coef_entries = bp.coef_entries;
@@ -474,11 +558,19 @@ int jds_selftest_jpeg_batch(const uint8_t* const* data, const int64_t* lens, int
 int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* lens, int32_t n, int32_t subseq_bits,
                                    uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs, jds_jpeg_batch_item* items,
                                    int32_t render) {
+  return jds_selftest_jpeg_batch_render_scaled(data, lens, n, subseq_bits, rgb, rgb_cap, coeffs, items, render, nullptr,
+                                               nullptr);
+}
+
+int jds_selftest_jpeg_batch_render_scaled(const uint8_t* const* data, const int64_t* lens, int32_t n,
+                                          int32_t subseq_bits, uint8_t* rgb, int64_t rgb_cap, int16_t* coeffs,
+                                          jds_jpeg_batch_item* items, int32_t render, const int32_t* scale_denoms,
+                                          jds_jpeg_scaled_item* scaled) {
   int rc;
   if ((rc = render_check(render))) return rc;
   if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
   BatchPlan bp;
-  rc = batch_layout(data, lens, n, items, bp);
+  rc = batch_layout(data, lens, n, items, bp, render, scale_denoms, scaled);
   if (rc) return rc;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
     return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
@@ -506,6 +598,16 @@ int jds_selftest_jpeg_batch_render(const uint8_t* const* data, const int64_t* le
     jpeg_ljt_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
   else
     jpeg_inv_batch_host(bp.recs.data(), maps, nmap, st.data(), coeffs, rgb);
+  if (bp.any_scaled) {  // (scale_check: the libjpeg rendering)
+    const JInvMap* smaps[JI_MODES][LS_ND];
+    int nsmap[JI_MODES][LS_ND];
+    for (int m = 0; m < JI_MODES; ++m)
+      for (int d = 0; d < LS_ND; ++d) {
+        smaps[m][d] = bp.smap[m][d].data();
+        nsmap[m][d] = (int)bp.smap[m][d].size() - 1;
+      }
+    jpeg_ljs_batch_host(bp.recs.data(), smaps, nsmap, st.data(), coeffs, rgb);
+  }
   batch_note(bp);
   return JDS_OK;
 }
@@ -581,6 +683,14 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
     tiles[m] = bp.map[m].back().tile0;
     nm += (int)bp.map[m].size();
   }
+  int smap_off[JI_MODES][LS_ND], nsmap[JI_MODES][LS_ND], stiles[JI_MODES][LS_ND];
+  for (int m = 0; m < JI_MODES; ++m)
+    for (int d = 0; d < LS_ND; ++d) {  // (a batch without scaled images uploads what it always did)
+      smap_off[m][d] = nm;
+      nsmap[m][d] = bp.any_scaled ? (int)bp.smap[m][d].size() - 1 : 0;
+      stiles[m][d] = bp.any_scaled ? bp.smap[m][d].back().tile0 : 0;
+      if (bp.any_scaled) nm += (int)bp.smap[m][d].size();
+    }
   const size_t o_files = 0, o_tabs = up(o, 256), o_mcu = up(o_tabs + sizeof(HuffDecTab) * tabs.size(), 256),
                o_rec = up(o_mcu + sizeof(HdMcu) * mcus.size(), 256), o_map = up(o_rec + sizeof(JInvRec) * (size_t)nv, 256),
                o_ivil = up(o_map + sizeof(JInvMap) * (size_t)nm, 256), o_ivpl = up(o_ivil + sizeof(RstIv) * iv_il.size(), 256),
@@ -602,6 +712,10 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
   memcpy(h + o_rec, bp.recs.data(), sizeof(JInvRec) * (size_t)nv);
   for (int m = 0; m < JI_MODES; ++m)
     memcpy(h + o_map + sizeof(JInvMap) * (size_t)map_off[m], bp.map[m].data(), sizeof(JInvMap) * bp.map[m].size());
+  for (int m = 0; bp.any_scaled && m < JI_MODES; ++m)
+    for (int d = 0; d < LS_ND; ++d)
+      memcpy(h + o_map + sizeof(JInvMap) * (size_t)smap_off[m][d], bp.smap[m][d].data(),
+             sizeof(JInvMap) * bp.smap[m][d].size());
   if (!iv_il.empty()) memcpy(h + o_ivil, iv_il.data(), sizeof(RstIv) * iv_il.size());
   if (!iv_pl.empty()) memcpy(h + o_ivpl, iv_pl.data(), sizeof(RstIv) * iv_pl.size());
   memcpy(h + o_st, st0.data(), 4 * (size_t)nv);
@@ -641,11 +755,15 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
   else if (inverse)
     HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
                                   st_d, cf_d, dst, s));
+  if (inverse && bp.any_scaled)
+    HIP_TRY(launch_jpeg_ljs_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), smap_off, nsmap, stiles,
+                                  st_d, cf_d, dst, s));
   if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
     for (int k = 0; k < nv; ++k) {
       const JInvRec& r = bp.recs[(size_t)k];
-      HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)r.a.H * (size_t)r.a.W * 3, hipMemcpyDeviceToHost,
-                             s));
+      long long oh, ow;
+      ls_scaled_size(r.a.H, r.a.W, ls_rec_denom(r), &oh, &ow);
+      HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)oh * (size_t)ow * 3, hipMemcpyDeviceToHost, s));
     }
   if (coeffs)
     HIP_TRY(hipMemcpyAsync(coeffs, cf_d, sizeof(int16_t) * (size_t)bp.coef_entries, hipMemcpyDeviceToHost, s));
@@ -667,11 +785,19 @@ int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t*
 int jds_jpeg_batch_to_rgb_render(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
                                  int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
                                  uint32_t* rounds_out, int32_t render) {
+  return jds_jpeg_batch_to_rgb_scaled(c, data, lens, n, rgb, rgb_cap, rgb_on_device, coeffs, items, rounds_out, render,
+                                      nullptr, nullptr);
+}
+
+int jds_jpeg_batch_to_rgb_scaled(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                                 int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
+                                 uint32_t* rounds_out, int32_t render, const int32_t* scale_denoms,
+                                 jds_jpeg_scaled_item* scaled) {
   int rc;
   if ((rc = render_check(render))) return rc;
   if (!c) return fail(JDS_EINVAL, "null argument");
   BatchPlan bp;
-  rc = batch_layout(data, lens, n, items, bp);
+  rc = batch_layout(data, lens, n, items, bp, render, scale_denoms, scaled);
   if (rc) return rc;
   if (rounds_out) *rounds_out = 0;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))

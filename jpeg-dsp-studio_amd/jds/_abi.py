@@ -31,6 +31,20 @@ RENDER_CODES = {'reference': 0, 'libjpeg': 1}    # JDS_RENDER_*
 RUN_SSE, RUN_FWD, RUN_INV, RUN_EXACT, RUN_EXACT_INV, RUN_INV_FIXALL, RUN_FWD_FIXALL, RUN_INV_FAST = 1, 2, 4, 8, 16, 32, 64, 128
 
 
+SCALE_DENOMS = (1, 2, 4, 8)
+
+
+def scale_denom_arg(scale_denom, render=None) -> int:
+    """1, 2, 4 or 8 as an int (ValueError otherwise, naming the value); with `render`, a denominator
+    other than 1 needs render='libjpeg'."""
+    if isinstance(scale_denom, bool) or not isinstance(scale_denom, (int, np.integer)) or int(scale_denom) not in SCALE_DENOMS:
+        raise ValueError(f'scale_denom {scale_denom!r} is not 1, 2, 4 or 8')
+    if render is not None and int(scale_denom) != 1 and render != 'libjpeg':
+        raise ValueError(f"scale_denom {int(scale_denom)} needs render='libjpeg': the reference rendering has no "
+                         f"scaled decode")
+    return int(scale_denom)
+
+
 def render_code(render) -> int:
     """'reference' / 'libjpeg' -> JDS_RENDER_*; anything else: ValueError('unknown render ...')."""
     if not isinstance(render, str) or render not in RENDER_CODES:
@@ -114,6 +128,10 @@ class JpegBatchItem(C.Structure):
     _fields_ = [('rc', C.c_int32), ('status', C.c_uint32), ('H', C.c_int64), ('W', C.c_int64),
                 ('subsampling', C.c_int32), ('interleaved', C.c_int32), ('rgb_off', C.c_int64),
                 ('coef_off', C.c_int64), ('coeffs_needed', C.c_int64)]
+
+
+class JpegScaledItem(C.Structure):
+    _fields_ = [('scale_denom', C.c_int32), ('reserved', C.c_int32), ('out_h', C.c_int64), ('out_w', C.c_int64)]
 
 
 class JpegTranscodeItem(C.Structure):
@@ -233,6 +251,19 @@ _SIGS = {
                                                C.POINTER(JpegBatchItem), C.POINTER(C.c_uint32), C.c_int32]),
     'jds_selftest_jpeg_batch_render': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P,
                                                  C.POINTER(JpegBatchItem), C.c_int32]),
+    'jds_jpeg_scaled_size': (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'jds_jpeg_render_scaled_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P, _P, C.c_int32, C.c_int32]),
+    'jds_jpeg_to_rgb_scaled': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.POINTER(JpegInfo),
+                                         C.c_int32, C.c_int32]),
+    'jds_jpeg_batch_layout_scaled': (C.c_int, [_P, _P, C.c_int32, C.POINTER(JpegBatchItem), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), _P, C.POINTER(JpegScaledItem)]),
+    'jds_jpeg_batch_to_rgb_scaled': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P,
+                                               C.POINTER(JpegBatchItem), C.POINTER(C.c_uint32), C.c_int32, _P,
+                                               C.POINTER(JpegScaledItem)]),
+    'jds_selftest_jpeg_render_scaled': (C.c_int, [C.POINTER(JpegInfo), _P, _P, C.c_int32, C.c_int32]),
+    'jds_selftest_jpeg_batch_render_scaled': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P,
+                                                        C.POINTER(JpegBatchItem), C.c_int32, _P,
+                                                        C.POINTER(JpegScaledItem)]),
     'jds_encode_jpeg': (C.c_int, [_P, C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
                                   C.POINTER(C.c_int64)]),
     'jds_jpeg_transcode': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),

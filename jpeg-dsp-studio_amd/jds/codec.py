@@ -186,32 +186,66 @@ def host_jpeg_inverse(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, gr
     return img
 
 
+def jpeg_scaled_size(H: int, W: int, scale_denom: int = 1) -> Tuple[int, int]:
+    """jds_jpeg_scaled_size: (ceil(H / scale_denom), ceil(W / scale_denom)), the image an H x W
+    file decodes to at scale_denom 1, 2, 4 or 8."""
+    d = _abi.scale_denom_arg(scale_denom)
+    oh, ow = C.c_int64(0), C.c_int64(0)
+    check(lib().jds_jpeg_scaled_size(int(H), int(W), d, C.byref(oh), C.byref(ow)))
+    return int(oh.value), int(ow.value)
+
+
+def draft_denom(H: int, W: int, size) -> int:
+    """The denominator Pillow's Image.draft(mode, size) chooses for an H x W file and a requested
+    size (width, height): the largest of 8, 4, 2, 1 that is at most min(W // size[0],
+    H // size[1]), so the scaled image still covers the request on both axes."""
+    rw, rh = int(size[0]), int(size[1])
+    if rw < 1 or rh < 1:
+        raise ValueError(f'bad requested size {size!r}')
+    scale = min(int(W) // rw, int(H) // rh)
+    return 8 if scale >= 8 else 4 if scale >= 4 else 2 if scale >= 2 else 1
+
+
 def jpeg_render_dev(info: dict, coeffs_ptr: int, rgb_ptr: int, render: str = 'libjpeg', stream=None,
-                    device: int = 0) -> None:
+                    device: int = 0, scale_denom: int = 1) -> None:
     """jds_jpeg_render_dev: jpeg_inverse_dev with the rendering chosen -- 'reference' (the launch
     jpeg_inverse_dev makes) or 'libjpeg' (k_jpeg_ljt: libjpeg's default decode byte for byte,
-    DESIGN.md "libjpeg rendering")."""
+    DESIGN.md "libjpeg rendering").  scale_denom 2, 4 or 8 (render='libjpeg' only):
+    jds_jpeg_render_scaled_dev, k_jpeg_ljs; rgb_ptr then holds jpeg_scaled_size's image."""
     code = _abi.render_code(render)
+    d = _abi.scale_denom_arg(scale_denom, render)
     st = _jpeg_info_struct(info['H'], info['W'], info['mode'], info['qtables'], info['grids'])
     with lease(device) as ctx:
-        check(lib().jds_jpeg_render_dev(ctx.handle, C.byref(st), C.c_void_p(int(coeffs_ptr)),
-                                        C.c_void_p(int(rgb_ptr)), C.c_void_p(int(stream or 0)), code))
+        if d == 1:
+            check(lib().jds_jpeg_render_dev(ctx.handle, C.byref(st), C.c_void_p(int(coeffs_ptr)),
+                                            C.c_void_p(int(rgb_ptr)), C.c_void_p(int(stream or 0)), code))
+        else:
+            check(lib().jds_jpeg_render_scaled_dev(ctx.handle, C.byref(st), C.c_void_p(int(coeffs_ptr)),
+                                                   C.c_void_p(int(rgb_ptr)), C.c_void_p(int(stream or 0)), code, d))
 
 
-def host_jpeg_render(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids, render: str = 'libjpeg') -> np.ndarray:
+def host_jpeg_render(coeffs: np.ndarray, H: int, W: int, mode: str, qtables, grids, render: str = 'libjpeg',
+                     scale_denom: int = 1) -> np.ndarray:
     """Test aid (jds_selftest_jpeg_render): host_jpeg_inverse with the rendering chosen; 'libjpeg'
-    runs k_jpeg_ljt's tile core in a host tile loop.  No GPU."""
+    runs k_jpeg_ljt's tile core in a host tile loop, with scale_denom 2, 4 or 8 k_jpeg_ljs's
+    (jds_selftest_jpeg_render_scaled).  No GPU."""
     code = _abi.render_code(render)
+    d = _abi.scale_denom_arg(scale_denom, render)
     st = _jpeg_info_struct(H, W, mode, qtables, grids)
     cf = np.ascontiguousarray(coeffs, np.int16).reshape(-1)
     if cf.size != int(st.coeffs_needed):
         raise ValueError(f'expected {int(st.coeffs_needed)} coefficients, got {cf.size}')
+    if d != 1:
+        img = np.empty((-(-int(H) // d), -(-int(W) // d), 3), np.uint8)
+        check(lib().jds_selftest_jpeg_render_scaled(C.byref(st), cf.ctypes.data, img.ctypes.data, code, d))
+        return img
     img = np.empty((int(H), int(W), 3), np.uint8)
     check(lib().jds_selftest_jpeg_render(C.byref(st), cf.ctypes.data, img.ctypes.data, code))
     return img
 
 
-def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render: str = 'reference'):
+def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render: str = 'reference',
+                scale_denom: int = 1):
     """jds_jpeg_to_rgb: any baseline JPEG parse_jpeg accepts -> the HxWx3 uint8 image, by the
     entropy decode and one fused inverse launch (k_jpeg_inv) with the file's own tables and
     grids: byte for byte decompress_jpeg(staged=True)'s image.  out: an object with data_ptr()
@@ -219,13 +253,18 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render
     device, written there, and `out` is returned.  with_info: (image, decode_jpeg's dict plus
     'route': 'fused').  render='libjpeg': the same decode, rendered by k_jpeg_ljt to the bytes
     libjpeg's default decode gives (np.asarray(PIL.Image.open(f).convert('RGB')); DESIGN.md
-    "libjpeg rendering")."""
+    "libjpeg rendering").  scale_denom 2, 4 or 8 (render='libjpeg' only): libjpeg's reduced-size
+    decode, PIL's Image.draft, byte for byte (k_jpeg_ljs; DESIGN.md "Scaled libjpeg rendering"):
+    the image, and `out`, are jpeg_scaled_size(H, W, scale_denom) x 3; the info dict gains
+    'scale_denom', 'out_H', 'out_W'."""
     from . import entropy
     code = _abi.render_code(render)
+    d = _abi.scale_denom_arg(scale_denom, render)
     a, p, n = entropy._bytes_arg(data)
     info = _abi.JpegInfo()
     check(lib().jds_jpeg_parse(p, n, C.byref(info)))
-    H, W = int(info.H), int(info.W)
+    fH, fW = int(info.H), int(info.W)
+    H, W = -(-fH // d), -(-fW // d)
     if out is None:
         img = np.empty((H, W, 3), np.uint8)
         dst, on_dev = img.ctypes.data, 0
@@ -235,7 +274,10 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render
         img, dst, on_dev = out, int(out.data_ptr()), 1
     cf = np.empty(int(info.coeffs_needed), np.int16) if with_info else None
     with lease(device) as ctx:
-        if code == 0:
+        if d != 1:
+            check(lib().jds_jpeg_to_rgb_scaled(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
+                                               cf.ctypes.data if with_info else None, C.byref(info), code, d))
+        elif code == 0:
             check(lib().jds_jpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev,
                                         cf.ctypes.data if with_info else None, C.byref(info)))
         else:
@@ -243,9 +285,9 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render
                                                cf.ctypes.data if with_info else None, C.byref(info), code))
     if not with_info:
         return img
-    d = entropy._jpeg_dict(info)
-    d.update(coeffs=cf, rounds=int(info.rounds), route='fused')
-    return img, d
+    dd = entropy._jpeg_dict(info)
+    dd.update(coeffs=cf, rounds=int(info.rounds), route='fused', scale_denom=d, out_H=H, out_W=W)
+    return img, dd
 
 
 def _batch_args(files):
@@ -261,26 +303,45 @@ def _batch_args(files):
     return keep, ptrs, lens
 
 
-def _batch_item_dict(it) -> dict:
+def _batch_denoms(scale_denom, n: int, render=None):
+    """(per-file denominators, the int32 array for the C call or None when all are 1)."""
+    if not isinstance(scale_denom, (list, tuple, np.ndarray)):
+        scale_denom = [_abi.scale_denom_arg(scale_denom, render)] * n
+    dens = [_abi.scale_denom_arg(v, render) for v in _per_item(scale_denom, n, 'scale_denom')]
+    if all(v == 1 for v in dens):
+        return dens, None
+    return dens, (C.c_int32 * max(n, 1))(*dens)
+
+
+def _batch_item_dict(it, denom: int = 1) -> dict:
     from . import entropy
     ok = it.rc == 0
-    return {'rc': int(it.rc), 'status': int(it.status), 'H': int(it.H), 'W': int(it.W),
+    return {'scale_denom': denom, 'out_H': -(-int(it.H) // denom) if it.H > 0 else 0,
+            'out_W': -(-int(it.W) // denom) if it.H > 0 else 0, 'rc': int(it.rc), 'status': int(it.status), 'H': int(it.H), 'W': int(it.W),
             'mode': entropy._MODE_NAMES.get(int(it.subsampling)) if it.H > 0 else None,
             'interleaved': bool(it.interleaved), 'rgb_off': int(it.rgb_off) if ok else -1,
             'coef_off': int(it.coef_off) if ok else -1, 'coeffs_needed': int(it.coeffs_needed)}
 
 
-def jpeg_batch_layout(files):
+def _batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c):
+    if dens_c is None:
+        return lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce))
+    return lib().jds_jpeg_batch_layout_scaled(ptrs, lens, n, items, C.byref(rb), C.byref(ce), dens_c, None)
+
+
+def jpeg_batch_layout(files, scale_denom=1):
     """jds_jpeg_batch_layout (host only): (per-file dicts, rgb_bytes, coef_entries) of a batch.
-    A file's image is bytes [rgb_off, rgb_off + H*W*3) of the batch's output (rgb_off a multiple
-    of 256), its coefficients entries [coef_off, coef_off + coeffs_needed); a file that does not
-    parse has rc != 0 and takes no space."""
+    A file's image is bytes [rgb_off, rgb_off + out_H*out_W*3) of the batch's output (rgb_off a
+    multiple of 256), its coefficients entries [coef_off, coef_off + coeffs_needed); a file that
+    does not parse has rc != 0 and takes no space.  scale_denom: 1, 2, 4 or 8, or one per file
+    (jds_jpeg_batch_layout_scaled): the images are placed by their scaled sizes."""
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
+    dens, dens_c = _batch_denoms(scale_denom, n)
     items = (_abi.JpegBatchItem * max(n, 1))()
     rb, ce = C.c_int64(0), C.c_int64(0)
-    check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
-    return [_batch_item_dict(items[i]) for i in range(n)], int(rb.value), int(ce.value)
+    check(_batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c))
+    return [_batch_item_dict(items[i], dens[i]) for i in range(n)], int(rb.value), int(ce.value)
 
 
 def _batch_first_error(items) -> str:
@@ -294,7 +355,7 @@ def _batch_first_error(items) -> str:
 
 
 def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False, errors: str = 'raise', ctx=None,
-                      render: str = 'reference'):
+                      render: str = 'reference', scale_denom=1):
     """jds_jpeg_batch_to_rgb: a sequence of baseline JPEGs (bytes-likes; any mix of sizes,
     subsampling modes, tables, restart intervals and scan forms) -> their images, decoded in one
     set of launches; each image is byte for byte jpeg_to_rgb's.  out=None: a list of HxWx3 uint8
@@ -305,17 +366,21 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     None in its place.  with_info: (images, {'items': per-file dicts, 'rounds': the batch's
     propagation rounds, 'rgb_bytes', 'coef_entries'}).  ctx: a caller-owned Context of that device
     (e.g. a profiled one) instead of a pooled one.  render='libjpeg': every image rendered as
-    jpeg_to_rgb(render='libjpeg') does (k_jpeg_ljt_batch), the same layout and error contract."""
+    jpeg_to_rgb(render='libjpeg') does (k_jpeg_ljt_batch), the same layout and error contract.
+    scale_denom: 1, 2, 4 or 8, or one per file (render='libjpeg' for any other than 1): each
+    image is jpeg_to_rgb(scale_denom=...)'s, out_H x out_W x 3, placed by that size
+    (k_jpeg_ljs_batch, one launch per mode and denominator present)."""
     if errors not in ('raise', 'return'):
         raise ValueError("errors must be 'raise' or 'return'")
     code = _abi.render_code(render)
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
+    dens, dens_c = _batch_denoms(scale_denom, n, render)
     items = (_abi.JpegBatchItem * max(n, 1))()
     if out is None or isinstance(out, str):
         # the output is sized here, from the layout; a caller's buffer is checked by the call itself
         rb, ce = C.c_int64(0), C.c_int64(0)
-        check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
+        check(_batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c))
         cap = int(rb.value)
     if out is None:
         buf = np.empty(max(cap, 1), np.uint8)
@@ -335,6 +400,9 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     rounds = C.c_uint32(0)
 
     def run(c):
+        if dens_c is not None:
+            return lib().jds_jpeg_batch_to_rgb_scaled(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None,
+                                                      items, C.byref(rounds), code, dens_c, None)
         if code == 0:
             return lib().jds_jpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None, items,
                                                C.byref(rounds))
@@ -345,7 +413,7 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     else:
         with lease(device) as c:
             check(run(c))
-    info = [_batch_item_dict(items[i]) for i in range(n)]
+    info = [_batch_item_dict(items[i], dens[i]) for i in range(n)]
     first = _batch_first_error(info)
     if first and errors == 'raise':
         raise ValueError(first)
@@ -354,35 +422,40 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
         if it['rc'] != 0 or it['status'] != 0:
             imgs.append(None)
             continue
-        o, sz = it['rgb_off'], it['H'] * it['W'] * 3
-        imgs.append(buf[o:o + sz].reshape(it['H'], it['W'], 3))
+        o, sz = it['rgb_off'], it['out_H'] * it['out_W'] * 3
+        imgs.append(buf[o:o + sz].reshape(it['out_H'], it['out_W'], 3))
     if not with_info:
         return imgs
     ok = [it for it in info if it['rc'] == 0]
     return imgs, {'items': info, 'rounds': int(rounds.value),
-                  'rgb_bytes': sum(-(-it['H'] * it['W'] * 3 // 256) * 256 for it in ok),
+                  'rgb_bytes': sum(-(-it['out_H'] * it['out_W'] * 3 // 256) * 256 for it in ok),
                   'coef_entries': sum(it['coeffs_needed'] for it in ok)}
 
 
-def host_jpeg_batch(files, subseq_bits: int = 1024, render: str = 'reference'):
+def host_jpeg_batch(files, subseq_bits: int = 1024, render: str = 'reference', scale_denom=1):
     """Test aid (jds_selftest_jpeg_batch): the batch's layout, the host decode model per file and
     the host model of the batch inverse.  -> (rgb buffer, coefficient buffer, per-file dicts).  No GPU.
-    render='libjpeg': jds_selftest_jpeg_batch_render with k_jpeg_ljt_batch's host model."""
+    render='libjpeg': jds_selftest_jpeg_batch_render with k_jpeg_ljt_batch's host model;
+    scale_denom (an int or one per file): jds_selftest_jpeg_batch_render_scaled, k_jpeg_ljs_batch's."""
     code = _abi.render_code(render)
     keep, ptrs, lens = _batch_args(files)
     n = len(keep)
+    dens, dens_c = _batch_denoms(scale_denom, n, render)
     items = (_abi.JpegBatchItem * max(n, 1))()
     rb, ce = C.c_int64(0), C.c_int64(0)
-    check(lib().jds_jpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce)))
+    check(_batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c))
     rgb = np.full(max(int(rb.value), 1), 0xA5, np.uint8)
     cf = np.zeros(max(int(ce.value), 1), np.int16)
-    if code == 0:
+    if dens_c is not None:
+        check(lib().jds_selftest_jpeg_batch_render_scaled(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data,
+                                                          int(rb.value), cf.ctypes.data, items, code, dens_c, None))
+    elif code == 0:
         check(lib().jds_selftest_jpeg_batch(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
                                             cf.ctypes.data, items))
     else:
         check(lib().jds_selftest_jpeg_batch_render(ptrs, lens, n, int(subseq_bits), rgb.ctypes.data, int(rb.value),
                                                    cf.ctypes.data, items, code))
-    return rgb[:int(rb.value)], cf[:int(ce.value)], [_batch_item_dict(items[i]) for i in range(n)]
+    return rgb[:int(rb.value)], cf[:int(ce.value)], [_batch_item_dict(items[i], dens[i]) for i in range(n)]
 
 
 def jpeg_transcode(data, optimize: bool = True, device: int = 0, with_info: bool = False):

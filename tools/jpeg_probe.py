@@ -38,6 +38,9 @@ beside them, in the same run, the same pictures as 4:2:0 colour files (--batch's
 and call: the median time, the per-kernel times from the context's launch marks, bytes in and out,
 the rounds; four outputs of each call compared with the single call.  Writes
 profiles/gray_probe.json (or --out FILE).
+--scale N (default 64) instead: the 1080p Pillow 4:2:0 batch at scale_denom 1, 2, 4, 8, see
+scale_main.  Writes profiles/jpeg_scale_probe.json (or --out FILE).
+
 --render N (default 64) instead: the two renderings ('reference', 'libjpeg') side by side, see
 render_main.  Writes profiles/jpeg_render_probe.json (or --out FILE).
 --encode N (default 64) instead: the way back, pixels to files: N 1080p pictures in a device tensor
@@ -579,6 +582,76 @@ def render_main():
     return 0 if all(r['libjpeg_equals_pillow'] for r in rows) else 1
 
 
+def scale_main():
+    """--scale [N]: the N (default 64) 1080p Pillow Q50 4:2:0 files of the --render batch leg through
+    jpeg_batch_to_rgb(out=tensor, render='libjpeg', scale_denom=d) at d = 1, 2, 4, 8, the four
+    alternating call by call in one process: the whole call by the host clock (median, min, max of
+    10 after 2 warm-ups); k_jpeg_ljt_batch (d = 1) and k_jpeg_ljs_batch (d = 2, 4, 8) from the
+    context's launch marks (events), per batch, in ROUNDS (default 7) rounds of 3 alternating
+    repetitions each -- median over the rounds and their min / max, the spread the comparison is
+    read against; the output bytes (derived from the layout); four images per denominator against
+    Pillow's Image.draft.  Writes profiles/jpeg_scale_probe.json (or --out FILE)."""
+    import torch
+    from jds import _abi
+    i = sys.argv.index('--scale')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    rounds = int(os.environ.get('ROUNDS', '7'))
+    pics = [np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8) for k in range(n)]
+    files = [pillow_file(p) for p in pics]
+    dens = (1, 2, 4, 8)
+    row = {'leg': 'batch_pillow_q50_420_1080p_scaled', 'n': n, 'H': H, 'W': W,
+           'file_bytes_total': int(sum(len(f) for f in files)), 'denominators': list(dens), 'rounds': rounds}
+    ctx = _abi.Context(0)
+    outs, row['output_bytes'], row['equals_pillow'] = {}, {}, {}
+    for d in dens:
+        items, rgb_bytes, _ = codec.jpeg_batch_layout(files, scale_denom=d)
+        outs[d] = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+        row['output_bytes'][str(d)] = int(sum(it['out_H'] * it['out_W'] * 3 for it in items))
+        views = codec.jpeg_batch_to_rgb(files, out=outs[d], ctx=ctx, render='libjpeg', scale_denom=d)
+        ok = True
+        for k in range(0, n, max(1, n // 4)):
+            im = Image.open(io.BytesIO(files[k]))
+            if d != 1:
+                im.draft('RGB', (W // d, H // d))
+            ok = ok and np.array_equal(views[k].cpu().numpy(), np.asarray(im.convert('RGB')))
+        row['equals_pillow'][str(d)] = bool(ok)
+    t = {d: [] for d in dens}
+    for r in range(2 + 10):
+        for d in dens:
+            t0 = time.perf_counter()
+            codec.jpeg_batch_to_rgb(files, out=outs[d], ctx=ctx, render='libjpeg', scale_denom=d)
+            if r >= 2:
+                t[d].append((time.perf_counter() - t0) * 1e3)
+    row['jpeg_batch_to_rgb_device_ms'] = {str(d): {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v)}
+                                          for d, v in t.items()}
+    ctx.profile(True)
+    ctx.profile_read()
+    reps, per = 3, {d: [] for d in dens}
+    for _ in range(rounds):
+        for _ in range(reps):
+            for d in dens:
+                codec.jpeg_batch_to_rgb(files, out=outs[d], ctx=ctx, render='libjpeg', scale_denom=d)
+        kern, _ = ctx.profile_read()
+        for d in dens:
+            name = 'k_jpeg_ljt_batch<2>' if d == 1 else f'k_jpeg_ljs_batch<2,{d}>'
+            per[d].append(kern[name][0] / reps)
+    ctx.profile(False)
+    ctx.close()
+    row['kernel_ms_per_batch'] = {('k_jpeg_ljt_batch' if d == 1 else f'k_jpeg_ljs_batch_1/{d}'):
+                                  {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v), 'rounds': v}
+                                  for d, v in per.items()}
+    full = row['kernel_ms_per_batch']['k_jpeg_ljt_batch']
+    row['scaled_not_slower_than_full'] = {k: bool(v['median'] <= full['median'] + (full['max'] - full['min']))
+                                          for k, v in row['kernel_ms_per_batch'].items() if k != 'k_jpeg_ljt_batch'}
+    print(json.dumps(row), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'jpeg_scale_probe.json')
+    with open(out, 'w') as f:
+        json.dump([row], f, indent=1)
+        f.write('\n')
+    return 0 if all(row['equals_pillow'].values()) else 1
+
+
 def encode_main():
     """--encode [N]: N (default 64) 1080p noise pictures in one device tensor through
     rgb_batch_to_jpeg (4:2:0, quality 75, out='device'), plain and optimize=True, against N
@@ -647,6 +720,8 @@ def encode_main():
 def main():
     if '--encode' in sys.argv:
         return encode_main()
+    if '--scale' in sys.argv:
+        return scale_main()
     if '--render' in sys.argv:
         return render_main()
     if '--gray' in sys.argv:
