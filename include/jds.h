@@ -983,6 +983,86 @@ int jds_rgb_batch_to_jpeg(jds_ctx* ctx, const uint8_t* rgb_base, int32_t rgb_on_
 int jds_selftest_jpeg_forward(const jds_jpeg_info* info, const uint8_t* rgb, int16_t* coeffs_out);
 int jds_selftest_jpeg_fwd_quant(int32_t q, int32_t n, int32_t* out, int32_t* bound);
 
+/* Pillow resizing (DESIGN.md "Pillow resizing"; definition:
+ * tests/pillow_resize_ref.py): packed 8-bit RGB -> the bytes Pillow's
+ * Image.resize(size, resample, box) gives, byte for byte: ImagingResample's
+ * coefficients built in double on the host with the C library's sin / cos,
+ * 22-bit fixed-point taps, the horizontal pass rounded to uint8, then the
+ * vertical one, a pass Pillow skips skipped, and Image.resize's rule that an
+ * image more than 100 times as tall as wide that shrinks is resized vertically
+ * first (two launches through a scratch image).  One kernel (k_resize /
+ * k_resize_batch, csrc/jds_resize.hip) does both passes of an output tile; the
+ * intermediate image is never written.  Image.thumbnail and reducing_gap go
+ * through Pillow's separate ImagingReduce and are not provided; neither is
+ * NEAREST, nor float or planar output.
+ *
+ * resample: JDS_RESAMPLE_* (Pillow's numbers); anything else, 0 (NEAREST)
+ *   included, is JDS_EINVAL naming the value.
+ * box: x0, y0, x1, y1 in pixels of the source, as C floats (Pillow's own
+ *   type); NULL: the whole image.  0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H, or
+ *   JDS_EINVAL.  out_h, out_w >= 1.
+ * JDS_ENOTSUP: an axis that needs more than the tap cap of taps per output
+ *   sample (2 * ceil(support * max(scale, 1)) + 1; the message names the need
+ *   and the cap), a table with which a 32-bit accumulator could overflow (255 *
+ *   sum|k| + 2^21 above 2^31 - 1), an image of more than 2^31 - 1 bytes or tiles.
+ * Images are rows of 3 * W bytes without padding at any byte alignment; an
+ *   output is out_h * out_w * 3 bytes.  Nothing outside an output is written,
+ *   and of a source only the rows and columns the tables name are read.
+ *
+ * jds_resize_info: host only; the default output tile and the tap cap.
+ * jds_rgb_resize: one image from host memory or (rgb_on_device != 0) memory of
+ *   the context's device, to host or device memory.  Synchronous.
+ * jds_rgb_batch_resize: image i is bytes [rgb_off, rgb_off + H * W * 3) of
+ *   rgb_base_dev (any offset: what jds_jpeg_batch_to_rgb reports serves);
+ *   output i is bytes [i, i + 1) * out_h * out_w * 3 of out_dev.  The tables
+ *   and records are uploaded, then one launch on `stream` (NULL: the null stream)
+ *   after the scratch launch of the tall images; the call returns when they
+ *   have run (the tables are the context's, and the next call rewrites
+ *   them).  n == 0 is valid.
+ * jds_jpeg_batch_to_tensor: jds_jpeg_batch_to_rgb_scaled with
+ *   JDS_RENDER_LIBJPEG into scratch of the context, then the batch resize on
+ *   the same stream: out is n slots of out_h * out_w * 3 bytes in file order
+ *   (out_cap at least that, JDS_EINVAL otherwise).  scale_denoms NULL: per file
+ *   the largest of 8, 4, 2, 1 that is at most min(W / out_w, H / out_h)
+ *   (Pillow's Image.draft).  boxes (nullable): n x 4 floats in the coordinates
+ *   of the image as decoded at its denominator.  A file that fails (items[i].rc
+ *   or .status, as jds_jpeg_batch_to_rgb reports them) keeps its slot, filled
+ *   with zeros; the call returns JDS_OK and jds_last_error names the first.
+ *   scaled (nullable): the denominators used and the decoded sizes.
+ *   Synchronous.
+ * jds_selftest_resize: test-only, host only: the tile core (csrc/jds_resize.hpp)
+ *   in a host tile loop with the tiles the device would use.  *worst
+ *   (nullable): the largest 255 * sum|k| + 2^21 of the tables built.
+ * jds_selftest_resize_coeffs: test-only, host only: one axis' table.  bounds:
+ *   2 * out_size int32 (first input sample, count), taps: out_size * *ksize
+ *   int32, cap: the entries `taps` holds (JDS_EINVAL, with *ksize set, if too
+ *   few).  The tap cap does not apply. */
+#define JDS_RESAMPLE_LANCZOS 1
+#define JDS_RESAMPLE_BILINEAR 2
+#define JDS_RESAMPLE_BICUBIC 3
+#define JDS_RESAMPLE_BOX 4
+#define JDS_RESAMPLE_HAMMING 5
+typedef struct {
+  int64_t rgb_off; /* the image's first byte from rgb_base_dev */
+  int64_t H, W;
+  int32_t has_box; /* 0: the whole image */
+  float box[4];    /* x0, y0, x1, y1 */
+  int32_t reserved;
+} jds_resize_item;
+int jds_resize_info(int32_t* tile_h, int32_t* tile_w, int32_t* max_taps);
+int jds_rgb_resize(jds_ctx* ctx, const uint8_t* rgb, int32_t rgb_on_device, int64_t H, int64_t W, const float* box,
+                   int64_t out_h, int64_t out_w, int32_t resample, uint8_t* out, int32_t out_on_device);
+int jds_rgb_batch_resize(jds_ctx* ctx, const uint8_t* rgb_base_dev, const jds_resize_item* items, int32_t n,
+                         int64_t out_h, int64_t out_w, int32_t resample, uint8_t* out_dev, void* stream);
+int jds_jpeg_batch_to_tensor(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n, int64_t out_h,
+                             int64_t out_w, int32_t resample, const int32_t* scale_denoms, const float* boxes,
+                             uint8_t* out, int64_t out_cap, int32_t out_on_device, jds_jpeg_batch_item* items,
+                             jds_jpeg_scaled_item* scaled, uint32_t* rounds_out);
+int jds_selftest_resize(const uint8_t* rgb, int64_t H, int64_t W, const float* box, int64_t out_h, int64_t out_w,
+                        int32_t resample, uint8_t* out, int64_t* worst);
+int jds_selftest_resize_coeffs(int32_t in_size, float in0, float in1, int32_t out_size, int32_t resample,
+                               int32_t* ksize, int32_t* bounds, int32_t* taps, int64_t cap);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp; the host model: csrc/jds_jpeg_parse.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

@@ -436,6 +436,7 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->mcu_up.release();
   c->mcu_scr.release();
   if (c->bat_host) (void)hipHostFree(c->bat_host);
+  resize_ctx_release(c);
   marks_release(c->marks);
   c->gen_tab.release();
   c->gen_sub.release();

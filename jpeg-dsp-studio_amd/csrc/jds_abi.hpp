@@ -143,6 +143,13 @@ hipError_t launch_jpeg_ljs(const JInvArgs& a, int denom, const int16_t* coeffs, 
 hipError_t launch_jpeg_ljs_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES][3],
                                  const int nmap[JI_MODES][3], const int tiles[JI_MODES][3], const uint32_t* status,
                                  const int16_t* coeffs, uint8_t* rgb, hipStream_t s);
+// Pillow resizing (jds_resize.hip; records and maps: jds_resize.hpp)
+struct RsRec;
+struct RsMap;
+hipError_t launch_resize(const RsRec& r, const int32_t* tabs, const uint8_t* src, uint8_t* dst, hipStream_t s);
+hipError_t launch_resize_batch(const RsRec* recs, const RsMap* map, int nmap, int tiles, const uint32_t* status,
+                               const int32_t* tabs, const uint8_t* src0, const uint8_t* src1, uint8_t* dst0,
+                               uint8_t* dst1, hipStream_t s);
 hipError_t launch_jpeg_fwd(const JInvArgs& a, const uint8_t* img, int16_t* coeffs, hipStream_t s);
 hipError_t launch_jpeg_fwd_batch(const JInvRec* recs, const JInvMap* maps, const int map_off[JI_MODES],
                                  const int nmap[JI_MODES], const int tiles[JI_MODES], const uint8_t* img,
@@ -220,6 +227,12 @@ struct jds_ctx {
   DevBuf mcu_up, mcu_scr;  // interleaved-scan writer (jds_jpeg_transcode): its uploads (records, segment table, prefixes), scratch
   void* bat_host = nullptr;
   size_t bat_host_cap = 0;
+  // Pillow resizing: the tables, records and maps of a call (pinned host staging, device copy), the scratch
+  // image of the tall-image rule, jds_jpeg_batch_to_tensor's decoded images, the event behind a call's launches
+  DevBuf rsz_tab, rsz_tall, rsz_src;
+  void* rsz_host = nullptr;
+  size_t rsz_host_cap = 0;
+  hipEvent_t rsz_ev = nullptr;
   // jds_ctx_profile: launch marks of the batch calls on this context
   KMarks marks;
   bool prof_on = false;
@@ -279,3 +292,21 @@ static void batch_parallel(int n, F fn) {
 // c->ent_cf (a decoded frame) -> rgb_out by the plan's inverse (jds_abi.hip).
 int inverse_of_decoded(jds_ctx* c, const jds_params* prm, int64_t H, int64_t W, int64_t n_coeffs, uint8_t* rgb_out,
                        int16_t* coeffs);
+
+// A batch resize (jds_abi_resize.hip): image i of n is H x W at byte `off` of
+// the source, its slot bytes [i, i + 1) * oh * ow * 3 of the output; st: the
+// status word that zeroes the slot when set (-1: none), zero: the slot is zeros.
+struct ResizeSrc {
+  long long off, H, W;
+  int st, zero, has_box;
+  float box[4];
+};
+struct ResizeJob;
+// The plans, tables and records on the host (JDS_EINVAL / JDS_ENOTSUP as jds.h says).
+int resize_job_build(const ResizeSrc* items, int n, long long oh, long long ow, int resample, ResizeJob** out);
+// The upload and the launches on s; wait: return once they have run (the staging and the tables may be
+// rewritten); without it the caller synchronises s before the context is used again.
+int resize_job_enqueue(jds_ctx* c, ResizeJob* j, const uint8_t* src_dev, const uint32_t* status_dev, uint8_t* out_dev,
+                       hipStream_t s, bool wait);
+void resize_job_free(ResizeJob* j);
+void resize_ctx_release(jds_ctx* c);

@@ -438,6 +438,7 @@ struct BatchPlan {
   std::vector<JInvMap> map[JI_MODES];          // the full-scale images
   std::vector<JInvMap> smap[JI_MODES][LS_ND];  // the scaled ones, per denominator 2, 4, 8
   bool any_scaled = false;
+  std::vector<int> denom;  // per file: the denominator it is decoded at
   int64_t rgb_bytes = 0, coef_entries = 0;
   int first_bad = -1;
   char first_msg[400] = "";
@@ -446,9 +447,11 @@ struct BatchPlan {
 // Parse every file, check what the single call checks before it decodes, and
 // lay the outputs out: images JI_RGB_ALIGN apart at least, coefficients end to
 // end.  A file that fails takes no space and does not stop the batch.
+// draft (without denoms): {width, height} asked for; a file's denominator is
+// then the largest of 8, 4, 2, 1 that is at most min(W / width, H / height).
 static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
                         BatchPlan& bp, int32_t render = JDS_RENDER_REFERENCE, const int32_t* denoms = nullptr,
-                        jds_jpeg_scaled_item* scaled = nullptr) {
+                        jds_jpeg_scaled_item* scaled = nullptr, const int64_t* draft = nullptr) {
   if (n < 0 || (n > 0 && (!data || !lens || !items))) return fail(JDS_EINVAL, "null argument");
   for (int i = 0; denoms && i < n; ++i) {
     if (!ls_denom_ok(denoms[i])) return fail(JDS_EINVAL, "file %d: scale_denom %d is not 1, 2, 4 or 8", i, (int)denoms[i]);
@@ -457,6 +460,7 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
   }
   bp.info.resize((size_t)n);
   bp.rec_of.assign((size_t)n, -1);
+  bp.denom.assign((size_t)n, 1);
   std::vector<JInvRec> parsed((size_t)n);
   std::vector<std::string> msg((size_t)n);  // (the message of a failing file: g_err is per thread)
   batch_parallel(n, [&](int i) {
@@ -494,7 +498,12 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
       continue;
     }
     long long rb = bp.rgb_bytes, ce = bp.coef_entries;
-    const int dn = denoms ? denoms[i] : 1;
+    int dn = denoms ? denoms[i] : 1;
+    if (!denoms && draft) {
+      const int64_t sc = info.W / draft[0] < info.H / draft[1] ? info.W / draft[0] : info.H / draft[1];
+      dn = sc >= 8 ? 8 : sc >= 4 ? 4 : sc >= 2 ? 2 : 1;
+    }
+    bp.denom[(size_t)i] = dn;
     ls_batch_place(r, (int)bp.recs.size(), dn, info.coeffs_needed, &rb, &ce);
     bp.any_scaled = bp.any_scaled || dn != 1;
     bp.rgb_bytes = rb;
@@ -511,7 +520,7 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
     return fail(JDS_ENOTSUP, "batch of %d files: too many blocks or tiles for one set of launches", n);
   for (int i = 0; scaled && i < n; ++i) {
     memset(&scaled[i], 0, sizeof scaled[i]);
-    scaled[i].scale_denom = denoms ? denoms[i] : 1;
+    scaled[i].scale_denom = denoms ? denoms[i] : bp.denom[(size_t)i];
     if (items[i].rc != JDS_OK) continue;
     long long oh, ow;
     ls_scaled_size(items[i].H, items[i].W, scaled[i].scale_denom, &oh, &ow);
@@ -616,9 +625,12 @@ int jds_selftest_jpeg_batch_render_scaled(const uint8_t* const* data, const int6
 // decode into c->ent_cf (file k's coefficients at bp.recs[k].coef_off), then
 // with `inverse` the batch inverse into rgb; the status words into items.
 // Synchronous.  Without `inverse` (jds_jpeg_batch_transcode) rgb is not used.
+// after (nullable): called with the device status words once the rendering is
+// in the stream, for work that follows it there.
 static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
                      int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, uint32_t* rounds_out,
-                     bool inverse, int32_t render = JDS_RENDER_REFERENCE) {
+                     bool inverse, int32_t render = JDS_RENDER_REFERENCE,
+                     const std::function<int(const uint32_t*, hipStream_t)>* after = nullptr) {
   const int nv = (int)bp.recs.size();
   hipStream_t s = c->stream;
   HIP_TRY(hipSetDevice(c->device));
@@ -758,6 +770,10 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
   if (inverse && bp.any_scaled)
     HIP_TRY(launch_jpeg_ljs_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), smap_off, nsmap, stiles,
                                   st_d, cf_d, dst, s));
+  if (after) {  // (jds_jpeg_batch_to_tensor: the resize behind the rendering, on the same stream)
+    const int rc = (*after)(st_d, s);
+    if (rc) return rc;
+  }
   if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
     for (int k = 0; k < nv; ++k) {
       const JInvRec& r = bp.recs[(size_t)k];
@@ -805,6 +821,74 @@ int jds_jpeg_batch_to_rgb_scaled(jds_ctx* c, const uint8_t* const* data, const i
   if (!bp.recs.empty() &&
       (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true, render)))
     return rc;
+  batch_note(bp);
+  return JDS_OK;
+}
+
+// The decode above with JDS_RENDER_LIBJPEG into scratch of the context, then
+// the batch resize behind it on the same stream (jds_abi_resize.hip; DESIGN.md
+// "Pillow resizing").
+int jds_jpeg_batch_to_tensor(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, int64_t out_h,
+                             int64_t out_w, int32_t resample, const int32_t* scale_denoms, const float* boxes,
+                             uint8_t* out, int64_t out_cap, int32_t out_on_device, jds_jpeg_batch_item* items,
+                             jds_jpeg_scaled_item* scaled, uint32_t* rounds_out) {
+  if (!c) return fail(JDS_EINVAL, "null argument");
+  if (out_h < 1 || out_w < 1)
+    return fail(JDS_EINVAL, "bad size: %lld x %lld (width x height)", (long long)out_w, (long long)out_h);
+  if (out_h * out_w > 0x7fffffffll / 3 || out_h > 0x7fffffffll || out_w > 0x7fffffffll)
+    return fail(JDS_ENOTSUP, "image too large: more than 2^31 - 1 bytes");
+  const int64_t slot = out_h * out_w * 3, draft[2] = {out_w, out_h};
+  BatchPlan bp;
+  int rc = batch_layout(data, lens, n, items, bp, JDS_RENDER_LIBJPEG, scale_denoms, scaled, draft);
+  if (rc) return rc;
+  if (rounds_out) *rounds_out = 0;
+  if (n > 0 && (!out || out_cap < slot * n))
+    return fail(JDS_EINVAL, "output too small: %lld bytes needed", (long long)(slot * n));
+  std::vector<ResizeSrc> src((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    ResizeSrc& r = src[(size_t)i];
+    memset(&r, 0, sizeof r);
+    r.st = -1;
+    r.zero = items[i].rc != JDS_OK;
+    if (r.zero) continue;
+    const JInvRec& rec = bp.recs[(size_t)bp.rec_of[(size_t)i]];
+    long long oh, ow;
+    ls_scaled_size(items[i].H, items[i].W, bp.denom[(size_t)i], &oh, &ow);
+    r.off = rec.rgb_off;
+    r.H = oh;
+    r.W = ow;
+    r.st = rec.st;
+    r.has_box = boxes != nullptr;
+    for (int k = 0; boxes && k < 4; ++k) r.box[k] = boxes[4 * (size_t)i + k];
+  }
+  ResizeJob* job = nullptr;
+  if ((rc = resize_job_build(src.data(), n, out_h, out_w, resample, &job))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  uint8_t* dst = out;
+  hipError_t e = c->rsz_src.ensure((size_t)bp.rgb_bytes);
+  if (e == hipSuccess && !out_on_device && n > 0) {
+    e = c->out.ensure((size_t)(slot * n));
+    dst = (uint8_t*)c->out.p;
+  }
+  if (e != hipSuccess) {
+    resize_job_free(job);
+    HIP_TRY(e);
+  }
+  const std::function<int(const uint32_t*, hipStream_t)> after = [&](const uint32_t* st_d, hipStream_t s) -> int {
+    const int r2 = resize_job_enqueue(c, job, (const uint8_t*)c->rsz_src.p, st_d, dst, s, false);
+    if (r2) return r2;
+    if (!out_on_device) HIP_TRY(hipMemcpyAsync(out, dst, (size_t)(slot * n), hipMemcpyDeviceToHost, s));
+    return JDS_OK;
+  };
+  if (!bp.recs.empty()) {
+    rc = batch_run(c, bp, data, lens, (uint8_t*)c->rsz_src.p, 1, nullptr, items, rounds_out, true, JDS_RENDER_LIBJPEG,
+                   &after);
+  } else if (n > 0) {  // no file decodes: every slot is zeros
+    rc = after(nullptr, c->stream);
+    if (rc == JDS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(JDS_EHIP, "hipStreamSynchronize");
+  }
+  resize_job_free(job);
+  if (rc) return rc;
   batch_note(bp);
   return JDS_OK;
 }

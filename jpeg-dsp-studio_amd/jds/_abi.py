@@ -145,6 +145,28 @@ class RgbItem(C.Structure):
                 ('subsampling', C.c_int32)]
 
 
+class ResizeItem(C.Structure):
+    _fields_ = [('rgb_off', C.c_int64), ('H', C.c_int64), ('W', C.c_int64), ('has_box', C.c_int32),
+                ('box', C.c_float * 4), ('reserved', C.c_int32)]
+
+
+# Pillow's filter numbers (include/jds.h JDS_RESAMPLE_*)
+RESAMPLE_CODES = {'lanczos': 1, 'bilinear': 2, 'bicubic': 3, 'box': 4, 'hamming': 5}
+
+
+def resample_code(resample) -> int:
+    """A filter name or Pillow's number (an int or an Image.Resampling member) -> JDS_RESAMPLE_*.
+    A name that is none of the five is a ValueError here; a number goes to the library, which
+    names it."""
+    if isinstance(resample, str):
+        if resample.lower() not in RESAMPLE_CODES:
+            raise ValueError(f'unknown resampling filter {resample!r}: one of {", ".join(RESAMPLE_CODES)}')
+        return RESAMPLE_CODES[resample.lower()]
+    if isinstance(resample, bool) or not isinstance(resample, (int, np.integer)):
+        raise ValueError(f'unknown resampling filter {resample!r}')
+    return int(resample)
+
+
 # lossless transform operations (include/jds.h JDS_XF_*)
 XF_OPS = {'none': 0, 'hflip': 1, 'vflip': 2, 'transpose': 3, 'transverse': 4, 'rot90': 5, 'rot180': 6, 'rot270': 7,
           'auto': 8}
@@ -290,6 +312,18 @@ _SIGS = {
     'jds_rgb_batch_to_jpeg': (C.c_int, [_P, _P, C.c_int32, C.POINTER(RgbItem), C.c_int32, C.c_int32, _P, C.c_int64,
                                         C.c_int32, C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
     'jds_selftest_jpeg_forward': (C.c_int, [C.POINTER(JpegInfo), _P, _P]),
+    'jds_resize_info': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'jds_rgb_resize': (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P,
+                                 C.c_int32]),
+    'jds_rgb_batch_resize': (C.c_int, [_P, _P, C.POINTER(ResizeItem), C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P,
+                                       _P]),
+    'jds_jpeg_batch_to_tensor': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
+                                           C.c_int64, C.c_int32, C.POINTER(JpegBatchItem), C.POINTER(JpegScaledItem),
+                                           C.POINTER(C.c_uint32)]),
+    'jds_selftest_resize': (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P,
+                                      C.POINTER(C.c_int64)]),
+    'jds_selftest_resize_coeffs': (C.c_int, [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                             C.POINTER(C.c_int32), _P, _P, C.c_int64]),
     'jds_selftest_jpeg_fwd_quant': (C.c_int, [C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'jds_selftest_jpeg_window': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'jds_selftest_dct8x8': (C.c_int, [_P, _P, C.c_int64, C.c_int32]),

@@ -834,6 +834,253 @@ def rgb_batch_to_jpeg(images, quality=75, subsampling='4:2:0', optimize: bool = 
     return outs if errors == 'raise' else (outs, info)
 
 
+# ------------------------------------------------------------ Pillow resizing --
+# (DESIGN.md "Pillow resizing"; Image.thumbnail and reducing_gap go through Pillow's separate
+# reduce and are not provided, nor is NEAREST)
+
+def resize_info() -> Tuple[int, int, int]:
+    """jds_resize_info: (tile_h, tile_w, max_taps) -- k_resize's default output tile and the taps
+    per output sample an axis may need."""
+    th, tw, mt = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(lib().jds_resize_info(C.byref(th), C.byref(tw), C.byref(mt)))
+    return int(th.value), int(tw.value), int(mt.value)
+
+
+def _size_arg(size) -> Tuple[int, int]:
+    try:
+        w, h = size
+        w, h = int(w), int(h)
+    except (TypeError, ValueError):
+        raise ValueError(f'size must be (width, height), got {size!r}') from None
+    return w, h
+
+
+def _box_arg(box):
+    """None, or the four C floats of (x0, y0, x1, y1)."""
+    if box is None:
+        return None
+    b = [float(v) for v in box]
+    if len(b) != 4:
+        raise ValueError(f'box must be (x0, y0, x1, y1), got {box!r}')
+    return (C.c_float * 4)(*b)
+
+
+def _rgb3_arg(image, device: int = 0):
+    keep, p, on_dev, H, W, gray = _image_arg(image, device)
+    if gray:
+        raise ValueError(f'an image is HxWx3, got shape ({H}, {W})')
+    return keep, p, on_dev, H, W
+
+
+def host_rgb_resize(image, size, resample, box=None, with_worst: bool = False):
+    """Test aid (jds_selftest_resize): k_resize's tile core in a host tile loop, with the tiles
+    the device would use.  with_worst: (image, the largest 255 * sum|k| + 2^21 of the tables
+    built -- what a 32-bit accumulator has to hold).  No GPU."""
+    keep, p, on_dev, H, W = _rgb3_arg(image)
+    if on_dev:
+        raise ValueError('host_rgb_resize takes a host array')
+    w, h = _size_arg(size)
+    out = np.empty((max(h, 0), max(w, 0), 3), np.uint8)
+    worst = C.c_int64(0)
+    check(lib().jds_selftest_resize(C.c_void_p(p), H, W, _box_arg(box), h, w, _abi.resample_code(resample),
+                                    out.ctypes.data if out.size else C.c_void_p(keep.ctypes.data), C.byref(worst)))
+    return (out, int(worst.value)) if with_worst else out
+
+
+def host_resize_coeffs(in_size: int, in0: float, in1: float, out_size: int, resample):
+    """Test aid (jds_selftest_resize_coeffs): one axis' table as (ksize, bounds (out_size, 2),
+    taps (out_size, ksize))."""
+    code = _abi.resample_code(resample)
+    ks = C.c_int32(0)
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    taps = np.zeros(1, np.int32)
+    rc = lib().jds_selftest_resize_coeffs(int(in_size), in0, in1, int(out_size), code, C.byref(ks),
+                                          bounds.ctypes.data, taps.ctypes.data, 0)
+    if rc == _abi.JDS_EINVAL and ks.value > 0:
+        taps = np.zeros((int(out_size), int(ks.value)), np.int32)
+        rc = lib().jds_selftest_resize_coeffs(int(in_size), in0, in1, int(out_size), code, C.byref(ks),
+                                              bounds.ctypes.data, taps.ctypes.data, taps.size)
+    check(rc)
+    return int(ks.value), bounds, taps
+
+
+def _tensor_out(out, shape, device: int):
+    """A caller's contiguous uint8 device tensor of `shape`, checked."""
+    if not _is_tensor(out) or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.element_size() != 1 \
+            or not out.is_cuda or out.device.index != int(device):
+        raise ValueError(f'out must be a contiguous uint8 {tuple(shape)} tensor on device {int(device)}')
+    return out
+
+
+def rgb_resize(image, size, resample='bilinear', box=None, device: int = 0, out=None):
+    """jds_rgb_resize: an HxWx3 uint8 image -- a NumPy array or a contiguous torch tensor on
+    `device` -- -> PIL's Image.resize(size, resample, box) of it, byte for byte (k_resize; DESIGN.md
+    "Pillow resizing").  size: (width, height), as in Pillow; resample: 'lanczos', 'bilinear',
+    'bicubic', 'box', 'hamming' or Pillow's number; box: (x0, y0, x1, y1) in source pixels.  Returns
+    an (height, width, 3) array for an array and a device tensor for a tensor; out: a device tensor
+    of that shape to write instead.  ValueError for an unknown filter, a size below 1, a box that is
+    empty or not within the image, or a reduction beyond the tap cap (resize_info)."""
+    keep, p, on_dev, H, W = _rgb3_arg(image, device)
+    w, h = _size_arg(size)
+    code = _abi.resample_code(resample)
+    bx = _box_arg(box)
+    if out is not None:
+        res = _tensor_out(out, (h, w, 3), device)
+        dst, out_dev = int(res.data_ptr()), 1
+    elif on_dev:
+        import torch
+        res = torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=f'cuda:{device}')
+        dst, out_dev = int(res.data_ptr()), 1
+    else:
+        res = np.empty((max(h, 0), max(w, 0), 3), np.uint8)
+        dst, out_dev = res.ctypes.data, 0
+    if on_dev or out_dev:
+        _torch_settled(device)
+    with lease(device) as ctx:
+        check(lib().jds_rgb_resize(ctx.handle, C.c_void_p(p), on_dev, H, W, bx, h, w, code, C.c_void_p(dst or p),
+                                   out_dev))
+    return res
+
+
+def _boxes_arg(boxes, n: int):
+    """(per-image boxes or Nones, has-any)."""
+    if boxes is None:
+        return [None] * n
+    boxes = list(boxes)
+    if len(boxes) == 4 and all(isinstance(v, (int, float, np.integer, np.floating)) for v in boxes):
+        boxes = [tuple(boxes)] * n                   # one box for every image
+    if len(boxes) != n:
+        raise ValueError(f'{len(boxes)} boxes for {n} images')
+    return boxes
+
+
+def rgb_batch_resize(images, size, resample='bilinear', boxes=None, out=None, device: int = 0, ctx=None):
+    """jds_rgb_batch_resize: N device images of any sizes -> one (N, height, width, 3) uint8 device
+    tensor, slot i rgb_resize(images[i], ...)'s bytes, by one launch of k_resize_batch on torch's
+    current stream (and one before it for images more than 100 times as tall as wide); the call
+    returns when they have run.  images: a
+    sequence of contiguous HxWx3 uint8 device tensors (views into one allocation -- e.g.
+    jpeg_batch_to_rgb(out='device')'s -- are passed by offset, anything else is gathered into one
+    buffer first) or an NxHxWx3 device tensor.  boxes: None, one box, or one (or None) per image.
+    out: a device tensor of the result's shape.  ctx: a caller-owned Context."""
+    import torch
+    if _is_tensor(images):
+        if images.dim() != 4:
+            raise ValueError(f'a batch tensor is NxHxWx3, got shape {tuple(images.shape)}')
+        if not images.is_contiguous():
+            raise ValueError('a device image must be a contiguous tensor')
+        images = [images[i] for i in range(int(images.shape[0]))]
+    args = [_rgb3_arg(im, device) for im in images]
+    n = len(args)
+    if not all(a[2] for a in args):
+        raise ValueError('rgb_batch_resize takes device tensors (rgb_resize takes an array)')
+    w, h = _size_arg(size)
+    code = _abi.resample_code(resample)
+    bxs = _boxes_arg(boxes, n)
+    base, offs, keep = 0, [], None
+    if n:
+        bases = {int(a[0].untyped_storage().data_ptr()) for a in args}
+        if len(bases) == 1:
+            base, keep = bases.pop(), [a[0] for a in args]
+            offs = [a[1] - base for a in args]
+        else:
+            sizes = [a[3] * a[4] * 3 for a in args]
+            keep = torch.cat([a[0].reshape(-1) for a in args])
+            base, offs = int(keep.data_ptr()), [0] + [int(v) for v in np.cumsum(sizes[:-1])]
+    items = (_abi.ResizeItem * max(n, 1))()
+    for i, (a, o, b) in enumerate(zip(args, offs, bxs)):
+        items[i].rgb_off, items[i].H, items[i].W = int(o), a[3], a[4]
+        if b is not None:
+            items[i].has_box = 1
+            items[i].box = _box_arg(b)
+    if out is not None:
+        res = _tensor_out(out, (n, h, w, 3), device)
+    else:
+        res = torch.empty((n, max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=f'cuda:{device}')
+    stream = int(torch.cuda.current_stream(device).cuda_stream)
+
+    def run(c):
+        return lib().jds_rgb_batch_resize(c.handle, C.c_void_p(base or 1), items, n, h, w, code,
+                                          C.c_void_p(int(res.data_ptr()) or 1), C.c_void_p(stream))
+    if ctx is not None:
+        check(run(ctx))
+    else:
+        with lease(device) as c:
+            check(run(c))
+    return res
+
+
+def jpeg_batch_to_tensor(files, size, resample='bilinear', scale_denom='draft', boxes=None, out='device',
+                         errors: str = 'raise', with_info: bool = False, device: int = 0, ctx=None):
+    """jds_jpeg_batch_to_tensor: N baseline JPEGs of any sizes -> one (N, height, width, 3) uint8
+    tensor: jpeg_batch_to_rgb(render='libjpeg', scale_denom=...)'s decode into scratch of the context,
+    then k_resize_batch behind it on the same stream.  With scale_denom='draft' slot i is, byte for
+    byte, Pillow's  im = Image.open(f); im.draft('RGB', size); im.convert('RGB').resize(size, resample)
+    (draft_denom per file); scale_denom may also be 1, 2, 4, 8 or one per file.  boxes: as
+    rgb_batch_resize's, in the coordinates of the image as decoded at its denominator.  A grayscale
+    file yields (Y, Y, Y).  out='device': a torch tensor on `device`; None: a NumPy array; or a
+    caller's device tensor of the result's shape.  A file that does not parse or whose scan data
+    are defective keeps its slot, filled with zeros: errors='raise' raises ValueError naming the
+    first such index after the batch has run, errors='return' returns (tensor, bad indices).
+    with_info: a dict {'items': per-file dicts with 'scale_denom', 'out_H', 'out_W' of the decode,
+    'rounds'} comes last."""
+    if errors not in ('raise', 'return'):
+        raise ValueError("errors must be 'raise' or 'return'")
+    w, h = _size_arg(size)
+    code = _abi.resample_code(resample)
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    if isinstance(scale_denom, str):
+        if scale_denom != 'draft':
+            raise ValueError(f"scale_denom {scale_denom!r} is not 'draft', 1, 2, 4 or 8")
+        dens_c = None
+    else:
+        dens, _ = _batch_denoms(scale_denom, n, 'libjpeg')
+        dens_c = (C.c_int32 * max(n, 1))(*dens)
+    bxs = _boxes_arg(boxes, n)
+    boxes_c = None
+    if any(b is not None for b in bxs):
+        if any(b is None for b in bxs):
+            raise ValueError('boxes: one for every file, or none')
+        boxes_c = (C.c_float * (4 * n))(*[v for b in bxs for v in _box_arg(b)])
+    shape = (n, max(h, 0), max(w, 0), 3)
+    if out is None:
+        res = np.empty(shape, np.uint8)
+        dst, on_dev = res.ctypes.data, 0
+    else:
+        if isinstance(out, str):
+            if out != 'device':
+                raise ValueError("out must be None, 'device' or a device tensor of the result's shape")
+            import torch
+            res = torch.empty(shape, dtype=torch.uint8, device=f'cuda:{device}')
+        else:
+            res = _tensor_out(out, (n, h, w, 3), device)
+        dst, on_dev = int(res.data_ptr()), 1
+        _torch_settled(device)
+    items = (_abi.JpegBatchItem * max(n, 1))()
+    scaled = (_abi.JpegScaledItem * max(n, 1))()
+    rounds = C.c_uint32(0)
+
+    def run(c):
+        return lib().jds_jpeg_batch_to_tensor(c.handle, ptrs, lens, n, h, w, code, dens_c, boxes_c, C.c_void_p(dst or 1),
+                                              n * max(h, 0) * max(w, 0) * 3, on_dev, items, scaled, C.byref(rounds))
+    if ctx is not None:
+        check(run(ctx))
+    else:
+        with lease(device) as c:
+            check(run(c))
+    info = [_batch_item_dict(items[i], max(int(scaled[i].scale_denom), 1)) for i in range(n)]
+    first = _batch_first_error(info)
+    if first and errors == 'raise':
+        raise ValueError(first)
+    ret = (res,)
+    if errors == 'return':
+        ret += ([i for i, it in enumerate(info) if it['rc'] != 0 or it['status'] != 0],)
+    if with_info:
+        ret += ({'items': info, 'rounds': int(rounds.value)},)
+    return ret[0] if len(ret) == 1 else ret
+
+
 def psnr_ssim_raw(a: np.ndarray, b: np.ndarray, device: int = 0) -> np.ndarray:
     """jds_psnr_ssim: [ssim_R, ssim_G, ssim_B, ssim_Y, mse_Y, mse_RGB] for two HxWx3 uint8 images."""
     a = _u8_image(a)

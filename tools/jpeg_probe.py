@@ -43,6 +43,9 @@ scale_main.  Writes profiles/jpeg_scale_probe.json (or --out FILE).
 
 --render N (default 64) instead: the two renderings ('reference', 'libjpeg') side by side, see
 render_main.  Writes profiles/jpeg_render_probe.json (or --out FILE).
+--resize N (default 64) instead: the same batch to one (N, 224, 224, 3) tensor, bicubic, through
+jpeg_batch_to_tensor with the draft denominator and with scale_denom=1, see resize_main.  Writes
+profiles/jpeg_resize_probe.json (or --out FILE).
 --encode N (default 64) instead: the way back, pixels to files: N 1080p pictures in a device tensor
 through rgb_batch_to_jpeg against N rgb_to_jpeg calls, see encode_main.  Writes
 profiles/jpeg_encode_probe.json (or --out FILE)."""
@@ -652,6 +655,89 @@ def scale_main():
     return 0 if all(row['equals_pillow'].values()) else 1
 
 
+def resize_main():
+    """--resize [N]: the N (default 64) 1080p Pillow Q50 4:2:0 files of --scale to one (N, 224, 224, 3)
+    device tensor, bicubic, in two legs: 'draft' (Image.draft's denominator: 4, 480 x 270 decoded)
+    and 'full' (scale_denom=1).  Per leg jpeg_batch_to_tensor alternates call by call with the
+    decode-only jpeg_batch_to_rgb(out=tensor, render='libjpeg', scale_denom=...) on the same context:
+    whole calls by the host clock (median, min, max of 10 after 2 warm-ups); then k_resize_batch and
+    the render kernel beside it from the context's launch marks (events) in ROUNDS (default 7) rounds
+    of 3 repetitions -- median over the rounds and their min / max; the bytes the resize reads and
+    writes; every slot against Pillow's draft + resize.  Two conditions are evaluated for the draft
+    leg: the resize kernel takes no longer than the render kernel, and the whole call exceeds the
+    decode-only call plus the resize kernel by no more than the decode-only call's spread.  Writes
+    profiles/jpeg_resize_probe.json (or --out FILE)."""
+    import torch
+    from jds import _abi
+    i = sys.argv.index('--resize')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    rounds = int(os.environ.get('ROUNDS', '7'))
+    size, flt = (224, 224), 'bicubic'
+    files = [pillow_file(np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8)) for k in range(n)]
+    ctx = _abi.Context(0)
+    out = torch.empty((n, size[1], size[0], 3), dtype=torch.uint8, device='cuda')
+    rows = []
+    for leg, den in (('draft', 'draft'), ('full', 1)):
+        d = codec.draft_denom(H, W, size) if den == 'draft' else 1
+        items, rgb_bytes, _ = codec.jpeg_batch_layout(files, scale_denom=d)
+        dec = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+        row = {'leg': f'batch_pillow_q50_420_1080p_to_224_bicubic_{leg}', 'n': n, 'H': H, 'W': W, 'scale_denom': d,
+               'decoded_H': items[0]['out_H'], 'decoded_W': items[0]['out_W'], 'rounds': rounds,
+               'file_bytes_total': int(sum(len(f) for f in files)),
+               'resize_bytes_read': int(sum(it['out_H'] * it['out_W'] * 3 for it in items)),
+               'resize_bytes_written': int(out.numel())}
+
+        def tensor():
+            return codec.jpeg_batch_to_tensor(files, size, flt, scale_denom=den, out=out, ctx=ctx)
+
+        def decode():
+            return codec.jpeg_batch_to_rgb(files, out=dec, ctx=ctx, render='libjpeg', scale_denom=d)
+        got = tensor().cpu().numpy()
+        ok = True
+        for k in range(n):
+            im = Image.open(io.BytesIO(files[k]))
+            if den == 'draft':
+                im.draft('RGB', size)
+            ok = ok and np.array_equal(got[k], np.asarray(im.convert('RGB').resize(size, Image.Resampling.BICUBIC)))
+        row['equals_pillow'] = bool(ok)
+        t = {'tensor': [], 'decode': []}
+        for r in range(2 + 10):
+            for name, fn in (('tensor', tensor), ('decode', decode)):
+                t0 = time.perf_counter()
+                fn()
+                if r >= 2:
+                    t[name].append((time.perf_counter() - t0) * 1e3)
+        row['whole_call_ms'] = {k: {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v)} for k, v in t.items()}
+        ctx.profile(True)
+        ctx.profile_read()
+        reps, per = 3, {'k_resize_batch': [], 'render': []}
+        render = 'k_jpeg_ljt_batch<2>' if d == 1 else f'k_jpeg_ljs_batch<2,{d}>'
+        for _ in range(rounds):
+            for _ in range(reps):
+                tensor()
+                decode()
+            kern, _ = ctx.profile_read()
+            per['k_resize_batch'].append(kern['k_resize_batch'][0] / reps)
+            per['render'].append(kern[render][0] / (2 * reps))          # (both calls launch it)
+        ctx.profile(False)
+        row['render_kernel'] = render
+        row['kernel_ms_per_batch'] = {k: {'median': sorted(v)[len(v) // 2], 'min': min(v), 'max': max(v), 'rounds': v}
+                                      for k, v in per.items()}
+        wc, km = row['whole_call_ms'], row['kernel_ms_per_batch']
+        row['resize_not_slower_than_render'] = bool(km['k_resize_batch']['median'] <= km['render']['median'])
+        row['whole_call_excess_ms'] = wc['tensor']['median'] - wc['decode']['median'] - km['k_resize_batch']['median']
+        row['whole_call_within_decode_spread'] = bool(row['whole_call_excess_ms'] <= wc['decode']['max'] - wc['decode']['min'])
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    ctx.close()
+    dst = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'jpeg_resize_probe.json')
+    with open(dst, 'w') as f:
+        json.dump(rows, f, indent=1)
+        f.write('\n')
+    return 0 if all(r['equals_pillow'] for r in rows) else 1
+
+
 def encode_main():
     """--encode [N]: N (default 64) 1080p noise pictures in one device tensor through
     rgb_batch_to_jpeg (4:2:0, quality 75, out='device'), plain and optimize=True, against N
@@ -720,6 +806,8 @@ def encode_main():
 def main():
     if '--encode' in sys.argv:
         return encode_main()
+    if '--resize' in sys.argv:
+        return resize_main()
     if '--scale' in sys.argv:
         return scale_main()
     if '--render' in sys.argv:
