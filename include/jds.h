@@ -38,7 +38,11 @@ extern "C" {
 /* jds_plan_run flags */
 #define JDS_RUN_SSE 1u  /* fill sse_rgb / sse_y (PSNR); the inverse kernel re-reads the input */
 #define JDS_RUN_FWD 2u  /* forward phase only (stats reset + k_fwd); with neither FWD nor INV: both */
-#define JDS_RUN_INV 4u  /* inverse phase only (k_inv + finalize); needs the forward's coeffs/stats */
+#define JDS_RUN_INV 4u  /* inverse phase only (k_inv + finalize); needs the forward's coeffs/stats.  The
+                           coefficients are the caller's: the certified fast inverse bounds |q Q| from
+                           the values it reads.  Only a run of both phases in one call (8x8 blocks,
+                           tiled geometry) certifies with the fixed bound |q Q| <= 1152 that holds
+                           for its own forward's output */
 #define JDS_RUN_EXACT 8u /* all-fp64 kernels (default: certified fp32 + exact fp64 fix-up, same results) */
 #define JDS_RUN_EXACT_INV 16u /* inverse only: the replayed-order fp64 kernel instead of the certified fast
                                  inverse + tile fix-up (same bytes; A/B and tests) */
@@ -149,7 +153,10 @@ int jds_plan_run(jds_plan* plan, const uint8_t* rgb, uint8_t* rgb_out, int16_t* 
                  jds_frame_stats* stats, uint32_t flags, void* stream);
 int jds_plan_geometry(const jds_plan* plan, jds_geometry* out);
 /* Entries the last run's fix-up lists received: [0] forward blocks recomputed exactly (k_fix_fwd),
-   [1] inverse tiles the certified fast inverse handed to the exact kernel (k_inv2_list). */
+   [1] inverse tiles the certified fast inverse handed to the exact kernel (k_inv2_list).  A run of
+   both phases in one call certifies against the fixed bound |q Q| <= 1152, an inverse-only run
+   (JDS_RUN_INV) against the bound it tracks over the tile (max |q| times max Q: larger on most tables, smaller
+   where the coefficients are small): [1] of the two can differ, the bytes cannot. */
 int jds_plan_fix_counts(const jds_plan* plan, uint32_t* counts);
 void jds_plan_destroy(jds_plan* plan);
 
@@ -1103,13 +1110,26 @@ int jds_selftest_fwd16(int32_t subsampling, int32_t prefilter, const double* gau
  * grid) evaluated on the host with the kernel's own helpers, for an H x W image
  * (even H at 4:2:0, even W at 4:2:x) from coefficients in the
  * IntermediateData.all_quantized_coeffs layout and one 8x8 quant table.
- * fuse: 0 = every multiply-add rounded twice, 1 = every one fused (the device
- * compiler may pick either per site).  values: H*W*3 f64, the value v' the
- * certificate judges (RGB order); bytes: H*W*3, the kernel's byte for it.
+ * fuse: bit 0: 0 = every multiply-add rounded twice, 1 = every one fused (the
+ * device compiler may pick either per site); bit 1: the offset form full runs
+ * take (the a-priori certificate: S grid steps of 2^-32 ride on the luma
+ * constant, jds_selftest_inv_cert reports S).  values: H*W*3 f64, the value v'
+ * the certificate judges (RGB order; with bit 1 v' + S * 2^-32, uncertain when
+ * its fraction is below 2 S * 2^-32); bytes: H*W*3, the kernel's byte for it.
  * Lets the CPU suite test tools/inv_bound.py's bound (K_LIN / K_CONST)
  * adversarially against the oracle's pre-truncation values. */
 int jds_selftest_inv_fast(int32_t subsampling, const int16_t* coeffs, const double* qtable, int64_t H, int64_t W,
                           int32_t fuse, double* values, uint8_t* bytes);
+
+/* Test-only, host only: both forms of the certified inverse's test at the
+ * a-priori threshold of full runs (|q Q| <= 1152: T = ceil(E * 2^32) + 1 grid
+ * steps, S = T + 1) on n given values (|v| < 2^19, RGB values before
+ * truncation).  Per value i: bytes[2i], certain[2i] = the two-sided form on
+ * v + MAGIC (uncertain when the fraction word lo <= T or lo >= 2^32 - 1 - T);
+ * bytes[2i+1], certain[2i+1] = the one-sided form on v + MAGIC + S * 2^-32
+ * (uncertain when lo'' < 2 S).  consts[5] = K_LIN, K_CONST, the |q Q| bound,
+ * T, S as compiled into the kernels. */
+int jds_selftest_inv_cert(const double* values, int64_t n, uint8_t* bytes, uint8_t* certain, double* consts);
 
 /* Test-only: the same for 16x16 blocks (k_inv16_fast's chain: fidct16 lines,
  * coefficients in 16x16 blocks, Q16[u][v] = qtable[u/2][v/2]); pins

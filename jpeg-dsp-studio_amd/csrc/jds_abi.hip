@@ -157,8 +157,11 @@ struct jds_plan {
   int last_fwd8_bank = -1;       // bank of the last such run (jds_plan_fix_counts), -1: none
   InvFix inv_fix() const {
     return {(unsigned*)invfix.p, (unsigned*)invfix.p + 16, 0, (int)(inv_runs & 1u), (int)(inv_runs % 3u),
-            (int)(inv_runs % 16u == 15u), (uint2*)invlist.p};
+            (int)(inv_runs % 16u == 15u), (uint2*)invlist.p, 0};
   }
+  // the forward's samples stay in [-128, 127.5] (InvFix::apriori's premise):
+  // no prefilter, or taps that are non-negative and sum to at most 1
+  bool apriori_ok = false;
   DevBuf planes;  // 16x16 path: reconstructed chroma planes (n x 2 x hc x wc f64)
   double* qt = nullptr;  // host copy of the per-frame 8x8 tables (entropy headers)
   DevBuf ent[8], ent_hdr, ent_tab;  // entropy coder scratch, allocated by the first jds_plan_entropy
@@ -510,6 +513,10 @@ int jds_plan_create_q(jds_ctx* ctx, const jds_params* params, int n_frames, int 
   p->mode = mode;
   p->pf = pf;
   p->g = g;
+  {
+    const double* gs = params[0].gauss;
+    p->apriori_ok = !pf || (gs[0] >= 0.0 && gs[1] >= 0.0 && gs[2] >= 0.0 && gs[0] + gs[1] + gs[2] <= 1.0 + 0x1p-40);
+  }
   hipError_t e;
   if ((e = p->fq.ensure(sizeof(FrameQ) * n)) != hipSuccess || (e = p->gk.ensure(3 * sizeof(double))) != hipSuccess ||
       (e = p->part.ensure(sizeof(double) * (size_t)n *
@@ -727,6 +734,8 @@ int jds_plan_run(jds_plan* p, const uint8_t* rgb, uint8_t* rgb_out, int16_t* coe
   }
   InvFix fx = p->inv_fix();
   fx.fix_all = (flags & JDS_RUN_INV_FIXALL) ? 1 : 0;
+  // both phases in this call: the inverse reads what the forward just wrote
+  fx.apriori = phases == 3 && p->apriori_ok;
   const bool exact_inv = exact || (flags & JDS_RUN_EXACT_INV) != 0 || (!p->inv_fast_any && !(flags & JDS_RUN_INV_FAST));
   if (phases & 2)
     HIP_TRY(launch_codec(p->mode, p->pf, p->g, p->n, rgb, rgb_out, coeffs, (const FrameQ*)p->fq.p,
@@ -1723,6 +1732,14 @@ int jds_selftest_inv_fast(int32_t subsampling, const int16_t* coeffs, const doub
     return fail(JDS_EINVAL, "bad argument");
   if (inv_fast_host(subsampling, coeffs, qtable, (int)H, (int)W, fuse, 8, values, bytes))
     return fail(JDS_EINVAL, "odd chroma geometry: the certified inverse runs even sizes only");
+  return JDS_OK;
+}
+
+int jds_selftest_inv_cert(const double* values, int64_t n, uint8_t* bytes, uint8_t* certain, double* consts) {
+  if (!values || !bytes || !certain || !consts || n < 0) return fail(JDS_EINVAL, "bad argument");
+  for (int64_t i = 0; i < n; ++i)
+    if (!(fabs(values[i]) < 0x1p+19)) return fail(JDS_EINVAL, "values[%lld] outside (-2^19, 2^19)", (long long)i);
+  inv_cert_forms_host(values, n, bytes, certain, consts);
   return JDS_OK;
 }
 

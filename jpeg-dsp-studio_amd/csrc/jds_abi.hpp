@@ -62,6 +62,7 @@ int fwd32_host_plane(int mode, bool pf, const double* gk, const uint8_t* rgb, in
 void fast_fwd_thresholds(const double* Q, int mode, bool pf, const double* gk, float* rq, float* thr);
 int inv_fast_host(int mode, const int16_t* cf, const double* Q, int H, int W, int fuse, int block, double* vout,
                   uint8_t* bout);
+void inv_cert_forms_host(const double* v, long long n, uint8_t* bytes, uint8_t* certain, double* consts);
 size_t fast_q_size();
 hipError_t stage_rgb_ycc(const double* in, double* out, long long n, int inverse, hipStream_t s);
 hipError_t stage_subsample(const double* in, double* tmp, double* tmp2, double* out, int H, int W, int sy,

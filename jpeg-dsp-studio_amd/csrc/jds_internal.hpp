@@ -110,6 +110,11 @@ struct Fwd16Fast {
 // * list (k_inv_fast6, 4:2:0): the (frame, tile) of every tile the run hands
 //   to the exact kernel, count[parity] entries (n x tiles capacity), walked by
 //   k_inv6_fix right after.
+// * apriori: the coefficients are this run's forward output (jds_plan_run with
+//   both phases in one call), so |q Q| <= 1152 by construction and the 8x8
+//   kernels take the a-priori certificate (jds_inv_fast.hip, AP): a constant
+//   threshold instead of the tracked Dmax.  Never set for an inverse-only run,
+//   whose coefficients are the caller's.
 struct InvFix {
   unsigned* count;
   unsigned* item;
@@ -118,6 +123,7 @@ struct InvFix {
   int rot;
   int probe;
   uint2* list;
+  int apriori;
 };
 
 // Per-frame quantiser: q16 = 16*Q (pocketfft's first-axis fct = 1/16 folded in), q = Q.

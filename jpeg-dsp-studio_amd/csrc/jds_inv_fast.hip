@@ -36,7 +36,8 @@
 // reference value is an integer up to pocketfft noise) always do, so those
 // tiles cost fast + exact.  (Recomputing only the affected blocks was
 // measured slower: the per-round bookkeeping cost the common path more than
-// it saved.)
+// it saved.)  Full runs, whose coefficients are their own forward's, certify
+// against a fixed Dmax instead and track nothing (AP, below the constants).
 //
 // Work decomposition and LDS layout are k_inv2's (jds_inv_common.hpp): one
 // workgroup per tile, chroma window (with the ring the upsample reaches into)
@@ -71,6 +72,27 @@ constexpr double K_CONST = 1.024801e-12 * 1.01;
 // the same for 16x16 blocks (fidct16 vs dct3_line16, tools/inv_bound.py --b16)
 constexpr double K_LIN16 = 3.345910e-12 * 1.01;
 constexpr double K_CONST16 = 1.024801e-12 * 1.01;
+
+// The a-priori certificate (AP) of full runs.  When the inverse reads the
+// coefficients the same run's forward has just written (InvFix::apriori),
+// |q * Q| <= 1152 holds by construction: the orthonormal 8x8 DCT of samples in
+// [-128, 127.5] has |c| <= 8 * 128, Q <= 255 (check_tables) and rounding c / Q
+// moves q * Q by at most Q / 2 (the plan sets the flag only when the
+// prefilter's taps are non-negative and sum to at most 1, so that the chroma
+// samples stay in that range).  With Dmax = AP_DMAX the threshold is a
+// compile-time constant, T = ceil(E * 2^32) + 1 grid steps, so no lane tracks
+// the coefficients it reads, and the two-sided test on a value's fraction word
+// lo (uncertain when lo <= T or lo >= 2^32 - 1 - T) becomes one-sided: with
+// S = T + 1 grid steps added to the constant the luma receives anyway, every
+// fraction word is lo'' = (lo + S) mod 2^32 and the value is uncertain exactly
+// when lo'' < 2 S (lo <= T gives lo'' <= 2 S - 1; lo >= 2^32 - S wraps into
+// [0, S - 1]; anything else stays >= 2 S without a wrap).  A certain value saw
+// no carry into its high word, so its byte is the unshifted one.
+constexpr double AP_DMAX = 1152.0;
+constexpr uint32_t ceil_u32(double x) { return (uint32_t)x + ((double)(uint32_t)x < x ? 1u : 0u); }
+constexpr uint32_t AP_T = ceil_u32((K_LIN * AP_DMAX + K_CONST + 0x1p-31) * 0x1p+32) + 1u;
+constexpr uint32_t AP_S = AP_T + 1u;
+static_assert(2u * AP_S < (1u << 16), "the one-sided window must stay far below 2^32");
 
 // AAN scale factors a_k = sqrt(2) cos(k pi / 16), a_0 = 1 (correctly rounded;
 // tools/inv_bound.py reads them from this list and prices their representation
@@ -165,7 +187,8 @@ __host__ __device__ __forceinline__ double col_g(double gt, double cr) { return 
 // AAN, into the transpose buffer (no +128: fast_row clips to [-128, 127] and
 // the luma's +128 rides on the magic constant, see byte_cert_y).
 // qhi / qlo track the largest and smallest q the lane read (integer max3 /
-// min3 chains: cheaper than an fp64 max of |q| per coefficient).
+// min3 chains: cheaper than an fp64 max of |q| per coefficient); not with AP
+// (the a-priori bound needs no Dmax).
 // The folded table is held transposed in LDS (column v's eight
 // entries contiguous, rows padded to QS_STRIDE doubles so the 8 columns' 16-B
 // slots fall on disjoint banks): four ds_read_b128 per column instead of four
@@ -173,6 +196,7 @@ __host__ __device__ __forceinline__ double col_g(double gt, double cr) { return 
 constexpr int QS_STRIDE = 10;
 constexpr int QS_WORDS = 1 ? 8 * QS_STRIDE : 64;
 __device__ __forceinline__ int qs_index(int r, int v) { return 1 ? v * QS_STRIDE + r : r * 8 + v; }
+template <bool AP = false>
 __device__ __forceinline__ void fast_col(const Col16& in, const double* __restrict__ qs, int v,
                                          double* __restrict__ dst, int& qhi, int& qlo) {
   double c[8];
@@ -186,8 +210,10 @@ __device__ __forceinline__ void fast_col(const Col16& in, const double* __restri
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const double qd = (double)in.q[r];
-    qhi = max(qhi, (int)in.q[r]);
-    qlo = min(qlo, (int)in.q[r]);
+    if constexpr (!AP) {
+      qhi = max(qhi, (int)in.q[r]);
+      qlo = min(qlo, (int)in.q[r]);
+    }
     c[r] = qd * t[r];
   }
   aan8(c);
@@ -273,13 +299,20 @@ __device__ __forceinline__ uint32_t byte_cert_y(double y, uint32_t& lo_min, uint
 }
 
 // The same without the clamp: the high word itself, whose low 16 bits are
-// floor(v') as an int16 (|v'| < 2^15), for pack4s.
+// floor(v') as an int16 (|v'| < 2^15), for pack4s.  AP: y carries the offset
+// AP_S, and the smallest shifted fraction word alone decides (lo_max unused).
+template <bool AP = false>
 __device__ __forceinline__ uint32_t cert_hi(double y, uint32_t& lo_min, uint32_t& lo_max) {
   const uint32_t lo = (uint32_t)__double2loint(y), hi = (uint32_t)__double2hiint(y);
   lo_min = lo_min < lo ? lo_min : lo;
-  lo_max = lo_max > lo ? lo_max : lo;
+  if constexpr (!AP) lo_max = lo_max > lo ? lo_max : lo;
   return hi;
 }
+// Y's constant on the magic grid: + 128 (fast_row's planes are level-shifted)
+// and, with AP, the S grid steps of the one-sided certificate (exact: the
+// grid's spacing at MAGIC is 2^-32)
+template <bool AP>
+constexpr double Y_OFF = MAGIC + 128.0 + (AP ? (double)AP_S * 0x1p-32 : 0.0);
 // Four bytes clamp(int16 low half, 0, 255) of cert_hi words a, b, c, d into one
 // word: the int16 pairs by two byte permutes, v_sat_pk_u8_i16 clamps and packs
 // each pair, one shift-or joins them (5 operations instead of 4 med3 + 3).
@@ -333,7 +366,7 @@ __device__ __forceinline__ void cert_to_lds(uint32_t mn, uint32_t mx, uint32_t q
 // tap from an all-zero block -- taken out of the certificate.  It left 62 of
 // 16320 tiles uncertain at 16 x 4K Q10 instead of 12449, but its bookkeeping
 // made the kernel slower than k_inv2 there: 425 vs 358 us; DESIGN.md.)
-template <int MODE, int XTRA>
+template <int MODE, int XTRA, bool AP>
 __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const Geo& g, const int tiles_x,
                                               const int frame, const int tile, const int16_t* __restrict__ coeffs,
                                               const FrameQ* __restrict__ fq, const uint8_t* __restrict__ rgb_in,
@@ -377,7 +410,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
       s_qs[qs_index(tid >> 3, tid & 7)] = q * c_aan[tid >> 3] * c_aan[tid & 7] * 0.125;
       // max Q from the host's FrameQ::qmax (a scalar load at the end): no
       // cross-lane reduction before the barrier
-      if (tid == 0) {
+      if (!AP && tid == 0) {
         s_cert[0] = 0xffffffffu;
         s_cert[1] = 0u;
         s_cert[2] = 0u;
@@ -398,7 +431,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   // row of its ring blocks)
   auto chroma_task = [&](const int p, const int by, const int bx, const Col16& cur) {
     const bool need = rows.need(by, lv);
-    fast_col(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
+    fast_col<AP>(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
     if (need) {
       double c[8];
       fast_row<-128>(s_mid + lb * MS, lv, c);
@@ -445,7 +478,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     long long off = tinfo(lb, pp, ii, by, bx, ok);
     Col16 cq = load_col(cf + (pp ? g.off_cr : g.off_cb), off, lv, ok);
     table_setup();
-    if (tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
+    if (!AP && tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
 #pragma unroll 1
     for (int tt = lb; tt < NTASK; tt += I::RB) {  // (uniform per wave: RB lane groups, 8 per wave)
       const Col16 cur = cq;
@@ -465,7 +498,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     const long long cboff = ((long long)cby * g.ncx + cbx) * 64;
     Col16 cq = load_col(cf + g.off_cb, cboff, lv, cvalid);
     table_setup();
-    if (tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
+    if (!AP && tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
     if (ctask) {
 #pragma unroll 1
       for (int p = 0; p < 2; ++p) {
@@ -497,7 +530,7 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
       const bool ok1 = luma_blk(r + 1, by1, bx1);
       lq = load_col(cf, ((long long)by1 * g.nbx + bx1) * 64, lv, ok1);
     }
-    if (bvalid) fast_col(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
+    if (bvalid) fast_col<AP>(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
     const int y = by * 8 + lv, x0 = bx * 8;
     if (bvalid && y < g.H && x0 < g.W) {
       double Yv[8];
@@ -540,24 +573,24 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
         chroma8_fast<MODE>(s_cw[0], x0, cwx0, wq, wt, C);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          Yv[k] = Yv[k] + (MAGIC + 128.0);  // Y on byte_cert_y's grid, shared by the three channels
+          Yv[k] = Yv[k] + Y_OFF<AP>;  // Y on byte_cert_y's grid, shared by the three channels
           const double B = col_b<MadDev, USH_>(Yv[k], C[k]);
           Gt[k] = col_gt<MadDev, USH_>(Yv[k], C[k]);
-          cb[3 * k + 2] = cert_hi(B, r_min, r_max);
+          cb[3 * k + 2] = cert_hi<AP>(B, r_min, r_max);
         }
         chroma8_fast<MODE>(s_cw[1], x0, cwx0, wq, wt, C);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const double R = col_r<MadDev, USH_>(Yv[k], C[k]);
           const double G = col_g<MadDev, USH_>(Gt[k], C[k]);
-          cb[3 * k] = cert_hi(R, r_min, r_max);
-          cb[3 * k + 1] = cert_hi(G, r_min, r_max);
+          cb[3 * k] = cert_hi<AP>(R, r_min, r_max);
+          cb[3 * k + 1] = cert_hi<AP>(G, r_min, r_max);
         }
 #pragma unroll
         for (int w = 0; w < 6; ++w) pk[w] = pack4s(cb[4 * w], cb[4 * w + 1], cb[4 * w + 2], cb[4 * w + 3]);
       }
       lo_min = lo_min < r_min ? lo_min : r_min;
-      lo_max = lo_max > r_max ? lo_max : r_max;
+      if constexpr (!AP) lo_max = lo_max > r_max ? lo_max : r_max;
       if (wide) {
         uint2* o2 = reinterpret_cast<uint2*>(o);
         o2[0] = make_uint2(pk[0], pk[1]);
@@ -592,8 +625,15 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   }
 
   // ---- 3. certification: the tile's closest approach to an integer vs its bound
-  int qm = max(qhi, -qlo);  // max |q| this lane read
-  cert_to_lds(lo_min, lo_max, (uint32_t)qm, s_cert);
+  if constexpr (AP) {
+    // a constant threshold: each lane judges its own smallest shifted fraction
+    // word (a lane without outputs keeps 2^32 - 1), and a wave with an
+    // uncertain lane flags the tile (sh.redo is 0 on entry)
+    if (__ballot(lo_min < 2u * AP_S || fix_all) != 0ull && (tid & 63) == 0) sh.redo = 1;
+  } else {
+    int qm = max(qhi, -qlo);  // max |q| this lane read
+    cert_to_lds(lo_min, lo_max, (uint32_t)qm, s_cert);
+  }
   if constexpr (XTRA > 0) {
     unsigned long long s = sse;
 #pragma unroll
@@ -606,14 +646,16 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   }
   __syncthreads();
   if (tid == 0) {
-    const uint32_t mn = s_cert[0], mx = s_cert[1];
-    const double q = (double)s_cert[2];
-    // |v_fast - v_ref| <= E, plus <= 3 roundings on the magic grid (2^-33 each:
-    // byte_cert); T in units of 2^-32
-    const double E = K_LIN * (q * s_qmax) + K_CONST + 0x1p-31;
-    const double T = ceil(E * 0x1p+32) + 1.0;
-    const bool uncertain = (double)mn <= T || (double)mx >= 0x1p+32 - 1.0 - T;
-    sh.redo = uncertain || fix_all;
+    if constexpr (!AP) {
+      const uint32_t mn = s_cert[0], mx = s_cert[1];
+      const double q = (double)s_cert[2];
+      // |v_fast - v_ref| <= E, plus <= 3 roundings on the magic grid (2^-33 each:
+      // byte_cert); T in units of 2^-32
+      const double E = K_LIN * (q * s_qmax) + K_CONST + 0x1p-31;
+      const double T = ceil(E * 0x1p+32) + 1.0;
+      const bool uncertain = (double)mn <= T || (double)mx >= 0x1p+32 - 1.0 - T;
+      sh.redo = uncertain || fix_all;
+    }
     if (sh.redo) {
       atomicAdd(fixcount, 1u);  // tiles recomputed (jds_plan_fix_counts)
       atomicAdd(cnt_now + frame, 1u);
@@ -625,14 +667,17 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     }
     if (frame == 0 && tile == 0) *next_count = 0u;  // the next run counts from zero
   }
-  __syncthreads();  // sh.redo is visible to the caller's uniform branch
+  // sh.redo is visible to the caller's uniform branch (AP: the waves stored it
+  // before the barrier above)
+  if constexpr (!AP) __syncthreads();
   return sh.redo != 0;
 }
 
 // XTRA: 0 = RGB only; 1 = + exact integer SSE and luma SSE partials (sweeps),
 // committed by the fast pass only for certified tiles (the exact tile code
 // commits the others).
-template <int MODE, int XTRA>
+// AP: the a-priori certificate (full runs, InvFix::apriori).
+template <int MODE, int XTRA, bool AP>
 __global__ void __launch_bounds__(Inv<MODE>::NT) __attribute__((amdgpu_waves_per_eu(Inv<MODE>::WPE)))
 k_inv_fast(const Geo g, const int tiles_x, const int16_t* __restrict__ coeffs, const FrameQ* __restrict__ fq,
            const uint8_t* __restrict__ rgb_in, uint8_t* __restrict__ rgb_out, jds_frame_stats* __restrict__ st,
@@ -667,7 +712,7 @@ k_inv_fast(const Geo g, const int tiles_x, const int16_t* __restrict__ coeffs, c
     }
   } else {
     sh.redo = 0;
-    redo = inv_fast_tile<MODE, XTRA>(sh, g, tiles_x, frame, tile, coeffs, fq, rgb_in, rgb_out, st, sse_y_part,
+    redo = inv_fast_tile<MODE, XTRA, AP>(sh, g, tiles_x, frame, tile, coeffs, fq, rgb_in, rgb_out, st, sse_y_part,
                                          fixcount, next_count, cnt_now, in_div, fix_all);
   }
   // one call site of the exact tile code: items in exact mode, uncertain tiles
@@ -1030,8 +1075,11 @@ k_inv6_fix(const Geo g, const int tiles_x, const int16_t* __restrict__ coeffs, c
 // colour8_exact, jds_inv_exact.hpp) and overwrites their rows.  (k_inv_fast's
 // tiled 4:4:4 form measured slower than k_inv2: 383 vs 332 us per 256 x 512^2,
 // its per-tile fixed costs spread over 2048 pixels.)
+// AP: the a-priori certificate of full runs, as in k_inv_fast: no Dmax over
+// the block, each lane's smallest shifted fraction word against 2 AP_S.
 constexpr int I444_WAVES = 4;
 
+template <bool AP>
 __global__ void __launch_bounds__(64 * I444_WAVES)
 k_inv_fast444(const Geo g, const int16_t* __restrict__ coeffs, const FrameQ* __restrict__ fq,
               uint8_t* __restrict__ rgb_out, jds_frame_stats* __restrict__ st, unsigned* __restrict__ fixcount,
@@ -1067,7 +1115,6 @@ k_inv_fast444(const Geo g, const int16_t* __restrict__ coeffs, const FrameQ* __r
     s_qi[tid] = (int)q;
   }
   __syncthreads();
-  const double qmax = fq[frame].qmax;
   const int y = by * 8 + lv, x0 = bx * 8;
   const bool row_ok = bvalid && y < g.H;
   const int nx = g.W - x0 < 8 ? g.W - x0 : 8;
@@ -1094,40 +1141,46 @@ k_inv_fast444(const Geo g, const int16_t* __restrict__ coeffs, const FrameQ* __r
     // chroma planes first, luma last, then the colour terms pixel by pixel
     // (bytes packed as they come: fewer live registers than plane by plane)
     double Cb[8], Cr[8], Yv[8];
-    fast_col(qb, s_qs, lv, slot, qhi, qlo);
+    fast_col<AP>(qb, s_qs, lv, slot, qhi, qlo);
     __builtin_amdgcn_wave_barrier();
     fast_row<-128>(slot, lv, Cb);  // Cb - 128
     __builtin_amdgcn_wave_barrier();
-    fast_col(qr, s_qs, lv, slot, qhi, qlo);
+    fast_col<AP>(qr, s_qs, lv, slot, qhi, qlo);
     __builtin_amdgcn_wave_barrier();
     fast_row<-128>(slot, lv, Cr);  // Cr - 128
     __builtin_amdgcn_wave_barrier();
-    fast_col(qy, s_qs, lv, slot, qhi, qlo);
+    fast_col<AP>(qy, s_qs, lv, slot, qhi, qlo);
     __builtin_amdgcn_wave_barrier();
     fast_row<-128>(slot, lv, Yv);  // Y - 128
     uint32_t cb[24];  // channel high words (byte: clamp(low 16 bits)), output order R0 G0 B0 R1 ...
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const double y = Yv[k] + (MAGIC + 128.0);
-      cb[3 * k] = cert_hi(col_r(y, Cr[k]), lo_min, lo_max);
-      cb[3 * k + 1] = cert_hi(col_g(col_gt(y, Cb[k]), Cr[k]), lo_min, lo_max);
-      cb[3 * k + 2] = cert_hi(col_b(y, Cb[k]), lo_min, lo_max);
+      const double y = Yv[k] + Y_OFF<AP>;
+      cb[3 * k] = cert_hi<AP>(col_r(y, Cr[k]), lo_min, lo_max);
+      cb[3 * k + 1] = cert_hi<AP>(col_g(col_gt(y, Cb[k]), Cr[k]), lo_min, lo_max);
+      cb[3 * k + 2] = cert_hi<AP>(col_b(y, Cb[k]), lo_min, lo_max);
     }
     uint32_t pk[6];
 #pragma unroll
     for (int w = 0; w < 6; ++w) pk[w] = pack4s(cb[4 * w], cb[4 * w + 1], cb[4 * w + 2], cb[4 * w + 3]);
     store(pk);
   }
-  // the block's Dmax over its three planes (its 8 lanes), then this lane's margin
-  int qm = max(qhi, -qlo);
-  // over the block's 8 lanes by DPP: quad_perm xor 1, xor 2, then row_half_mirror
-  // (lane i of 8 with lane 7 - i, in the other quad)
-  qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0xb1, 0xf, 0xf, true));
-  qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0x4e, 0xf, 0xf, true));
-  qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0x141, 0xf, 0xf, true));
-  const double E = K_LIN * ((double)qm * qmax) + K_CONST + 0x1p-31;
-  const double T = ceil(E * 0x1p+32) + 1.0;
-  const bool unc = row_ok && ((double)lo_min <= T || (double)lo_max >= 0x1p+32 - 1.0 - T);
+  bool unc;
+  if constexpr (AP) {
+    unc = row_ok && lo_min < 2u * AP_S;
+  } else {
+    // the block's Dmax over its three planes (its 8 lanes), then this lane's margin
+    int qm = max(qhi, -qlo);
+    // over the block's 8 lanes by DPP: quad_perm xor 1, xor 2, then row_half_mirror
+    // (lane i of 8 with lane 7 - i, in the other quad)
+    qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0xb1, 0xf, 0xf, true));
+    qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0x4e, 0xf, 0xf, true));
+    qm = max(qm, __builtin_amdgcn_update_dpp(0, qm, 0x141, 0xf, 0xf, true));
+    const double qmax = fq[frame].qmax;
+    const double E = K_LIN * ((double)qm * qmax) + K_CONST + 0x1p-31;
+    const double T = ceil(E * 0x1p+32) + 1.0;
+    unc = row_ok && ((double)lo_min <= T || (double)lo_max >= 0x1p+32 - 1.0 - T);
+  }
 #ifndef JDS_PROBE_NOFALLBACK
   if (__ballot(unc || fix_all) == 0ull) return;  // (uniform) the wave's rows are certified
 
@@ -1527,18 +1580,18 @@ static hipError_t inv_fast_t(const Geo& g, int n, const int16_t* coeffs, const F
     return hipGetLastError();
   }
 #endif
-  if (rgb_in != nullptr) {
-    // SSE runs (sweeps): the exact integer SSE and the luma SSE partials, per
-    // certified tile by the fast pass, per uncertain tile by the exact tile code
-    hipLaunchKernelGGL((k_inv_fast<MODE, 1>), grid, blk, 0, s, g, tx, coeffs, fq, rgb_in, rgb_out, st, part, cnt,
-                       nxt, fx.item, fx.rot, fx.probe, in_div, fx.fix_all, -1);
-    kmark(s, "k_inv_fast<%d,1>", MODE);
+  // fx.apriori (full runs) selects the a-priori certificate's instantiation
+  auto go = [&](auto kern, const uint8_t* rin, int xtra, int f) {
+    hipLaunchKernelGGL(kern, grid, blk, 0, s, g, tx, coeffs, fq, rin, rgb_out, st, part, cnt, nxt, fx.item, fx.rot,
+                       fx.probe, in_div, fx.fix_all, f);
+    kmark(s, "k_inv_fast<%d,%d>", MODE, xtra);
     return hipGetLastError();
-  }
-  hipLaunchKernelGGL((k_inv_fast<MODE, 0>), grid, blk, 0, s, g, tx, coeffs, fq, nullptr, rgb_out, st, part, cnt, nxt,
-                     fx.item, fx.rot, fx.probe, in_div, fx.fix_all, fin);
-  kmark(s, "k_inv_fast<%d,0>", MODE);
-  return hipGetLastError();
+  };
+  // SSE runs (sweeps): the exact integer SSE and the luma SSE partials, per
+  // certified tile by the fast pass, per uncertain tile by the exact tile code
+  if (rgb_in != nullptr)
+    return fx.apriori ? go(k_inv_fast<MODE, 1, true>, rgb_in, 1, -1) : go(k_inv_fast<MODE, 1, false>, rgb_in, 1, -1);
+  return fx.apriori ? go(k_inv_fast<MODE, 0, true>, nullptr, 0, fin) : go(k_inv_fast<MODE, 0, false>, nullptr, 0, fin);
 }
 
 hipError_t launch_inv_fast(int mode, const Geo& g, int n, const int16_t* coeffs, const FrameQ* fq,
@@ -1554,8 +1607,12 @@ hipError_t launch_inv_fast(int mode, const Geo& g, int n, const int16_t* coeffs,
       (void)in_div;
       const long long nblk = (long long)g.nby * g.nbx;
       const dim3 grid((unsigned)((nblk + 8 * I444_WAVES - 1) / (8 * I444_WAVES)), n), blk(64 * I444_WAVES);
-      hipLaunchKernelGGL(k_inv_fast444, grid, blk, 0, s, g, coeffs, fq, rgb_out, st, fx.count + fx.parity,
-                         fx.count + (fx.parity ^ 1), fx.item, fx.rot, fx.fix_all, fin);
+      if (fx.apriori)
+        hipLaunchKernelGGL(k_inv_fast444<true>, grid, blk, 0, s, g, coeffs, fq, rgb_out, st, fx.count + fx.parity,
+                           fx.count + (fx.parity ^ 1), fx.item, fx.rot, fx.fix_all, fin);
+      else
+        hipLaunchKernelGGL(k_inv_fast444<false>, grid, blk, 0, s, g, coeffs, fq, rgb_out, st, fx.count + fx.parity,
+                           fx.count + (fx.parity ^ 1), fx.item, fx.rot, fx.fix_all, fin);
       kmark(s, "k_inv_fast444");
       return hipGetLastError();
     }
@@ -1574,7 +1631,10 @@ hipError_t launch_inv_fast(int mode, const Geo& g, int n, const int16_t* coeffs,
 // multiply-add rounded twice (MadDev on x86-64); 1: every one fused (MadFma).
 // values[] = v' = y - MAGIC (exact), the value the certificate judges.
 // Q: the 8x8 table (16x16: Q16[u][v] = Q[u/2][v/2]).
-template <class M, int BS>
+// AP (8x8): the a-priori certificate's offset form, Y_OFF<true> in the luma
+// constant; values[] then carry the offset too (v' + AP_S * 2^-32: uncertain
+// when their fraction is below 2 AP_S * 2^-32).
+template <class M, int BS, bool AP = false>
 static void inv_fast_host_t(int mode, const int16_t* cf, const double* Q, int H, int W, double* vout,
                             uint8_t* bout) {
   const int sy = mode == M420 ? 2 : 1, sx = mode == M444 ? 1 : 2;
@@ -1644,7 +1704,7 @@ static void inv_fast_host_t(int mode, const int16_t* cf, const double* Q, int H,
         const int m = x >> 1;
         C[p] = (x & 1) == 0 ? fhsum<M>(vb(m - 1), vb(m)) : fhsum<M>(vb(m + 1), vb(m));
       }
-      const double Yv = S(0, y, x) + (MAGIC + 128.0);
+      const double Yv = S(0, y, x) + Y_OFF<AP>;
       double B, Gt, R, G;
       if (sx == 1) {
         B = col_b<M>(Yv, C[1]), Gt = col_gt<M>(Yv, C[1]);
@@ -1669,10 +1729,19 @@ static void inv_fast_host_t(int mode, const int16_t* cf, const double* Q, int H,
     }
 }
 
+// fuse: bit 0 = fused multiply-adds, bit 1 = the offset form (8x8 only)
 int inv_fast_host(int mode, const int16_t* cf, const double* Q, int H, int W, int fuse, int block, double* vout,
                   uint8_t* bout) {
   const int sy = mode == M420 ? 2 : 1, sx = mode == M444 ? 1 : 2;
   if (H % sy || W % sx || (block != 8 && block != 16)) return -1;  // the tiled kernels' even geometries
+  if (fuse & 2) {
+    if (block != 8) return -1;
+    if (fuse & 1)
+      inv_fast_host_t<MadFma, 8, true>(mode, cf, Q, H, W, vout, bout);
+    else
+      inv_fast_host_t<MadDev, 8, true>(mode, cf, Q, H, W, vout, bout);
+    return 0;
+  }
   if (block == 16) {
     if (fuse)
       inv_fast_host_t<MadFma, 16>(mode, cf, Q, H, W, vout, bout);
@@ -1684,6 +1753,35 @@ int inv_fast_host(int mode, const int16_t* cf, const double* Q, int H, int W, in
     inv_fast_host_t<MadDev, 8>(mode, cf, Q, H, W, vout, bout);
   }
   return 0;
+}
+
+// The two forms of the certificate's test on given values v (|v| < 2^19), at
+// the a-priori threshold: [0] two-sided on y = v + MAGIC (uncertain when its
+// fraction word lo <= AP_T or lo >= 2^32 - 1 - AP_T), [1] one-sided on
+// y = v + (MAGIC + AP_S * 2^-32) (uncertain when lo'' < 2 AP_S); the byte of
+// each is clamp(high word - MAGIC_HI, 0, 255).  bytes / certain: 2 per value.
+// consts[5] = K_LIN, K_CONST, AP_DMAX, AP_T, AP_S.
+void inv_cert_forms_host(const double* v, long long n, uint8_t* bytes, uint8_t* certain, double* consts) {
+  auto words = [](double y, uint32_t& lo) {
+    uint64_t bits;
+    memcpy(&bits, &y, 8);
+    lo = (uint32_t)bits;
+    const uint32_t hi = (uint32_t)(bits >> 32);
+    const uint32_t c = hi < MAGIC_HI ? MAGIC_HI : (hi > MAGIC_HI + 255u ? MAGIC_HI + 255u : hi);
+    return (uint8_t)(c & 255u);
+  };
+  for (long long i = 0; i < n; ++i) {
+    uint32_t lo;
+    bytes[2 * i] = words(v[i] + MAGIC, lo);
+    certain[2 * i] = !(lo <= AP_T || lo >= 0xffffffffu - AP_T);
+    bytes[2 * i + 1] = words(v[i] + (Y_OFF<true> - 128.0), lo);
+    certain[2 * i + 1] = !(lo < 2u * AP_S);
+  }
+  consts[0] = K_LIN;
+  consts[1] = K_CONST;
+  consts[2] = AP_DMAX;
+  consts[3] = (double)AP_T;
+  consts[4] = (double)AP_S;
 }
 
 }  // namespace jds

@@ -332,6 +332,7 @@ _SIGS = {
     'jds_selftest_inv_rows': (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     'jds_selftest_inv_fast': (C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
     'jds_selftest_inv_fast16': (C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    'jds_selftest_inv_cert': (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     'jds_selftest_fwd32': (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                      _P]),
     'jds_selftest_fwd16': (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,

@@ -53,7 +53,10 @@ exact), NumPy's colour expressions (cr - 128, product, sum; g left to right).
 Output: (e_lin, e_const) for both chains and K_LIN / K_CONST = 2 * (sums): the
 factor 2 is a safety margin.  tests/test_inv_bound_cpu.py asserts the kernel's
 constants are at least these and checks the chain itself against the oracle
-(jds_selftest_inv_fast).
+(jds_selftest_inv_fast).  Beside them it prints what full runs certify with:
+at the codec's own |q Q| <= 1152 the threshold is a constant, T = ceil(E *
+2^32) + 1 steps of the 2^-32 grid, and S = T + 1 is the offset of the
+one-sided test (the kernel's AP_T / AP_S; tests/test_inv_apriori_cpu.py).
 """
 import math
 import os
@@ -124,6 +127,18 @@ def kernel_constants():
     return {'aan': aan, 'F_SQ2': c['F_SQ2'], 'F_A2C2': c['F_A2C2'], 'F_K10': c['F_K10'], 'F_K12': c['F_K12'],
             'MAGIC': c.get('MAGIC'), 'K_LIN': float(klin.group(1)) * float(klin.group(2)),
             'K_CONST': float(kcon.group(1)) * float(kcon.group(2)), 'colour': colour}
+
+
+AP_DMAX = 1152  # |q Q| of the codec's own forward output: |c| <= 8 * 128, Q <= 255, |q Q| <= |c| + Q / 2
+
+
+def apriori_steps(k_lin, k_const, dmax=AP_DMAX):
+    """(T, S) of the a-priori certificate (jds_inv_fast.hip AP_T / AP_S): the
+    threshold T = ceil(E * 2^32) + 1 in steps of the 2^-32 grid at
+    E = k_lin * dmax + k_const + 2^-31, and the offset S = T + 1 that makes the
+    test one-sided ((lo + S) mod 2^32 < 2 S)."""
+    T = math.ceil((k_lin * dmax + k_const + KERNEL_GRID_SLACK) * 2.0 ** 32) + 1
+    return T, T + 1
 
 
 def pocketfft_constants():
@@ -537,3 +552,8 @@ elif __name__ == '__main__':
           f'<= kernel slack {KERNEL_GRID_SLACK:.3e}')
     print(f'E at Dmax = 1152 (codec output): {k_lin * 1152 + k_const + KERNEL_GRID_SLACK:.3e};  '
           f'at 255*32767: {k_lin * 255 * 32767 + k_const + KERNEL_GRID_SLACK:.3e}')
+    # the a-priori certificate of full runs (jds_inv_fast.hip, AP_T / AP_S): the
+    # kernel's constants at Dmax = 1152, in steps of the 2^-32 grid
+    T, S = apriori_steps(K['K_LIN'], K['K_CONST'])
+    print(f'a-priori certificate (kernel K_LIN / K_CONST, Dmax = {AP_DMAX}): T = ceil(E * 2^32) + 1 = {T} grid steps, '
+          f'offset S = T + 1 = {S}; a value is uncertain when (lo + S) mod 2^32 < 2 S = {2 * S}')
