@@ -48,9 +48,14 @@ extern "C" {
                                  inverse + tile fix-up (same bytes; A/B and tests) */
 #define JDS_RUN_INV_FIXALL 32u /* test: the certified fast inverse flags every tile, so the exact
                                   tile code recomputes the whole frame (exercises the fix-up path) */
-#define JDS_RUN_INV_FAST 128u /* A/B and tests, coarse tables (DC quantiser > 60): the certified fast
-                                inverse instead of the exact k_inv2 such plans run (most tiles of
-                                those frames fall back) */
+#define JDS_RUN_INV_FAST 128u /* A/B and tests, plans whose tables are all coarse (DC quantiser > 60): the
+                                certified fast inverse instead of the exact k_inv2 such plans run (most
+                                tiles of those frames fall back).  The 4:2:x kernel
+                                then works as on any plan: an item whose previous fast run recomputed more
+                                than 1/8 of its tiles runs the exact tile code directly (per-item exact
+                                mode) until the next probe run, every 16th fast inverse of the plan.
+                                Plans with some coarse and some finer tables take the fast inverse
+                                without this flag, their coarse items in exact mode from the first run */
 #define JDS_RUN_FWD_FIXALL 64u /* test, 16x16 plans: the certified fp32 forward lists every block, so
                                   k_fix_fwd16 recomputes the whole frame (exercises the fix-up path) */
 
@@ -156,7 +161,19 @@ int jds_plan_geometry(const jds_plan* plan, jds_geometry* out);
    [1] inverse tiles the certified fast inverse handed to the exact kernel (k_inv2_list).  A run of
    both phases in one call certifies against the fixed bound |q Q| <= 1152, an inverse-only run
    (JDS_RUN_INV) against the bound it tracks over the tile (max |q| times max Q: larger on most tables, smaller
-   where the coefficients are small): [1] of the two can differ, the bytes cannot. */
+   where the coefficients are small): [1] of the two can differ, the bytes cannot.
+   [1] depends on the plan's earlier runs, the bytes never do.  On the 8x8 4:2:0 / 4:2:2 kernel an
+   item whose previous fast inverse recomputed more than 1/8 of its tiles (count * 8 > tiles) runs the
+   exact tile code directly: it contributes all of its tiles to [1], whatever this run's content, and
+   carries its count forward.  Only a probe run (the 16th, 32nd, ... fast inverse of the plan) and a
+   JDS_RUN_INV_FIXALL run measure such an item again; it leaves exact mode when the fresh count is at
+   most 1/8 of its tiles.  Coarse items (DC quantiser > 60) of a plan that also has finer tables start
+   in exact mode, so they add all their tiles to [1] on every run but the probes.  The 4:4:4 kernel
+   (units: waves of 8 blocks) and the 16x16 kernel have no exact mode.  Runs whose inverse is an exact
+   kernel (JDS_RUN_EXACT, JDS_RUN_EXACT_INV, JDS_RUN_SSE at 4:4:4 or 16x16, all-coarse 4:2:x plans without
+   JDS_RUN_INV_FAST) report [1] = 0 and count neither towards the probe rhythm nor as a previous run;
+   a forward-only run leaves [1] as the last inverse left it.  [0] is that of the last certified
+   forward (16x16: 0 after a JDS_RUN_EXACT forward). */
 int jds_plan_fix_counts(const jds_plan* plan, uint32_t* counts);
 void jds_plan_destroy(jds_plan* plan);
 

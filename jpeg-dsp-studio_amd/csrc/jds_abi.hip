@@ -743,7 +743,11 @@ int jds_plan_run(jds_plan* p, const uint8_t* rgb, uint8_t* rgb_out, int16_t* coe
                          nullptr, nullptr, 0, s, nullptr, exact ? 6 : (phases == 3 ? 2 | 8 : 2), p->nq, nullptr,
                          exact_inv || !p->invfix.p ? nullptr : &fx));
   if (phases & 2) {
-    p->last_inv_fast = !exact_inv && p->invfix.p;
+    // 4:4:4 SSE runs take the exact kernel (launch_codec): no fast inverse ran, so
+    // the counters' cycles must not advance (the next fast run would count into a
+    // counter nobody zeroed)
+    const bool sse444 = (flags & JDS_RUN_SSE) && p->mode == JDS_SS_444;
+    p->last_inv_fast = !exact_inv && p->invfix.p && !sse444;
     if (p->last_inv_fast) p->inv_runs++;
   }
   return JDS_OK;
