@@ -79,7 +79,17 @@ typedef struct {
   int32_t subsampling; /* JDS_SS_* */
   int32_t prefilter;   /* 0/1; ignored for 4:4:4 (engines/color_space.py:34-35) */
   double qtable[64];   /* scale_quant_matrix(JPEG_LUMA_Q50, quality) (engines/quantizer.py:7-19) */
-  double gauss[3];     /* cv2.getGaussianKernel(3, 0.75) taps (engines/color_space.py:39-40) */
+  /* The prefilter's taps: cv2.getGaussianKernel(3, 0.75) in the reference
+   * (engines/color_space.py:39-40).  Read only where the prefilter runs
+   * (prefilter != 0 and not 4:4:4); there they must be finite with gauss[0] ==
+   * gauss[2] (JDS_EINVAL otherwise, from every entry point that takes them):
+   * the column pass is cv2's symmetric form k1 T[y] + k0 (T[y+1] + T[y-1]),
+   * which has no definition for asymmetric taps.  Signs and sum are free; a
+   * full run keeps its fixed |q Q| <= 1152 certificate (jds_plan_fix_counts)
+   * only for non-negative taps whose sum is at most 1 and tracks the bound
+   * otherwise, and taps whose sum is not 1 send every chroma block through
+   * the forward's exact fix-up.  Same bytes either way. */
+  double gauss[3];
 } jds_params;
 
 /* Per-frame statistics, all exact integers; sse_y is an exact integer sum

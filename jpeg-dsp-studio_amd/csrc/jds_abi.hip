@@ -225,6 +225,7 @@ static int make_geo(const jds_params* p, int64_t H, int64_t W, Geo* g, int* mode
   const int B = p->block_size;
   if (p->subsampling < JDS_SS_444 || p->subsampling > JDS_SS_420)
     return fail(JDS_EINVAL, "Unknown subsampling mode: %d", p->subsampling);
+  if (int rc = check_taps(p->gauss, p->subsampling, p->prefilter)) return rc;
   if (H < 1 || W < 1 || H > 65536 || W > 65536 || H * W > (int64_t)1 << 28)
     return fail(JDS_EINVAL, "unsupported image size %lldx%lld", (long long)H, (long long)W);
   const int mode = p->subsampling;
@@ -1181,6 +1182,7 @@ int jds_stage_subsample(jds_ctx* c, const double* cb, const double* cr, int64_t 
                         int32_t prefilter, const double* gauss, double* cb_out, double* cr_out) {
   if (!c || !cb || !cr || !cb_out || !cr_out || !gauss || H < 1 || W < 1) return fail(JDS_EINVAL, "bad argument");
   if (mode != JDS_SS_422 && mode != JDS_SS_420) return fail(JDS_EINVAL, "Unknown subsampling mode: %d", mode);
+  if (int trc = check_taps(gauss, mode, prefilter)) return trc;
   const int sy = mode == JDS_SS_420 ? 2 : 1;
   const int oh = (int)(H / sy), ow = (int)(W / 2);
   if (oh < 1 || ow < 1)

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <thread>
 #include <vector>
 
@@ -260,6 +261,22 @@ static int check_tables(const jds_params* p) {
     if (p->qtable[i] != floor(p->qtable[i]))
       return fail(JDS_EINVAL, "qtable[%d] = %g is not an integer", i, p->qtable[i]);
   }
+  return JDS_OK;
+}
+
+// The prefilter's column pass is cv2's SymmColumnFilter, k1 T[y] + k0 (T[y+1] +
+// T[y-1]) (engines/color_space.py:39-40 through sepFilter2D): defined for
+// symmetric taps only, which is all cv2 hands it.  The exact kernels restate
+// that form, the certified kernels weigh rows by k0, k0+k1, k1+k2, k2; the two
+// agree only when gauss[0] == gauss[2].  Taps are read only where the
+// prefilter runs (prefilter != 0 and not 4:4:4).
+static int check_taps(const double* gauss, int subsampling, int prefilter) {
+  if (!prefilter || subsampling == JDS_SS_444) return JDS_OK;
+  if (!std::isfinite(gauss[0]) || !std::isfinite(gauss[1]) || !std::isfinite(gauss[2]) || gauss[0] != gauss[2])
+    return fail(JDS_EINVAL,
+                "prefilter taps [%.17g, %.17g, %.17g] must be finite and symmetric (gauss[0] == gauss[2]): the column "
+                "pass is cv2's symmetric filter",
+                gauss[0], gauss[1], gauss[2]);
   return JDS_OK;
 }
 

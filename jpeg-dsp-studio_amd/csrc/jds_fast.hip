@@ -1642,7 +1642,8 @@ hipError_t launch_fast_fwd(int mode, bool pf, const Geo& g, int n, int nq, const
 //
 // Rigorous bound on |c_fp32 - c_exact| per coefficient for k_fwd32.  Unit
 // roundoff u = 2^-24; each fp32 op rounds once: |fl(a op b) - (a op b)| <= u|result|.
-// Input samples: |x| <= X = 128, |x_fp32 - x_exact| <= e_in (colour / prefilter /
+// Input samples: |x| <= X (fwd_sample_bound: 128, more where the prefilter's
+// taps can exceed it), |x_fp32 - x_exact| <= e_in (colour / prefilter /
 // area stage bound below).  One fdct8_f32 pass over inputs (bound X, error e):
 //   s_i, d_i:  |.| <= 2X,   error <= 2e + 2uX
 //   output k:  |.| <= 2X b_k, error <= b_k (2e + 2uX) + 2uX (b_k + P_k)
@@ -1696,6 +1697,28 @@ static double combined_chain_error(const double* gk, double X, double e) {
   return sh * e + dh * X + u * X * P + 1e-12;
 }
 
+// The taps' absolute sum A = |k0| + |k1| + |k2| as the bounds use it: every
+// magnitude of a filtered sample scales with A per pass.  For non-negative taps
+// that sum to at most 1 (to rounding: S = 1 + 2^-52 is a Gaussian's own sum) it is
+// taken as exactly 1, so the samples stay within the unfiltered planes' 128 and
+// the excess, below 2^-40 relative, lies inside fast_fwd_bounds' second-order slack.
+static double taps_abs_sum(const double* gk) {
+  const double A = (fabs(gk[0]) + fabs(gk[1])) + fabs(gk[2]);
+  return A <= 1.0 + 0x1p-40 ? 1.0 : A;
+}
+
+// Bound on the magnitude of a level-shifted sample as the DCT passes receive
+// it: 128 for luma and unfiltered chroma; a prefiltered chroma sample is a
+// weighted sum of level-shifted pixels (|x - 128| <= 128) whose absolute
+// weights sum to at most A per pass (row: the combined taps k0, k0+k1, k1+k2,
+// k2 over 2, at most A; column: the same at 4:2:0, |k1| + 2 |k0| = A at 4:2:2;
+// check_taps: k0 == k2).
+double fwd_sample_bound(int plane, int mode, bool pf, const double* gk) {
+  if (plane == 0 || mode == M444 || !pf) return 128.0;
+  const double A = taps_abs_sum(gk);
+  return 128.0 * (A * A);
+}
+
 double fwd_input_error(int plane, int mode, bool pf, const double* gk, int chains) {
   const double u = 0x1p-24;
   // luma32: fmaf(kb, B, fmaf(kg, G, kr*R)); constants in fp32; then -128
@@ -1710,37 +1733,51 @@ double fwd_input_error(int plane, int mode, bool pf, const double* gk, int chain
   double e_comb = 0.0;  // k_fwd32i's combined-tap chain (prefiltered chroma)
   double e_sum = 0.0;   // the taps' sum against 1 (prefiltered chroma)
   if (mode != M444 && pf) {
-    const double k0 = gk[0], k1 = gk[1], k2 = gk[2];
-    const double k0f = (float)k0, k1f = (float)k1, k2f = (float)k2;
-    const double dk = fabs(k0f - k0) + fabs(k1f - k1) + fabs(k2f - k2);
+    // Signed taps: every term that sums magnitudes takes |k|, and every
+    // magnitude downstream of a pass scales with A (taps_abs_sum: 1 for
+    // non-negative taps of sum <= 1, where each expression below is the one
+    // the bound has always had, bit for bit).
+    const double k0 = fabs(gk[0]), k1 = fabs(gk[1]);
+    const double k0f = fabs((double)(float)gk[0]), k1f = fabs((double)(float)gk[1]),
+                 k2f = fabs((double)(float)gk[2]);
+    const double dk = fabs((double)(float)gk[0] - gk[0]) + fabs((double)(float)gk[1] - gk[1]) +
+                      fabs((double)(float)gk[2] - gk[2]);
+    const double A = taps_abs_sum(gk);
     // The reference filters the unshifted plane and subtracts 128 after; the
     // chains filter x - 128, so with exact taps they give sum(w x) - 128 sum(w)
     // where the reference has sum(w x) - 128.  sum(w) = S^2 for both layouts (S
-    // the sum of the Gaussian's fp64 taps, each of the two passes weighs by S;
+    // the signed sum of the fp64 taps, each of the two passes weighs by S: the
+    // symmetric column form's k1 + 2 k0 is S because k0 == k2 (check_taps);
     // the area mean's weights sum to 1 exactly), and S is 1 only to rounding
-    // (S formed here in fp64: 2 roundings, priced at 4 ulp of S^2).
-    const double S = (k0 + k1) + k2;
-    e_sum = 128 * (fabs(S * S - 1.0) + 0x1p-50);
-    // k_fwd32 (per pixel): row fmaf(k2, S1, fmaf(k1, S0, k0*S_1)); |S| <= 128, taps sum to 1
-    const double er = (k0f + k1f + k2f) * e + dk * 128 + u * 128 * (k0 + (k0 + k1) + 1.0) + 1e-12;
-    // column: fmaf(k0, T+1 + T-1, k1*T0)
-    e = (k1f + 2 * k0f) * er + dk * 256 + u * (256 + k1 * 128 + 128) + 1e-12;
+    // (S formed here in fp64: 2 roundings, priced at 4 ulp of max(S^2, 1)).
+    const double S = (gk[0] + gk[1]) + gk[2];
+    const double S2 = S * S <= 1.0 + 0x1p-40 ? 1.0 : S * S;
+    e_sum = 128 * (fabs(S * S - 1.0) + 0x1p-50 * S2);
+    // k_fwd32 (per pixel): row fmaf(k2, S1, fmaf(k1, S0, k0*S_1)); |S| <= 128,
+    // partial sums <= 128 (|k0|, |k0| + |k1|, A)
+    const double er = (k0f + k1f + k2f) * e + dk * 128 + u * 128 * (k0 + (k0 + k1) + A) + 1e-12;
+    // column: fmaf(k0, T+1 + T-1, k1*T0) over rows |T| <= 128 A
+    e = (k1f + 2 * k0f) * er + dk * (256 * A) + u * (256 * A + k1 * (128 * A) + 128 * (A * A)) + 1e-12;
     // k_fwd32i, k_fwd32 and k_fwd16f: horizontal pair sums H =
     // combined chain over 4 chroma samples
-    // (|H| <= 256), then 4:2:0: the combined chain down 4 rows of H (|.| <= 512)
+    // (|H| <= 256 A), then 4:2:0: the combined chain down 4 rows of H (|.| <= 512 A^2)
     // and *0.25 (exact); 4:2:2: the column form over H (magnitudes doubled) and
     // *0.5 (exact)
     const double eh = combined_chain_error(gk, 128, ec);
     if (mode == M420)
-      e_comb = combined_chain_error(gk, 256, eh) / 4;
+      e_comb = combined_chain_error(gk, 256 * A, eh) / 4;
     else
-      e_comb = ((k1f + 2 * k0f) * eh + dk * 512 + u * (512 + k1 * 256 + 256) + 1e-12) / 2;
+      e_comb = ((k1f + 2 * k0f) * eh + dk * (512 * A) + u * (512 * A + k1 * (256 * A) + 256 * (A * A)) + 1e-12) / 2;
+    // the area sums of the per-pixel chain: filtered pixels |.| <= 128 A^2
+    if (mode == M420) e = e + u * ((256 + 384 + 512) * (A * A)) / 4;  // ((a+b)+c)+d, *0.25 exact
+    if (mode == M422) e = e + u * (256 * (A * A)) / 2;                  // (a+b), *0.5 exact
+    // the bound covers the chains named (every certified forward kernel now
+    // uses the combined taps: callers pass 2)
+    e = (chains & 1) ? ((chains & 2) && e_comb > e ? e_comb : e) : e_comb;
+  } else {
+    if (mode == M420) e = e + u * (256 + 384 + 512) / 4;  // ((a+b)+c)+d, *0.25 exact
+    if (mode == M422) e = e + u * 256 / 2;                  // (a+b), *0.5 exact
   }
-  if (mode == M420) e = e + u * (256 + 384 + 512) / 4;  // ((a+b)+c)+d, *0.25 exact
-  if (mode == M422) e = e + u * 256 / 2;                  // (a+b), *0.5 exact
-  // the bound covers the chains named (every certified forward kernel now
-  // uses the combined taps: callers pass 2)
-  if (mode != M444 && pf) e = (chains & 1) ? ((chains & 2) && e_comb > e ? e_comb : e) : e_comb;
   return e + e_sum;  // (no trailing -128: the samples are level-shifted from the start)
 }
 
@@ -1756,7 +1793,7 @@ void fast_fwd_bounds(int mode, bool pf, const double* gk, double* E) {
   for (int p = 0; p < 2; ++p) {
     const double e_in = fwd_input_error(p, mode, pf, gk, 2);  // k_fwd32i and k_fwd32: combined taps
     double X1[8], e1[8];
-    pass_bound(128.0, e_in, nullptr, nullptr, X1, e1, W);
+    pass_bound(fwd_sample_bound(p, mode, pf, gk), e_in, nullptr, nullptr, X1, e1, W);
     double E2[8][8];  // [first-pass frequency][second-pass frequency]
     for (int k = 0; k < 8; ++k) {
       double X2[8], e2[8];

@@ -973,7 +973,7 @@ void fast_fwd16_bounds(int mode, bool pf, const double* gk, double* E /*2 x 256*
   for (int p = 0; p < 2; ++p) {
     const double e_in = fwd_input_error(p, mode, pf, gk, 2);  // both staging paths: combined taps
     double X1[16], e1[16];
-    pass_bound16(128.0, e_in, X1, e1);
+    pass_bound16(fwd_sample_bound(p, mode, pf, gk), e_in, X1, e1);
     double E2[16][16];
     for (int k = 0; k < 16; ++k) {
       double X2[16], e2[16];

@@ -131,5 +131,8 @@ void pass_bound(double X, double e, const double* Xin, const double* ein, double
 // chains (prefiltered chroma): bit 0 the per-pixel Gaussian then area chain,
 // bit 1 the combined taps; the bound covers every chain named
 double fwd_input_error(int plane, int mode, bool pf, const double* gk, int chains = 3);
+// |x| bound of those samples: 128, times the squared absolute sum of the taps
+// where a prefilter with negative taps or a sum above 1 can exceed it
+double fwd_sample_bound(int plane, int mode, bool pf, const double* gk);
 
 }  // namespace jds

@@ -28,6 +28,16 @@ def gaussian_kernel3(sigma: float = 0.75) -> np.ndarray:
     return np.array([e, mul1, e], dtype=np.float64)
 
 
+def _taps(gauss) -> np.ndarray:
+    """The prefilter's taps as jds_params.gauss takes them (None: the reference's)."""
+    if gauss is None:
+        return gaussian_kernel3(0.75)
+    g = np.ascontiguousarray(gauss, dtype=np.float64).reshape(-1)
+    if g.size != 3:
+        raise ValueError(f'the prefilter takes three taps, got {g.size}')
+    return g
+
+
 def _u8_image(image: np.ndarray) -> np.ndarray:
     a = np.asarray(image)
     if a.ndim != 3 or a.shape[2] != 3:
@@ -42,11 +52,13 @@ def _u8_image(image: np.ndarray) -> np.ndarray:
 
 def compress_reconstruct_raw(image: np.ndarray, quality: int, qtable: np.ndarray, mode: str, prefilter: bool,
                              block_size: int = 8, selected_block_idx: Tuple[int, int] = (0, 0),
-                             maps: bool = True, device: int = 0) -> Dict[str, object]:
-    """One jds_compress_reconstruct call (include/jds.h): returns the raw outputs."""
+                             maps: bool = True, device: int = 0, gauss=None) -> Dict[str, object]:
+    """One jds_compress_reconstruct call (include/jds.h): returns the raw outputs.
+    gauss: the prefilter's three taps (None: gaussian_kernel3(0.75), the reference's);
+    symmetric and finite wherever the prefilter runs."""
     img = _u8_image(image)
     H, W = img.shape[:2]
-    p = make_params(quality, qtable, mode, prefilter, gaussian_kernel3(0.75), block_size)
+    p = make_params(quality, qtable, mode, prefilter, _taps(gauss), block_size)
     geo = _abi.geometry(p, H, W)
     out = np.empty_like(img)
     coeffs = np.empty(geo.coeffs_per_frame, dtype=np.int16)
@@ -1177,13 +1189,13 @@ def stage_rgb_ycbcr(x: np.ndarray, inverse: bool) -> np.ndarray:
     return out
 
 
-def stage_subsample(cb: np.ndarray, cr: np.ndarray, mode: str, prefilter: bool):
+def stage_subsample(cb: np.ndarray, cr: np.ndarray, mode: str, prefilter: bool, gauss=None):
     cb, cr = _f64(cb), _f64(cr)
     H, W = cb.shape
     oh = H // 2 if mode == '4:2:0' else H
     ocb = np.empty((oh, W // 2), np.float64)
     ocr = np.empty((oh, W // 2), np.float64)
-    g = gaussian_kernel3(0.75)
+    g = _taps(gauss)
     with lease() as ctx:
         check(lib().jds_stage_subsample(ctx.handle, cb.ctypes.data, cr.ctypes.data, H, W,
                                         _abi.MODE_CODES[mode], 1 if prefilter else 0, g.ctypes.data,

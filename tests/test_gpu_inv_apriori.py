@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import cpu_ref
+from params_cases import _bound_inputs  # (shared with test_params_cpu.py, which imports no GPU module)
 from test_gpu_inv_fast import _plan, _same
 
 pytestmark = pytest.mark.gpu
@@ -51,40 +52,6 @@ def test_full_run_equals_exact_and_oracle(h, w, mode, q):
         assert np.array_equal(full[0][i], ref['reconstructed']), i
         assert [int(v) for v in full[2][i]['hist']] == [int(v) for v in ref['hist']]
         assert int(full[2][i]['nonzero']) == ref['bitrate']['nonzero_count']
-
-
-def _basis_sign(u, v, scale):
-    """255 where basis function (u, v) of the 8x8 DCT is positive, else 0, each
-    sample `scale` pixels wide (2: the pattern a subsampled chroma block sees)."""
-    n = np.arange(8)
-    cu = np.cos((2 * n + 1) * u * np.pi / 16)
-    cv = np.cos((2 * n + 1) * v * np.pi / 16)
-    p = (np.outer(cu, cv) > 0).astype(np.uint8) * 255
-    return np.kron(p, np.ones((scale, scale), np.uint8))
-
-
-def _bound_inputs(h, w):
-    """Frames that drive |c| to its largest: pure 0 / 255 channels, 8x8
-    checkerboards, basis sign patterns in luma (gray) and in Cb / Cr (blue
-    against yellow, red against cyan), uniform noise."""
-    out = []
-    for rgb in ((0, 0, 0), (255, 255, 255), (255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0)):
-        out.append(np.broadcast_to(np.array(rgb, np.uint8), (h, w, 3)).copy())
-    yy, xx = np.mgrid[0:h, 0:w]
-    for cell in (8, 16):
-        m = (((yy // cell) + (xx // cell)) % 2).astype(np.uint8) * 255
-        out.append(np.stack([m, m, m], axis=-1))
-        out.append(np.stack([255 - m, 255 - m, m], axis=-1))
-    for u, v in ((0, 0), (1, 1), (7, 7), (0, 7)):
-        for scale in (1, 2):
-            p = _basis_sign(u, v, scale)
-            p = np.tile(p, (-(-h // p.shape[0]), -(-w // p.shape[1])))[:h, :w]
-            out.append(np.stack([p, p, p], axis=-1))              # luma
-            out.append(np.stack([255 - p, 255 - p, p], axis=-1))  # Cb
-            out.append(np.stack([p, 255 - p, 255 - p], axis=-1))  # Cr
-    out.append(cpu_ref.random_image(h, w, 1400))
-    out.append((np.random.default_rng(1401).integers(0, 2, (h, w, 3)) * 255).astype(np.uint8))
-    return np.stack(out)
 
 
 @pytest.mark.parametrize('mode', ['4:2:0', '4:2:2', '4:4:4'])

@@ -26,20 +26,32 @@ def gpu():
     assert _abi.device_count() >= 1, 'no HIP device: the MI355X path has no CPU fallback'
 
 
-def _plan(frames, qs, mode, pf, flags_list, coeffs=None):
-    """Run one plan once per flags value on the same frames; optionally replace
-    the coefficients before an inverse-only run.  Returns [(out, cf, stats, fix)]."""
-    import torch
+def _params(item, mode, pf):
+    """jds_params of one plan item: a quality (the reference's luma table and
+    taps, 8x8 blocks) or (table, taps, block_size), taps None being the reference's."""
     from jds import _abi, codec
+    if isinstance(item, tuple):
+        table, taps, bs = item
+        return _abi.make_params(50, table, mode, pf, codec.gaussian_kernel3() if taps is None else taps, bs)
+    return _abi.make_params(item, cpu_ref.scale_quant_matrix(cpu_ref.JPEG_LUMA_Q50, item), mode, pf,
+                            codec.gaussian_kernel3())
+
+
+def _plan(frames, qs, mode, pf, flags_list, coeffs=None, nq=1):
+    """Run one plan once per flags value on the same frames; optionally replace
+    the coefficients before an inverse-only run.  qs: one quality or (table,
+    taps, block_size) per item; nq > 1: a sweep plan, len(qs) // nq frames.
+    Returns [(out, cf, stats, fix)]."""
+    import torch
+    from jds import _abi
     H, W = frames.shape[1:3]
-    params = [_abi.make_params(q, cpu_ref.scale_quant_matrix(cpu_ref.JPEG_LUMA_Q50, q), mode, pf,
-                               codec.gaussian_kernel3()) for q in qs]
-    plan = _abi.Plan(_abi.context(0), params, H, W)
+    assert len(frames) * nq == len(qs)
+    plan = _abi.Plan(_abi.context(0), [_params(q, mode, pf) for q in qs], H, W, nq)
     dev = torch.device('cuda:0')
     rgb = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
     res = []
     for flags in flags_list:
-        out = torch.zeros_like(rgb)
+        out = torch.zeros((len(qs), H, W, 3), dtype=torch.uint8, device=dev)
         cf = torch.empty((len(qs), plan.geometry.coeffs_per_frame), dtype=torch.int16, device=dev)
         st = torch.zeros((len(qs), _abi.STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize()
