@@ -84,6 +84,26 @@ __device__ __forceinline__ Col16 load_col(const int16_t* __restrict__ plane, lon
   return c;
 }
 
+// The fast kernels' column (k_inv_fast, k_inv_fast444): one coefficient per
+// VGPR, sign-extended by the load itself (global_load_sshort), so that
+// v_cvt_f64_i32 and the integer min / max of the tracked instantiations read
+// the loaded register directly: no v_bfe_i32 per coefficient.  The exact
+// kernels keep Col16 (their int16 form measured faster, above).
+// __builtin_annotation keeps the widening beside its load: the compiler's
+// late code sinking otherwise moves it into the block of the first use, and
+// the load is then selected zero-extending with an extract at every use
+// (the intrinsic itself is not sunk and lowers to no instruction).
+struct Col32 {
+  int q[8];
+};
+__device__ __forceinline__ Col32 load_col32(const int16_t* __restrict__ plane, long long boff, int v, bool ok) {
+  const int16_t* blk = plane + (ok ? boff : 0ll);
+  Col32 c;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) c.q[r] = __builtin_annotation((int)blk[r * 8 + v], "sext16");
+  return c;
+}
+
 #ifdef JDS_INV6  // k_inv_fast6's helpers (jds_inv_fast.hip, A/B builds only)
 // A column held two coefficients per VGPR (k_inv_fast6: the prefetched column
 // lives across a whole luma round, 4 VGPRs instead of 8): element r in the

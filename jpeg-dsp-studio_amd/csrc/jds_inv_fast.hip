@@ -44,6 +44,13 @@
 // in LDS, Y in registers, one lane per 8-pixel row, 24-byte stores.  4:2:0
 // tiles start 8 luma rows above 64 ty where that adds no tile row (InvRows,
 // Geo::inv_yoff): five chroma block rows per window instead of six.
+// The per-block paths carry no integer bookkeeping beside the fp64 work:
+// coefficient columns arrive sign-extended (Col32, global_load_sshort), each
+// prefetched column has registers of its own (the two planes, the 4:2:2
+// tasks and the luma rounds are written out, none copied), and a chroma
+// task's eight window stores go to one base at constant offsets (a ring
+// block's to a sink in its own transpose slot, its one column by a single
+// predicated store).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -197,7 +204,7 @@ constexpr int QS_STRIDE = 10;
 constexpr int QS_WORDS = 1 ? 8 * QS_STRIDE : 64;
 __device__ __forceinline__ int qs_index(int r, int v) { return 1 ? v * QS_STRIDE + r : r * 8 + v; }
 template <bool AP = false>
-__device__ __forceinline__ void fast_col(const Col16& in, const double* __restrict__ qs, int v,
+__device__ __forceinline__ void fast_col(const Col32& in, const double* __restrict__ qs, int v,
                                          double* __restrict__ dst, int& qhi, int& qlo) {
   double c[8];
   double t[8];
@@ -209,12 +216,12 @@ __device__ __forceinline__ void fast_col(const Col16& in, const double* __restri
   }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const double qd = (double)in.q[r];
+    const int q = in.q[r];
     if constexpr (!AP) {
-      qhi = max(qhi, (int)in.q[r]);
-      qlo = min(qlo, (int)in.q[r]);
+      qhi = max(qhi, q);
+      qlo = min(qlo, q);
     }
-    c[r] = qd * t[r];
+    c[r] = (double)q * t[r];
   }
   aan8(c);
 #pragma unroll
@@ -383,7 +390,6 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   __shared__ double s_red[I::NT / 64], s_dq[I::NT / 64];
   __shared__ uint32_t s_lmin[I::NT / 64], s_lmax[I::NT / 64];
   __shared__ uint32_t s_cert[3];  // min / max fraction word, max |q|
-  __shared__ double s_dummy[64];  // the window stores' sink for ring columns outside it
   __shared__ unsigned long long s_sse;
   const int tid = threadIdx.x, lv = tid & 7, lb = tid >> 3;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
@@ -419,17 +425,17 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     if (XTRA && tid == 0) s_sse = 0ull;
     __syncthreads();
   };
-  Col16 lq;
-  {
+  auto luma_load = [&](int r) {
     int by, bx;
-    const bool ok = luma_blk(0, by, bx);
-    lq = load_col(cf, ((long long)by * g.nbx + bx) * 64, lv, ok);
-  }
+    const bool ok = luma_blk(r, by, bx);
+    return load_col32(cf, ((long long)by * g.nbx + bx) * 64, lv, ok);
+  };
+  Col32 lq = luma_load(0);
   // one chroma block task: column pass, and for the rows the tile needs the row
   // pass, clip and window stores (plane p; InvRows::need: a raised 4:2:0 tile
   // takes five rows of its top and bottom block rows, an aligned one a single
   // row of its ring blocks)
-  auto chroma_task = [&](const int p, const int by, const int bx, const Col16& cur) {
+  auto chroma_task = [&](const int p, const int by, const int bx, const Col32& cur) __attribute__((always_inline)) {
     const bool need = rows.need(by, lv);
     fast_col<AP>(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
     if (need) {
@@ -437,11 +443,33 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
       fast_row<-128>(s_mid + lb * MS, lv, c);
       double* w = &s_cw[p][(by * 8 + lv - cwy0) * I::CWS];
       const int wc0 = bx * 8 - cwx0;
-      // the ring blocks' columns outside the window go to a per-lane dummy
-      // slot: a select per store instead of a branch per store
+      if constexpr (I::RX == 0) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k)
-        *((unsigned)(wc0 + k) < (unsigned)I::CWC ? w + wc0 + k : s_dummy + (tid & 63)) = c[k];
+        for (int k = 0; k < 8; ++k) w[wc0 + k] = c[k];
+      } else {
+        // X0 / SX is a multiple of 8, so block column j of the task grid starts
+        // at window column 8 j - 7: an interior block (1 <= j <= CBC - 2) lies
+        // wholly inside the window, the left ring block (j = 0) contributes
+        // its column 7 to window column 0 and the right one (j = CBC - 1) its
+        // column 0 to window column CWC - 1.  One store base per task and
+        // eight stores at constant offsets (paired into ds_write2_b64, whose
+        // 8-lane groups are one block's rows: 70 doubles apart, disjoint
+        // banks).  A ring block's go to a sink, the lane's own row of the
+        // block's transpose slot: the slot's eight lanes are one wave's,
+        // fast_row's reads are issued before these stores and the wave's LDS
+        // operations execute in order.  (Rows 8 doubles apart share banks
+        // four ways; a sink at 9 doubles per lane is conflict-free by
+        // tools/lds_bank_model.py, costs 4 VALU instructions per wave more
+        // and measured level)  The block's one needed
+        // value follows in a single predicated store.
+        static_assert((I::TW / I::SX) % 8 == 0, "block columns at 8 j - 7");
+        const int j = bx - cbx0;
+        const bool ring = j == 0 || j == I::CBC - 1;
+        double* const base = ring ? s_mid + lb * MS + lv * 8 : w + wc0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) base[k] = c[k];
+        if (ring) *(j == 0 ? w : w + (I::CWC - 1)) = j == 0 ? c[7] : c[0];
+      }
       if constexpr (I::SX == 2) {
         // cv2's clamped taps at the image's left / right edge pixels read the
         // edge column alone: replicate it into the ring (and past the
@@ -473,38 +501,38 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
       ok = tt < NTASK && by >= 0 && bx >= 0 && by < g.ncy && bx < g.ncx;
       return ((long long)by * g.ncx + bx) * 64;
     };
-    int pp, ii, by, bx;
-    bool ok;
-    long long off = tinfo(lb, pp, ii, by, bx, ok);
-    Col16 cq = load_col(cf + (pp ? g.off_cr : g.off_cb), off, lv, ok);
+    // a lane group's one or two tasks (lb, lb + RB) written out, each column
+    // in registers of its own: the second task's loads are in flight during
+    // the first's arithmetic, and nothing is copied between them
+    static_assert(NTASK <= 2 * I::RB, "two tasks per lane group at the most");
+    int p0, p1, ii, by0, bx0, by1, bx1;
+    bool ok0, ok1;
+    const long long off0 = tinfo(lb, p0, ii, by0, bx0, ok0);
+    const Col32 cq0 = load_col32(cf + (p0 ? g.off_cr : g.off_cb), off0, lv, ok0);
     table_setup();
     if (!AP && tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
-#pragma unroll 1
-    for (int tt = lb; tt < NTASK; tt += I::RB) {  // (uniform per wave: RB lane groups, 8 per wave)
-      const Col16 cur = cq;
-      const int pc = pp, byc = by, bxc = bx;
-      const bool okc = ok;
-      if (tt + I::RB < NTASK) {
-        off = tinfo(tt + I::RB, pp, ii, by, bx, ok);
-        cq = load_col(cf + (pp ? g.off_cr : g.off_cb), off, lv, ok);
-      }
-      if (okc) chroma_task(pc, byc, bxc, cur);
-    }
+    const bool two = lb + I::RB < NTASK;  // (uniform per wave: RB lane groups, 8 per wave)
+    const long long off1 = tinfo(lb + I::RB, p1, ii, by1, bx1, ok1);  // (ok1 false without a second task)
+    Col32 cq1;  // (read only when `two`)
+    if (two) cq1 = load_col32(cf + (p1 ? g.off_cr : g.off_cb), off1, lv, ok1);
+    if (ok0) chroma_task(p0, by0, bx0, cq0);
+    if (two && ok1) chroma_task(p1, by1, bx1, cq1);
   } else {
     const bool ctask = lb < rows.ncbr * I::CBC;
     const int ci = lb / I::CBC, cj = lb - ci * I::CBC;
     const int cby = cby0 + ci, cbx = cbx0 + cj;
     const bool cvalid = ctask && cby >= 0 && cbx >= 0 && cby < g.ncy && cbx < g.ncx;
     const long long cboff = ((long long)cby * g.ncx + cbx) * 64;
-    Col16 cq = load_col(cf + g.off_cb, cboff, lv, cvalid);
+    const Col32 cqb = load_col32(cf + g.off_cb, cboff, lv, cvalid);
     table_setup();
     if (!AP && tid == 0) s_qmax = fq[frame].qmax;  // (used by this thread after the next barrier)
+    // the two planes written out, each column in registers of its own: Cr's
+    // loads are in flight during Cb's arithmetic and nothing is copied
     if (ctask) {
-#pragma unroll 1
-      for (int p = 0; p < 2; ++p) {
-        const Col16 cur = cq;
-        if (p == 0) cq = load_col(cf + g.off_cr, cboff, lv, cvalid);
-        if (cvalid) chroma_task(p, cby, cbx, cur);
+      const Col32 cqr = load_col32(cf + g.off_cr, cboff, lv, cvalid);
+      if (cvalid) {
+        chroma_task(0, cby, cbx, cqb);
+        chroma_task(1, cby, cbx, cqr);
       }
     }
   }
@@ -517,19 +545,12 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
   double ssy = 0.0;
   const uint8_t* in_f = XTRA ? rgb_in + (size_t)(frame / in_div) * g.H * g.W * 3 : nullptr;
   uint8_t* out_f = rgb_out + (size_t)frame * g.H * g.W * 3;
-#pragma unroll 1
-  for (int r = 0; r < I::NYB / I::RB; ++r) {
+  auto luma_round = [&](const int r, const Col32& cur) __attribute__((always_inline)) {
     int by, bx;
     const bool bvalid = luma_blk(r, by, bx);
     // the luma SSE in the exact kernel's order: per-round sums, added per round
     unsigned long long r_sse = 0ull;
     double r_ssy = 0.0;
-    const Col16 cur = lq;
-    if (r + 1 < I::NYB / I::RB) {
-      int by1, bx1;
-      const bool ok1 = luma_blk(r + 1, by1, bx1);
-      lq = load_col(cf, ((long long)by1 * g.nbx + bx1) * 64, lv, ok1);
-    }
     if (bvalid) fast_col<AP>(cur, s_qs, lv, s_mid + lb * MS, qhi, qlo);
     const int y = by * 8 + lv, x0 = bx * 8;
     if (bvalid && y < g.H && x0 < g.W) {
@@ -621,6 +642,20 @@ __device__ __forceinline__ bool inv_fast_tile(InvShared<MODE, XTRA>& sh, const G
     if constexpr (XTRA > 0) {
       sse += r_sse;
       ssy = ssy + r_ssy;
+    }
+  };
+  // two rounds per trip with the columns' roles swapped: round r + 1's loads
+  // land in `nq` during round r's arithmetic on `lq`, round r + 2's in `lq`
+  // during round r + 1's: no copy of the prefetched column
+  constexpr int NR = I::NYB / I::RB;
+#pragma unroll 1
+  for (int r = 0; r < NR; r += 2) {
+    Col32 nq;  // (read only when round r + 1 exists)
+    if (r + 1 < NR) nq = luma_load(r + 1);
+    luma_round(r, lq);
+    if (r + 1 < NR) {
+      if (r + 2 < NR) lq = luma_load(r + 2);
+      luma_round(r + 1, nq);
     }
   }
 
@@ -1106,9 +1141,9 @@ k_inv_fast444(const Geo g, const int16_t* __restrict__ coeffs, const FrameQ* __r
   const int16_t* cf = coeffs + (size_t)frame * g.cpf;
   double* slot = s_mid + lb * MS;
   // the coefficient loads are issued before the table set-up and its barrier
-  const Col16 qy = load_col(cf, bq * 64, lv, bvalid);
-  const Col16 qb = load_col(cf + g.off_cb, bq * 64, lv, bvalid);
-  const Col16 qr = load_col(cf + g.off_cr, bq * 64, lv, bvalid);
+  const Col32 qy = load_col32(cf, bq * 64, lv, bvalid);
+  const Col32 qb = load_col32(cf + g.off_cb, bq * 64, lv, bvalid);
+  const Col32 qr = load_col32(cf + g.off_cr, bq * 64, lv, bvalid);
   if (tid < 64) {
     const double q = fq[frame].q[tid];
     s_qs[qs_index(tid >> 3, tid & 7)] = q * c_aan[tid >> 3] * c_aan[tid & 7] * 0.125;
