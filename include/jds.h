@@ -1097,6 +1097,102 @@ int jds_selftest_resize(const uint8_t* rgb, int64_t H, int64_t W, const float* b
 int jds_selftest_resize_coeffs(int32_t in_size, float in0, float in1, int32_t out_size, int32_t resample,
                                int32_t* ksize, int32_t* bounds, int32_t* taps, int64_t cap);
 
+/* Progressive files (DESIGN.md "Progressive files"): entry points of their own
+ * beside the baseline ones -- jds_jpeg_parse and every jds_jpeg_* call keep
+ * rejecting SOF2 by name.  A progressive file is read as its frame (a
+ * jds_jpeg_info filled as jds_jpeg_parse fills it for the baseline file of the
+ * same frame: interleaved = 1, n_scans = 1; one component: JDS_SS_GRAY,
+ * interleaved = 0; scan[] and huff[] stay zero) plus its scan script, and
+ * decodes into the planar coefficient layout of jds_decode_jpeg, so the
+ * renderings, the reduced-size decode and the baseline writer take it
+ * unchanged.
+ *
+ * jds_pjpeg_parse (host only; never reads outside [data, data + len)) accepts
+ *   SOF2, 8-bit, one or three components with the sampling jds_jpeg_parse
+ *   accepts; DC scans (Ss = Se = 0) of one or of all three components; AC scans
+ *   with Ns = 1 and 1 <= Ss <= Se <= 63; Al <= 13, Ah = 0 or Al = Ah - 1;
+ *   Huffman ids 0..3, redefined between scans at will: a scan records the FILE
+ *   OFFSETS (of the Tc/Th byte) of the DHT definitions in effect at its SOS,
+ *   -1 for a table it does not read.  The progression must be consistent: a
+ *   coefficient's first scan has Ah = 0, a refinement has Ah equal to the Al
+ *   last coded for every coefficient of its band, no AC scan comes before the
+ *   component's first DC scan -- otherwise JDS_EINVAL naming the scan.  A 65th
+ *   scan is JDS_ENOTSUP.  A baseline file is JDS_ENOTSUP "not progressive
+ *   (SOF0): use the jpeg_* calls"; the other refusals of jds_jpeg_parse stay.
+ *   complete: every coefficient of every component was coded down to Al = 0.
+ * The decode (k_pjpeg_chains) walks CHAINS: the DC scans of a file form one,
+ *   the AC scans of each component one more; a chain is walked by one lane,
+ *   scan after scan, by T.81 Annex G.  A defect -- a code not in the table, a
+ *   run or a correction past Se, an EOBRUN longer than the blocks left, data
+ *   ending early, a wrong or missing RSTm -- sets JDS_DEC_* bits and ends the
+ *   chain; coefficients of such a file are unspecified, nothing outside its
+ *   coefficient range is written.
+ * jds_pjpeg_decode: one file, host bytes to host coefficients; synchronous;
+ *   fills info (info->status: the JDS_DEC_* bits) and returns JDS_EINVAL naming
+ *   the defect when status != 0.
+ * jds_pjpeg_batch_layout / jds_pjpeg_batch_to_rgb: jds_jpeg_batch_layout_scaled's
+ *   and jds_jpeg_batch_to_rgb_scaled's layout, item and error contracts
+ *   (scale_denoms NULL: all 1); the chains launch, then the existing batch
+ *   render kernels.  A file with complete == 0 is an item error JDS_ENOTSUP
+ *   "incomplete progression" (libjpeg smooths such files; the rendering would
+ *   not be libjpeg's).
+ * jds_pjpeg_batch_transcode: jds_jpeg_batch_transcode's contract; the prefix
+ *   is the file's own segments before its first SOS except DHT and DRI, with
+ *   its SOF2 marker rewritten as SOF0.  Incomplete files transcode.
+ * jds_pjpeg_to_rgb, jds_pjpeg_transcode: the batch of one; the item's rc (or
+ *   JDS_EINVAL for defective scan data) is the call's.
+ * jds_selftest_pjpegdec: test-only, host only: the same core, chain after chain. */
+#define JDS_PJPEG_MAX_SCANS 64
+typedef struct {
+  int32_t n_components;        /* Ns: 1 or 3 */
+  int32_t component[3];        /* 1 Y, 2 Cb, 3 Cr, in scan order */
+  int32_t dc_table[3], ac_table[3]; /* Huffman table ids (0..3) per scan component */
+  int32_t ss, se, ah, al;
+  int32_t restart_interval;    /* DRI in effect at SOS, in MCUs of this scan (Ns = 1: blocks); 0: none */
+  int32_t reserved;
+  int64_t offset, length;      /* the entropy-coded segment, RSTm markers included */
+  int64_t dc_dht[3], ac_dht[3]; /* per scan component: file offset of the table definition it reads; -1: none */
+} jds_pjpeg_scan;
+
+typedef struct {
+  jds_jpeg_info frame;
+  int32_t n_scans;
+  int32_t complete;
+  uint32_t status;             /* jds_pjpeg_decode: the file's JDS_DEC_* bits */
+  uint32_t reserved;
+  jds_pjpeg_scan scan[JDS_PJPEG_MAX_SCANS]; /* in file order */
+} jds_pjpeg_info;
+
+int jds_pjpeg_parse(const uint8_t* data, int64_t len, jds_pjpeg_info* out);
+int jds_pjpeg_decode(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
+                     jds_pjpeg_info* info);
+/* jds_pjpeg_decode with the coefficients left in the caller's buffer on the context's device
+ * (coeffs_cap >= coeffs_needed entries; only entries [0, coeffs_needed) are written): what
+ * jds_jpeg_render_dev and jds_jpeg_render_scaled_dev take with info->frame.  Synchronous. */
+int jds_pjpeg_decode_dev(jds_ctx* ctx, const uint8_t* data, int64_t len, int16_t* coeffs_dev, int64_t coeffs_cap,
+                         jds_pjpeg_info* info);
+int jds_selftest_pjpegdec(const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap, jds_pjpeg_info* info);
+/* On a profiled context (jds_ctx_profile): the walk time in microseconds of every scan of the
+ * last progressive call on it, by the device's wall clock inside k_pjpeg_chains.  Order: the
+ * files that took part, in batch order; per file its DC chain, then the AC chain of each
+ * component; per chain its scans in file order.  *count entries (cap too small: JDS_EINVAL with
+ * the need in *count); none when the context was not profiled. */
+int jds_pjpeg_scan_times(jds_ctx* ctx, double* us, int64_t cap, int64_t* count);
+int jds_pjpeg_batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
+                           int64_t* rgb_bytes, int64_t* coef_entries, const int32_t* scale_denoms,
+                           jds_jpeg_scaled_item* scaled);
+int jds_pjpeg_batch_to_rgb(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
+                           int64_t rgb_cap, int32_t rgb_on_device, int32_t render, const int32_t* scale_denoms,
+                           jds_jpeg_batch_item* items, jds_jpeg_scaled_item* scaled, int16_t* coeffs);
+int jds_pjpeg_to_rgb(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t* rgb_out, int64_t rgb_cap,
+                     int32_t rgb_on_device, int32_t render, int32_t scale_denom, int16_t* coeffs,
+                     jds_pjpeg_info* info);
+int jds_pjpeg_batch_transcode(jds_ctx* ctx, const uint8_t* const* data, const int64_t* lens, int32_t n,
+                              int32_t optimize, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                              jds_jpeg_transcode_item* items, int64_t* out_bytes);
+int jds_pjpeg_transcode(jds_ctx* ctx, const uint8_t* data, int64_t len, int32_t optimize, uint8_t* out,
+                        int64_t out_cap, int64_t* out_len, jds_pjpeg_info* info);
+
 /* Test-only: the whole decode on the host with the kernels' shared core
  * (csrc/jds_huffdec.hpp; the host model: csrc/jds_jpeg_parse.hpp) and subsequences of subseq_bits bits (a multiple of 8,
  * >= 64), a host loop standing in for the lanes under the same propagation

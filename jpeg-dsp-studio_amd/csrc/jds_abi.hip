@@ -436,6 +436,7 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->dec_st.release();
   c->dec_iv.release();
   c->dec_mcu.release();
+  c->pj_ticks.release();
   c->bat.release();
   c->mcu_up.release();
   c->mcu_scr.release();

@@ -239,6 +239,10 @@ struct jds_ctx {
   KMarks marks;
   bool prof_on = false;
   DevBuf gen_tab, gen_sub, gen_rec;  // general-geometry path (jds_gen.hip)
+  // progressive files on a profiled context (jds_pjpeg_scan_times): the walk time of every scan
+  // of the last batch, in chain order (device ticks, then microseconds)
+  DevBuf pj_ticks;
+  std::vector<double> pj_scan_us;
   size_t ss_budget = 0;  // SSIM scratch budget per launch group (0: SSIM_SCRATCH; jds_ctx_set_ssim_scratch)
 };
 

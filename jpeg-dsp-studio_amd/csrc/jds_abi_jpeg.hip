@@ -9,6 +9,7 @@
 #include <string>
 
 #include "jds_abi.hpp"
+#include "jds_abi_jpeg.hpp"
 #include "jds_dec_jobs.hpp"
 #include "jds_entropy_mcu_dev.hpp"
 #include "jds_jpeg_fwd.hpp"
@@ -266,7 +267,7 @@ int jds_jpeg_inverse_info(int32_t* tile_h, int32_t* tile_w) {
 
 // The rendering a _render call names: JDS_RENDER_REFERENCE (k_jpeg_inv) or
 // JDS_RENDER_LIBJPEG (k_jpeg_ljt); anything else is the caller's error.
-static int render_check(int32_t render) {
+int render_check(int32_t render) {
   if (render != JDS_RENDER_REFERENCE && render != JDS_RENDER_LIBJPEG)
     return fail(JDS_EINVAL, "unknown render %d (JDS_RENDER_REFERENCE or JDS_RENDER_LIBJPEG)", (int)render);
   return JDS_OK;
@@ -274,7 +275,7 @@ static int render_check(int32_t render) {
 
 // The denominator a _scaled call names: 1, 2, 4 or 8, and only the libjpeg
 // rendering scales.
-static int scale_check(int32_t render, int32_t denom) {
+int scale_check(int32_t render, int32_t denom) {
   if (!ls_denom_ok(denom)) return fail(JDS_EINVAL, "scale_denom %d is not 1, 2, 4 or 8", (int)denom);
   if (denom != 1 && render != JDS_RENDER_LIBJPEG)
     return fail(JDS_EINVAL, "scale_denom %d needs JDS_RENDER_LIBJPEG: the reference rendering has no scaled decode",
@@ -284,7 +285,7 @@ static int scale_check(int32_t render, int32_t denom) {
 
 // The launch arguments of a parsed file: its tables by check_tables' rule, its
 // grids T.81's for H x W, every tile's chroma window within the kernel's arrays.
-static int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
+int jpeg_inv_args(const jds_jpeg_info* info, JInvArgs* a) {
   const int rc = jinv_args(info, a);
   if (rc == -1000)
     return fail(JDS_EINVAL, "jpeg inverse: %lldx%lld with these grids is not a T.81 geometry of subsampling %d",
@@ -898,12 +899,8 @@ int jds_jpeg_batch_to_tensor(jds_ctx* c, const uint8_t* const* data, const int64
 
 // One file of a writer batch: its geometry record (the planes' offsets count
 // from the start of c->ent_cf) and its header prefix.
-struct McuJob {
-  McuFile f;
-  std::vector<uint8_t> pfx;
-};
-
-static int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j) {
+// (struct McuJob: jds_abi_jpeg.hpp, shared with jds_abi_pjpeg.hip)
+int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j) {
   if (mcu_file_of(info, &j->f))
     return fail(JDS_EINVAL,
                 "%lldx%lld with block grids %lldx%lld, %lldx%lld, %lldx%lld is not a T.81 geometry of subsampling %d",
@@ -1162,7 +1159,7 @@ static int xf_prepare(const uint8_t* data, int64_t len, const jds_jpeg_info* inf
 // of 256 into out (jds_jpeg_batch_transcode's contract) with out_off / out_len
 // of their items, and rc for a job that is not baseline-codable, of which
 // bad(item, message) hears.  Synchronous.
-static int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int>& job_item, int32_t optimize,
+int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int>& job_item, int32_t optimize,
                            const XfSet* xf, uint8_t* out, int64_t out_cap, int32_t out_on_device,
                            jds_jpeg_transcode_item* items, int64_t* out_bytes,
                            const std::function<void(int, const char*)>& bad) {

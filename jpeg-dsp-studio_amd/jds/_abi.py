@@ -124,6 +124,21 @@ class JpegInfo(C.Structure):
                 ('huff', JfifHuff * 4), ('coeffs_needed', C.c_int64), ('status', C.c_uint32), ('rounds', C.c_uint32)]
 
 
+PJPEG_MAX_SCANS = 64
+
+
+class PjpegScan(C.Structure):
+    _fields_ = [('n_components', C.c_int32), ('component', C.c_int32 * 3), ('dc_table', C.c_int32 * 3),
+                ('ac_table', C.c_int32 * 3), ('ss', C.c_int32), ('se', C.c_int32), ('ah', C.c_int32),
+                ('al', C.c_int32), ('restart_interval', C.c_int32), ('reserved', C.c_int32), ('offset', C.c_int64),
+                ('length', C.c_int64), ('dc_dht', C.c_int64 * 3), ('ac_dht', C.c_int64 * 3)]
+
+
+class PjpegInfo(C.Structure):
+    _fields_ = [('frame', JpegInfo), ('n_scans', C.c_int32), ('complete', C.c_int32), ('status', C.c_uint32),
+                ('reserved', C.c_uint32), ('scan', PjpegScan * PJPEG_MAX_SCANS)]
+
+
 class JpegBatchItem(C.Structure):
     _fields_ = [('rc', C.c_int32), ('status', C.c_uint32), ('H', C.c_int64), ('W', C.c_int64),
                 ('subsampling', C.c_int32), ('interleaved', C.c_int32), ('rgb_off', C.c_int64),
@@ -293,6 +308,21 @@ _SIGS = {
     'jds_jpeg_batch_transcode': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32,
                                            C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
     'jds_selftest_jpeg_transcode': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    'jds_pjpeg_parse': (C.c_int, [_P, C.c_int64, C.POINTER(PjpegInfo)]),
+    'jds_pjpeg_decode': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(PjpegInfo)]),
+    'jds_pjpeg_decode_dev': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.POINTER(PjpegInfo)]),
+    'jds_pjpeg_scan_times': (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    'jds_selftest_pjpegdec': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(PjpegInfo)]),
+    'jds_pjpeg_batch_layout': (C.c_int, [_P, _P, C.c_int32, C.POINTER(JpegBatchItem), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), _P, C.POINTER(JpegScaledItem)]),
+    'jds_pjpeg_batch_to_rgb': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P,
+                                         C.POINTER(JpegBatchItem), C.POINTER(JpegScaledItem), _P]),
+    'jds_pjpeg_to_rgb': (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
+                                   C.POINTER(PjpegInfo)]),
+    'jds_pjpeg_batch_transcode': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32,
+                                            C.POINTER(JpegTranscodeItem), C.POINTER(C.c_int64)]),
+    'jds_pjpeg_transcode': (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),
+                                      C.POINTER(PjpegInfo)]),
     'jds_selftest_jpeg_encode': (C.c_int, [C.POINTER(JpegInfo), _P, C.c_int32, _P, C.c_int64, _P, C.c_int64,
                                            C.POINTER(C.c_int64)]),
     'jds_selftest_jpeg_hist_dev': (C.c_int, [_P, C.POINTER(JpegInfo), _P, _P]),

@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, 'libjds.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = os.environ.get('JDS_OFFLOAD_ARCH', 'gfx950')
 
-SOURCES = ['jds_codec.hip', 'jds_gen.hip', 'jds_b16.hip', 'jds_inv.hip', 'jds_inv_fast.hip', 'jds_fast.hip', 'jds_fast16.hip', 'jds_stages.hip', 'jds_ssim.hip', 'jds_ssim_band.hip', 'jds_entropy.hip', 'jds_huffopt.hip', 'jds_entropy_mcu.hip', 'jds_xform.hip', 'jds_entropy_dec.hip', 'jds_jpeg_inv.hip', 'jds_jpeg_ljt.hip', 'jds_jpeg_ljs.hip', 'jds_jpeg_fwd.hip', 'jds_abi.hip', 'jds_abi_jpeg.hip', 'jds_resize.hip', 'jds_abi_resize.hip']
+SOURCES = ['jds_codec.hip', 'jds_gen.hip', 'jds_b16.hip', 'jds_inv.hip', 'jds_inv_fast.hip', 'jds_fast.hip', 'jds_fast16.hip', 'jds_stages.hip', 'jds_ssim.hip', 'jds_ssim_band.hip', 'jds_entropy.hip', 'jds_huffopt.hip', 'jds_entropy_mcu.hip', 'jds_xform.hip', 'jds_entropy_dec.hip', 'jds_jpeg_inv.hip', 'jds_jpeg_ljt.hip', 'jds_jpeg_ljs.hip', 'jds_jpeg_fwd.hip', 'jds_abi.hip', 'jds_abi_jpeg.hip', 'jds_pjpeg_dec.hip', 'jds_abi_pjpeg.hip', 'jds_resize.hip', 'jds_abi_resize.hip']
 
 
 def headers():

@@ -513,8 +513,9 @@ def jpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = '
     return _batch_transcode(files, optimize, out, errors, device, ctx, None)
 
 
-def _batch_transcode(files, optimize, out, errors, device, ctx, ops):
-    """jpeg_batch_transcode (ops None) and jpeg_batch_transform (ops: one JDS_XF_* code per file)."""
+def _batch_transcode(files, optimize, out, errors, device, ctx, ops, progressive=False):
+    """jpeg_batch_transcode (ops None) and jpeg_batch_transform (ops: one JDS_XF_* code per file);
+    progressive: pjpeg_batch_transcode (jds_pjpeg_batch_transcode, the same arguments)."""
     if errors not in ('raise', 'items'):
         raise ValueError("errors must be 'raise' or 'items'")
     keep, ptrs, lens = _batch_args(files)
@@ -538,8 +539,8 @@ def _batch_transcode(files, optimize, out, errors, device, ctx, ops):
         if ops is not None:
             return lib().jds_jpeg_batch_transform(c.handle, ptrs, lens, n, ops_arr, int(bool(optimize)),
                                                   C.c_void_p(dst), cap, on_dev, items, C.byref(need))
-        return lib().jds_jpeg_batch_transcode(c.handle, ptrs, lens, n, int(bool(optimize)), C.c_void_p(dst), cap,
-                                              on_dev, items, C.byref(need))
+        call = lib().jds_pjpeg_batch_transcode if progressive else lib().jds_jpeg_batch_transcode
+        return call(c.handle, ptrs, lens, n, int(bool(optimize)), C.c_void_p(dst), cap, on_dev, items, C.byref(need))
 
     def alloc(cap):
         if out is None:
@@ -634,6 +635,174 @@ def jpeg_batch_transform(files, ops='auto', trim: bool = False, optimize: bool =
 
 # ----------------------------------------------------------- libjpeg encoding --
 # (DESIGN.md "libjpeg encoding"; definition: tests/libjpeg_fwd_ref.py)
+
+def is_progressive(data) -> bool:
+    """True when the file's frame header is SOF2 (host only: a marker walk up to the first SOF or
+    SOS; anything that is not a marker sequence from SOI is False).  Such a file goes through the
+    pjpeg_* calls; the jpeg_* calls reject it by name."""
+    b = bytes(data) if not isinstance(data, np.ndarray) else data.tobytes()
+    if len(b) < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        return False
+    p = 2
+    while p + 4 <= len(b) and b[p] == 0xFF:
+        m = b[p + 1]
+        if m == 0xFF:
+            p += 1
+            continue
+        if m == 0xC2:
+            return True
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC) or m in (0xDA, 0xD9):
+            return False
+        p += 2 + ((b[p + 2] << 8) | b[p + 3])
+    return False
+
+
+def pjpeg_to_rgb(data, out=None, render: str = 'libjpeg', scale_denom: int = 1, with_info: bool = False,
+                 device: int = 0):
+    """jds_pjpeg_to_rgb: a progressive JPEG parse_pjpeg accepts -> the image, by the chain decode
+    (k_pjpeg_chains) and the rendering jpeg_to_rgb names: render='libjpeg' is byte for byte
+    np.asarray(PIL.Image.open(f).convert('RGB')), with scale_denom 2, 4, 8 PIL's Image.draft;
+    render='reference' is jpeg_to_rgb's image of the baseline file with the same coefficients.
+    out, scale_denom and with_info (image, decode_pjpeg's dict) as jpeg_to_rgb's.  ValueError for
+    a file the parser rejects (a baseline file: "not progressive"), for defective scan data and
+    for a progression that stops short of Al = 0 ("incomplete progression": libjpeg smooths such
+    a file; pjpeg_transcode takes it)."""
+    from . import entropy
+    code = _abi.render_code(render)
+    d = _abi.scale_denom_arg(scale_denom, render)
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.PjpegInfo()
+    check(lib().jds_pjpeg_parse(p, n, C.byref(info)))
+    H, W = -(-int(info.frame.H) // d), -(-int(info.frame.W) // d)
+    if out is None:
+        img = np.empty((H, W, 3), np.uint8)
+        dst, on_dev = img.ctypes.data, 0
+    else:
+        if tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.element_size() != 1:
+            raise ValueError(f'out must be a contiguous uint8 ({H}, {W}, 3) device tensor')
+        img, dst, on_dev = out, int(out.data_ptr()), 1
+    cf = np.empty(int(info.frame.coeffs_needed), np.int16) if with_info else None
+    with lease(device) as ctx:
+        check(lib().jds_pjpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev, code, d,
+                                     cf.ctypes.data if with_info else None, C.byref(info)))
+    if not with_info:
+        return img
+    dd = entropy._pjpeg_dict(info)
+    dd.update(coeffs=cf, route='chains', scale_denom=d, out_H=H, out_W=W)
+    return img, dd
+
+
+def pjpeg_batch_to_rgb(files, out='device', render: str = 'libjpeg', scale_denom=1, errors: str = 'raise',
+                       with_info: bool = False, device: int = 0, ctx=None):
+    """jds_pjpeg_batch_to_rgb: a sequence of progressive JPEGs -> their images, decoded by one
+    k_pjpeg_chains launch over every file's chains and the batch render kernels jpeg_batch_to_rgb
+    runs; each image is pjpeg_to_rgb's.  out, scale_denom, errors ('raise' / 'return'), with_info
+    and ctx as jpeg_batch_to_rgb's, with its layout (images at multiples of 256) and its item
+    contract: a baseline file ("not progressive"), an incomplete progression or defective scan
+    data is that file's error and does not stop the others."""
+    if errors not in ('raise', 'return'):
+        raise ValueError("errors must be 'raise' or 'return'")
+    code = _abi.render_code(render)
+    keep, ptrs, lens = _batch_args(files)
+    n = len(keep)
+    dens, dens_c = _batch_denoms(scale_denom, n, render)
+    items = (_abi.JpegBatchItem * max(n, 1))()
+    if out is None or isinstance(out, str):
+        rb, ce = C.c_int64(0), C.c_int64(0)
+        check(lib().jds_pjpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce), dens_c, None))
+        cap = int(rb.value)
+    if out is None:
+        buf = np.empty(max(cap, 1), np.uint8)
+        dst, on_dev = buf.ctypes.data, 0
+    else:
+        if isinstance(out, str):
+            if out != 'device':
+                raise ValueError("out must be None, 'device' or a 1-D uint8 device tensor")
+            import torch
+            buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=f'cuda:{device}')
+        else:
+            buf = out
+            if buf.dim() != 1 or buf.element_size() != 1 or not buf.is_contiguous():
+                raise ValueError('out must be a contiguous 1-D uint8 device tensor')
+            cap = int(buf.numel())
+        dst, on_dev = int(buf.data_ptr()), 1
+
+    def run(c):
+        return lib().jds_pjpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, code, dens_c, items,
+                                            None, None)
+    if ctx is not None:
+        check(run(ctx))
+    else:
+        with lease(device) as c:
+            check(run(c))
+    info = [_batch_item_dict(items[i], dens[i]) for i in range(n)]
+    first = _batch_first_error(info)
+    if first and errors == 'raise':
+        raise ValueError(first)
+    imgs = []
+    for it in info:
+        if it['rc'] != 0 or it['status'] != 0:
+            imgs.append(None)
+            continue
+        o, sz = it['rgb_off'], it['out_H'] * it['out_W'] * 3
+        imgs.append(buf[o:o + sz].reshape(it['out_H'], it['out_W'], 3))
+    if not with_info:
+        return imgs
+    ok = [it for it in info if it['rc'] == 0]
+    return imgs, {'items': info, 'rgb_bytes': sum(-(-it['out_H'] * it['out_W'] * 3 // 256) * 256 for it in ok),
+                  'coef_entries': sum(it['coeffs_needed'] for it in ok)}
+
+
+def pjpeg_scan_times(ctx, files, took_part=None):
+    """jds_pjpeg_scan_times: after a pjpeg_batch_* call on the profiled Context `ctx`
+    (ctx.profile(True)), the walk time of every scan inside k_pjpeg_chains -> per file that took
+    part (took_part: one flag per file, default all) a list of (scan index in file order,
+    microseconds), None for the others."""
+    from . import entropy
+    n = C.c_int64(0)
+    lib().jds_pjpeg_scan_times(ctx.handle, None, 0, C.byref(n))
+    us = np.zeros(max(int(n.value), 1), np.float64)
+    check(lib().jds_pjpeg_scan_times(ctx.handle, us.ctypes.data, int(n.value), C.byref(n)))
+    out, k = [], 0
+    for i, f in enumerate(files):
+        if took_part is not None and not took_part[i]:
+            out.append(None)
+            continue
+        scans = entropy.parse_pjpeg(f)['scans']
+        order = [j for j, s in enumerate(scans) if s['ss'] == 0]
+        for c in (1, 2, 3):
+            order += [j for j, s in enumerate(scans) if s['ss'] and s['components'][0] == c]
+        out.append([(j, float(us[k + m])) for m, j in enumerate(order)])
+        k += len(order)
+    if k != int(n.value):
+        raise ValueError(f'{int(n.value)} scan times for {k} scans: the files are not the last call\'s')
+    return out
+
+
+def pjpeg_transcode(data, optimize: bool = True, device: int = 0, with_info: bool = False):
+    """jds_pjpeg_transcode: a progressive JPEG -> the baseline file of the same coefficients
+    (`jpegtran` from progressive to baseline): one interleaved scan behind the file's own APPn,
+    COM and DQT segments and its frame header rewritten as SOF0, with optimised Huffman tables or
+    the Annex K ones; every jpeg_* call reads the result.  A progression that stops short of
+    Al = 0 transcodes as well: the coefficients are what the scans give.  ValueError as
+    jpeg_transcode.  with_info: (bytes, parse_pjpeg's dict)."""
+    from . import entropy
+    a, p, n = entropy._bytes_arg(data)
+    info = _abi.PjpegInfo()
+    with lease(device) as ctx:
+        out = entropy._grown(lambda o, cap, m: lib().jds_pjpeg_transcode(
+            ctx.handle, p, n, int(bool(optimize)), o.ctypes.data, cap, C.byref(m), C.byref(info)),
+            2 * n + 4096)
+    return (out, entropy._pjpeg_dict(info)) if with_info else out
+
+
+def pjpeg_batch_transcode(files, optimize: bool = True, out=None, errors: str = 'raise', device: int = 0, ctx=None):
+    """jds_pjpeg_batch_transcode: a sequence of progressive JPEGs -> each one's pjpeg_transcode
+    output, by one k_pjpeg_chains launch and one set of writer launches; arguments, packing (file
+    i at a multiple of 256) and item contract of jpeg_batch_transcode.  out='device' feeds
+    jpeg_batch_to_rgb, jpeg_batch_to_tensor and the transforms without leaving the device."""
+    return _batch_transcode(files, optimize, out, errors, device, ctx, None, progressive=True)
+
 
 def _ss_code(subsampling) -> int:
     if subsampling not in _abi.JPEG_MODE_CODES:

@@ -218,6 +218,82 @@ def host_decode_jpeg(data, subseq_bits: int = 1024):
     return cf, [int(r) for r in rounds][:int(info.n_scans)]
 
 
+def _pjpeg_dict(info: _abi.PjpegInfo) -> dict:
+    """The frame in parse_jpeg's terms (as the baseline file of the same frame parses, without
+    'scans' and 'huffman' entries of its own) plus the scan script."""
+    d = _jpeg_dict(info.frame)
+    scans = []
+    for s in info.scan[:info.n_scans]:
+        n = int(s.n_components)
+        scans.append({'components': list(s.component)[:n], 'dc_tables': list(s.dc_table)[:n],
+                      'ac_tables': list(s.ac_table)[:n], 'ss': int(s.ss), 'se': int(s.se), 'ah': int(s.ah),
+                      'al': int(s.al), 'restart_interval': int(s.restart_interval), 'offset': int(s.offset),
+                      'length': int(s.length), 'dc_dht': list(s.dc_dht)[:n], 'ac_dht': list(s.ac_dht)[:n]})
+    d.update(scans=scans, huffman={}, progressive=True, complete=bool(info.complete))
+    return d
+
+
+def parse_pjpeg(data) -> dict:
+    """jds_pjpeg_parse (host only, no GPU): a progressive JPEG (SOF2, 8-bit, one or three
+    components) -> parse_jpeg's dict of its frame plus 'scans': the scan script in file order
+    ('components', 'ss', 'se', 'ah', 'al', 'restart_interval', the byte range, and 'dc_dht' /
+    'ac_dht': the file offsets of the Huffman table definitions in effect at that scan, -1 where
+    it reads none) and 'complete': every coefficient is coded down to Al = 0.  ValueError naming
+    the feature or the scan for anything else; a baseline file is "not progressive"."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.PjpegInfo()
+    check(lib().jds_pjpeg_parse(p, n, C.byref(info)))
+    return _pjpeg_dict(info)
+
+
+def decode_pjpeg(data, device: int = 0, with_status: bool = False) -> dict:
+    """jds_pjpeg_decode: one progressive file -> parse_pjpeg's dict plus 'coeffs' (decode_jpeg's
+    planar layout), decoded by k_pjpeg_chains: one lane per chain (all DC scans; each component's
+    AC scans), scan after scan.  Defective scan data: ValueError naming the defect, or with
+    with_status the dict with 'status' != 0 and unspecified coefficients."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.PjpegInfo()
+    check(lib().jds_pjpeg_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.frame.coeffs_needed), np.int16)
+    with _abi.lease(device) as ctx:
+        rc = lib().jds_pjpeg_decode(ctx.handle, p, n, cf.ctypes.data, cf.size, C.byref(info))
+    if not (with_status and rc == _abi.JDS_EINVAL and info.status):
+        check(rc)
+    d = _pjpeg_dict(info)
+    d['coeffs'] = cf
+    d['status'] = int(info.status)
+    return d
+
+
+def decode_pjpeg_dev(data, coeffs_ptr: int, coeffs_cap: int, device: int = 0) -> dict:
+    """jds_pjpeg_decode_dev: decode_pjpeg with the coefficients left in the caller's device buffer
+    (coeffs_cap int16 entries at coeffs_ptr; entries [0, coeffs_needed) are written) -> parse_pjpeg's
+    dict plus 'status' (never raises for defective scan data)."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.PjpegInfo()
+    with _abi.lease(device) as ctx:
+        rc = lib().jds_pjpeg_decode_dev(ctx.handle, p, n, C.c_void_p(int(coeffs_ptr)), int(coeffs_cap), C.byref(info))
+    if not (rc == _abi.JDS_EINVAL and info.status):
+        check(rc)
+    d = _pjpeg_dict(info)
+    d['status'] = int(info.status)
+    return d
+
+
+def host_decode_pjpeg(data, with_status: bool = False):
+    """Test aid (jds_selftest_pjpegdec): decode_pjpeg's core on the host, chain after chain ->
+    coeffs (with_status: (coeffs, status bits)).  No GPU."""
+    a, p, n = _bytes_arg(data)
+    info = _abi.PjpegInfo()
+    check(lib().jds_pjpeg_parse(p, n, C.byref(info)))
+    cf = np.empty(int(info.frame.coeffs_needed), np.int16)
+    rc = lib().jds_selftest_pjpegdec(p, n, cf.ctypes.data, cf.size, C.byref(info))
+    if with_status and rc == _abi.JDS_EINVAL and info.status:
+        return cf, int(info.status)
+    check(rc)
+    return (cf, 0) if with_status else cf
+
+
 def _grown(call, cap: int) -> bytes:
     """call(out array, cap, length) -> rc, repeated once with the size the C side reports."""
     n = C.c_int64(0)

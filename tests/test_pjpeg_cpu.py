@@ -1,0 +1,298 @@
+"""Progressive files without a GPU (DESIGN.md "Progressive files"): the yardstick
+(tests/progressive_ref.py) against Pillow in both directions, the parser's fields and refusals,
+the host model of the chain decode (jds_selftest_pjpegdec: the kernel's own core) against the
+yardstick, the ABI mirror, and the stand-alone sanitizer program."""
+import ctypes as C
+import io
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import interleaved_ref as il
+import pjpeg_cases as pc
+import progressive_ref as pr
+from conftest import ROOT
+
+
+@pytest.fixture(scope='module')
+def E():
+    from jds import build, entropy
+    build.build()
+    return entropy
+
+
+# ------------------------------------------------- 1. the yardstick and Pillow --
+
+@pytest.mark.parametrize('H,W,ss,rst,q', pc.PILLOW_PARAMS, ids=pc.PILLOW_IDS)
+def test_yardstick_decodes_pillow_progressive_to_the_baseline_twins_coefficients(H, W, ss, rst, q):
+    """libjpeg quantises identically in both modes."""
+    arr, prog, base, _ = pc.pillow_pair(H, W, ss, rst, q)
+    if ss == 'L':
+        import gray_ref
+        want = gray_ref.decode(base)['planar']
+    else:
+        want = il.decode(base)['planar']
+    d = pr.decode(prog)
+    assert d['complete'] and np.array_equal(d['planar'], want)
+
+
+@pytest.mark.parametrize('H,W,mode,name', pc.SCRIPT_PARAMS, ids=pc.SCRIPT_IDS)
+def test_pillow_opens_the_yardsticks_files(H, W, mode, name):
+    f, padded, complete = pc.script_file(H, W, mode, name)
+    _, grids, _ = il.geometry(H, W, mode)
+    d = pr.decode(f)
+    if not complete:
+        assert not d['complete']
+        return
+    assert d['complete'] and np.array_equal(d['planar'], il.crop(padded, grids))
+    if name == 'full_amplitude':
+        return          # (pixels far outside [0, 255]: libjpeg's C and SIMD inverses differ there)
+    base = il.write(padded, H, W, mode, pc.QT)
+    assert np.array_equal(pc.pillow_rgb(f), pc.pillow_rgb(base))
+
+
+def test_yardstick_round_trips_the_eobrun_file():
+    f, planar = pc.eobrun_file()
+    assert np.array_equal(pc.reference(f), planar)
+    # Pillow reads the one AC coefficient where it was put: the last block alone has texture
+    img = pc.pillow_rgb(f)[:, :, 0].astype(int)
+    blocks = img.reshape(182, 8, 182, 8).transpose(0, 2, 1, 3).reshape(182, 182, 64)
+    flat = blocks.max(axis=2) == blocks.min(axis=2)
+    assert not flat[-1, -1] and flat.sum() == 182 * 182 - 1
+
+
+# ---------------------------------------------------------- 2. parser fields --
+
+def _scan_tuple(s):
+    return (tuple(c - 1 for c in s['components']), s['ss'], s['se'], s['ah'], s['al'])
+
+
+def test_parser_fields_on_pillows_colour_file(E):
+    arr, prog, base, _ = pc.pillow_pair(40, 56, 2, 0, 75)
+    d, b = E.parse_pjpeg(prog), E.parse_jpeg(base)
+    assert [_scan_tuple(s) for s in d['scans']] == [(tuple(c), ss, se, ah, al) for c, ss, se, ah, al in pr.pillow_script('4:2:0')]
+    assert d['complete'] and d['progressive'] and d['interleaved'] and d['mode'] == '4:2:0'
+    for k in ('H', 'W', 'mode', 'components', 'interleaved', 'reference_grid', 'single_table', 'tq', 'sampling', 'grids',
+              'mcu', 'coeffs_needed'):
+        assert d[k] == b[k], k
+    assert np.array_equal(d['qtables'], b['qtables'])
+    # the tables are a property of the scan: Pillow redefines them between scans
+    offs = [s['ac_dht'][0] for s in d['scans'] if s['ss']]
+    assert len(set(offs)) == len(offs) and all(o > 0 for o in offs)
+    for s in d['scans']:
+        if s['ss'] == 0 and s['ah'] == 0:
+            assert all(o > 0 and prog[o] >> 4 == 0 and prog[o] & 15 == t for o, t in zip(s['dc_dht'], s['dc_tables']))
+        elif s['ss']:
+            assert prog[s['ac_dht'][0]] >> 4 == 1 and prog[s['ac_dht'][0]] & 15 == s['ac_tables'][0]
+            assert s['dc_dht'] == [-1]
+        else:
+            assert s['dc_dht'] == [-1, -1, -1] and s['ac_dht'] == [-1, -1, -1]
+        assert prog[s['offset'] - 3:s['offset']] == bytes([s['ss'], s['se'], s['ah'] << 4 | s['al']])
+        e = s['offset'] + s['length']
+        assert prog[e] == 0xFF and prog[e + 1] not in (0x00,) + tuple(range(0xD0, 0xD8))
+    # the bytes before the frame header are the baseline file's
+    assert prog[:prog.index(b'\xff\xc2')] == base[:base.index(b'\xff\xc0')]
+
+
+def test_parser_fields_on_pillows_gray_and_restart_files(E):
+    arr, prog, base, _ = pc.pillow_pair(24, 40, 'L', 0, 75)
+    d, b = E.parse_pjpeg(prog), E.parse_jpeg(base)
+    assert [_scan_tuple(s) for s in d['scans']] == [(tuple(c), ss, se, ah, al) for c, ss, se, ah, al in pr.pillow_script('gray')]
+    assert len(d['scans']) == 6 and d['mode'] == 'gray' and not d['interleaved'] and d['components'] == 1
+    for k in ('H', 'W', 'grids', 'mcu', 'coeffs_needed', 'sampling', 'tq'):
+        assert d[k] == b[k], k
+    arr, prog, base, _ = pc.pillow_pair(100, 75, 2, 1, 75)
+    d = E.parse_pjpeg(prog)
+    # libjpeg counts the rows in MCUs of each scan and writes a DRI whenever the count changes
+    assert b'\xff\xdd\x00\x04' in prog
+    for s in d['scans']:
+        row = d['mcu']['cols'] if len(s['components']) == 3 else d['grids'][s['components'][0] - 1][1]
+        assert s['restart_interval'] == row, s
+    assert prog[:prog.index(b'\xff\xc2')] == base[:base.index(b'\xff\xc0')]
+
+
+# ------------------------------------------------------------ 3. host model --
+
+@pytest.mark.parametrize('H,W,ss,rst,q', pc.PILLOW_PARAMS, ids=pc.PILLOW_IDS)
+def test_host_model_on_pillow_files(E, H, W, ss, rst, q):
+    prog = pc.pillow_pair(H, W, ss, rst, q)[1]
+    assert np.array_equal(E.host_decode_pjpeg(prog), pc.reference(prog))
+
+
+@pytest.mark.parametrize('H,W,mode,name', pc.SCRIPT_PARAMS, ids=pc.SCRIPT_IDS)
+def test_host_model_on_scripted_files(E, H, W, mode, name):
+    f, _, complete = pc.script_file(H, W, mode, name)
+    assert bool(E.parse_pjpeg(f)['complete']) == complete
+    assert np.array_equal(E.host_decode_pjpeg(f), pc.reference(f))
+
+
+def test_host_model_on_the_eobrun_file(E):
+    f, planar = pc.eobrun_file()
+    assert np.array_equal(E.host_decode_pjpeg(f), planar)
+
+
+def test_host_model_flags_every_hostile_file(E):
+    for name, f in pc.hostile_files().items():
+        E.parse_pjpeg(f)                                        # each parses: the defect is in the scan data
+        cf, st = E.host_decode_pjpeg(f, with_status=True)
+        assert st != 0, name
+        with pytest.raises(ValueError, match='defective scan data'):
+            E.host_decode_pjpeg(f)
+
+
+# -------------------------------------------------------------- 4. refusals --
+
+def _patch(f, E, scan, at, *values):
+    """Bytes from `at` on (negative: counted back from the scan's first data byte) of scan `scan`'s SOS."""
+    o = E.parse_pjpeg(f)['scans'][scan]['offset'] + at
+    return f[:o] + bytes(values) + f[o + len(values):]
+
+
+def test_refusals_by_name(E):
+    H, W, mode = 24, 40, '4:2:0'
+    p = pc.padded(H, W, mode)
+    good = pr.write(p, H, W, mode, pc.QT, pr.pillow_script(mode))
+    allc = (0, 1, 2)
+
+    def w(script, **kw):
+        return pr.write(p, H, W, mode, pc.QT, script, **kw)
+    with pytest.raises(ValueError, match=r'not progressive \(SOF0\): use the jpeg_\* calls'):
+        E.parse_pjpeg(pc.pillow_pair(40, 56, 2, 0, 75)[2])
+    with pytest.raises(ValueError, match='scan 1: refinement of coefficient 1 before its first pass'):
+        E.parse_pjpeg(w([(allc, 0, 0, 0, 0), ((0,), 1, 63, 1, 0)]))
+    with pytest.raises(ValueError, match='scan 1: Ah = 1 where coefficient 0 was last coded to Al = 2'):
+        E.parse_pjpeg(w([(allc, 0, 0, 0, 2), (allc, 0, 0, 1, 0)]))
+    with pytest.raises(ValueError, match='scan 0: AC scan with Ns = 3'):
+        E.parse_pjpeg(_patch(good, E, 0, -3, 1, 5))
+    with pytest.raises(ValueError, match=r'scan 1: spectral selection 6\.\.5'):
+        E.parse_pjpeg(_patch(good, E, 1, -3, 6))
+    with pytest.raises(ValueError, match='scan 0: successive approximation Al = 14'):
+        E.parse_pjpeg(_patch(good, E, 0, -1, 0x0E))
+    with pytest.raises(ValueError, match="scan 0: AC scan before the component's first DC scan"):
+        E.parse_pjpeg(w([((0,), 1, 63, 0, 0), (allc, 0, 0, 0, 0)]))
+    with pytest.raises(ValueError, match='scan 0: SOS refers to a Huffman table the file has not defined'):
+        E.parse_pjpeg(_patch(good, E, 0, -3 - 2 * 3 + 1, 0x30))
+    # 64 scans parse, a 65th is refused
+    g = [np.asarray(p[0])[:3, :5]]
+    s64 = [((0,), 0, 0, 0, 0)] + [((0,), k, k, 0, 0) for k in range(1, 64)]
+    assert len(E.parse_pjpeg(pr.write(g, H, W, 'gray', {0: pc.QT[0]}, s64))['scans']) == 64
+    s65 = [((0,), 0, 0, 0, 1)] + s64[1:] + [((0,), 0, 0, 1, 0)]
+    with pytest.raises(ValueError, match='more than 64 scans'):
+        E.parse_pjpeg(pr.write(g, H, W, 'gray', {0: pc.QT[0]}, s65))
+    # the baseline parser's other refusals stay refusals
+    sof = good.index(b'\xff\xc2')
+    for marker, pat in ((0xC1, 'SOF1'), (0xC3, 'SOF3'), (0xC9, 'arithmetic'), (0xCA, 'arithmetic')):
+        with pytest.raises(ValueError, match=pat):
+            E.parse_pjpeg(good[:sof + 1] + bytes([marker]) + good[sof + 2:])
+    with pytest.raises(ValueError, match='sample precision 12'):
+        E.parse_pjpeg(good[:sof + 4] + b'\x0c' + good[sof + 5:])
+    with pytest.raises(ValueError, match='16-bit DQT'):
+        q = good.index(b'\xff\xdb')
+        E.parse_pjpeg(good[:q + 4] + b'\x10' + good[q + 5:])
+
+
+def test_every_truncation_of_a_small_files_header_is_refused(E):
+    f = pc.pillow_pair(9, 9, 2, 0, 75)[1]
+    first = E.parse_pjpeg(f)['scans'][0]['offset']
+    for n in range(first + 1):
+        with pytest.raises(ValueError):
+            E.parse_pjpeg(f[:n])
+    for n in range(first + 1, len(f)):          # (and the rest of the file: never a crash, never accepted)
+        with pytest.raises(ValueError):
+            E.parse_pjpeg(f[:n])
+
+
+def test_the_existing_calls_still_refuse_progressive_files(E):
+    f = pc.pillow_pair(40, 56, 2, 0, 75)[1]
+    with pytest.raises(ValueError, match='progressive'):
+        E.parse_jpeg(f)
+    with pytest.raises(ValueError, match='progressive'):
+        E.parse_jfif(f)
+    from jds import codec
+    assert codec.is_progressive(f) and not codec.is_progressive(pc.pillow_pair(40, 56, 2, 0, 75)[2])
+    assert not codec.is_progressive(b'') and not codec.is_progressive(f[:10])
+
+
+# ------------------------------------------------------------------- 5. ABI --
+
+def test_pjpeg_struct_layout_matches_the_c_header_and_exports(E, tmp_path):
+    from jds import _abi
+    structs = {'jds_pjpeg_scan': _abi.PjpegScan, 'jds_pjpeg_info': _abi.PjpegInfo, 'jds_jpeg_info': _abi.JpegInfo}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "jds.h"', 'int main(void) {',
+             'printf("MAX %d\\n", JDS_PJPEG_MAX_SCANS);']
+    for cname, py in structs.items():
+        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
+        for fname, _ in py._fields_:
+            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
+    lines.append('return 0; }')
+    src = tmp_path / 'layout.c'
+    src.write_text('\n'.join(lines))
+    exe = tmp_path / 'layout'
+    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
+    got = dict(l.rsplit(' ', 1) for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split('\n') if l)
+    assert int(got['MAX']) == _abi.PJPEG_MAX_SCANS == 64
+    for cname, py in structs.items():
+        assert int(got[cname]) == C.sizeof(py), cname
+        for fname, _ in py._fields_:
+            assert int(got[f'{cname}.{fname}']) == getattr(py, fname).offset, (cname, fname)
+    hdr = open(os.path.join(ROOT, 'include', 'jds.h')).read()
+    names = sorted(set(re.findall(r'^\s*int\s+(jds_(?:selftest_)?pjpeg\w+)\s*\(', hdr, re.M)))
+    assert len(names) == 10, names
+    out = subprocess.run(['nm', '-D', '--defined-only', _abi.LIB_PATH], capture_output=True, text=True).stdout
+    exported = set(re.findall(r'\sT\s(jds_\w+)', out))
+    assert not [n for n in names if n not in exported]
+    assert all(n in _abi._SIGS for n in names)
+
+
+# ------------------------------------------------------------ 6. sanitizers --
+
+def build_pjpeg_san(tmp_path):
+    cxx = next((c for c in (shutil.which('g++'), shutil.which('clang++'), '/opt/rocm/lib/llvm/bin/clang++')
+                if c and os.path.exists(c)), None)
+    assert cxx, 'no host C++ compiler'
+    exe = tmp_path / 'pjpeg_san'
+    subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    '-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'jpeg-dsp-studio_amd', 'csrc'),
+                    os.path.join(ROOT, 'tools', 'pjpeg_san.cpp'), '-o', str(exe)], check=True)
+    return exe
+
+
+def run_pjpeg_san(exe, tmp_path, files, fuzz=False):
+    """{name: file} through the program -> {name: (rc, status)}."""
+    paths = []
+    for name, f in files.items():
+        pth = tmp_path / f'{name}.jpg'
+        pth.write_bytes(f)
+        paths.append(str(pth))
+    r = subprocess.run([str(exe)] + (['--fuzz'] if fuzz else []) + paths, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert r.stdout.rstrip().endswith('ok')
+    got = {}
+    for line in r.stdout.splitlines():
+        m = re.match(r'(\S+) rc=(-?\d+) status=0x([0-9a-f]+)$', line)
+        if m:
+            got[os.path.basename(m.group(1))[:-4]] = (int(m.group(2)), int(m.group(3), 16))
+    return got
+
+
+def test_parser_and_host_model_under_sanitizers(tmp_path):
+    """tools/pjpeg_san.cpp (its own main, no HIP, nothing loaded into Python) built with
+    -fsanitize=address,undefined: the valid files, the hostile ones, and one small file truncated
+    at every length and with every byte of its SOS headers and scan data substituted."""
+    exe = build_pjpeg_san(tmp_path)
+    valid = {f'pillow{i}': pc.pillow_pair(*prm)[1] for i, prm in enumerate(pc.PILLOW_PARAMS) if prm[4] == 75}
+    valid.update({f'script{i}': pc.script_file(*prm)[0] for i, prm in enumerate(pc.SCRIPT_PARAMS)})
+    got = run_pjpeg_san(exe, tmp_path, valid)
+    assert len(got) == len(valid) and all(v == (0, 0) for v in got.values()), got
+    hostile = pc.hostile_files()
+    got = run_pjpeg_san(exe, tmp_path, hostile)
+    assert len(got) == len(hostile) and all(rc == 0 and st != 0 for rc, st in got.values()), got
+    small = {'small_pillow': pc.pillow_pair(9, 9, 2, 0, 75)[1],
+             'small_rst': pr.write(pc.padded(17, 33, '4:4:4'), 17, 33, '4:4:4', pc.QT, pr.pillow_script('4:4:4'), ri=1)}
+    got = run_pjpeg_san(exe, tmp_path, small, fuzz=True)
+    assert all(v == (0, 0) for v in got.values()), got

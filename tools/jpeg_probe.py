@@ -48,7 +48,10 @@ jpeg_batch_to_tensor with the draft denominator and with scale_denom=1, see resi
 profiles/jpeg_resize_probe.json (or --out FILE).
 --encode N (default 64) instead: the way back, pixels to files: N 1080p pictures in a device tensor
 through rgb_batch_to_jpeg against N rgb_to_jpeg calls, see encode_main.  Writes
-profiles/jpeg_encode_probe.json (or --out FILE)."""
+profiles/jpeg_encode_probe.json (or --out FILE).
+--progressive N (default 64) instead: the pictures of --batch as progressive files through
+pjpeg_batch_to_rgb against their baseline twins through jpeg_batch_to_rgb and against Pillow on
+one core, see progressive_main.  Writes profiles/pjpeg_probe.json (or --out FILE)."""
 import io
 import json
 import os
@@ -803,7 +806,97 @@ def encode_main():
     return 0 if all(r['first_file_equals_pillow'] and r['batch_equals_single'] for r in rows) else 1
 
 
+def progressive_main():
+    """--progressive N: the N 1080p pictures of --batch saved by Pillow with progressive=True through
+    pjpeg_batch_to_rgb(out=tensor, render='libjpeg') against jpeg_batch_to_rgb(render='libjpeg') on
+    their baseline twins, the two legs alternating in one run (REPS rounds, default 5, after one
+    warm-up each; medians); k_pjpeg_chains from the context's launch marks (events) and, from the
+    walk times the kernel takes itself on a profiled context, the longest chain of the batch and
+    the scan kinds it spends its time in; Pillow's decode of the same N progressive files in a loop
+    on one core of this machine.  Writes profiles/pjpeg_probe.json (or --out FILE)."""
+    import torch
+    from jds import _abi
+    i = sys.argv.index('--progressive')
+    n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 64
+    H, W = int(os.environ.get('HEIGHT', '1080')), int(os.environ.get('WIDTH', '1920'))
+    reps = int(os.environ.get('REPS', '5'))
+    imgs = [np.random.default_rng(100 + k).integers(0, 256, (H, W, 3), dtype=np.uint8) for k in range(n)]
+    prog = [pillow_file(im, progressive=True) for im in imgs]
+    base = [pillow_file(im) for im in imgs]
+    _, rgb_bytes, _ = codec.jpeg_batch_layout(base)
+    out_p = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    out_b = torch.empty(rgb_bytes, dtype=torch.uint8, device='cuda')
+    ctx = _abi.Context(0)
+
+    def leg_p():
+        return codec.pjpeg_batch_to_rgb(prog, out=out_p, render='libjpeg', ctx=ctx)
+
+    def leg_b():
+        return codec.jpeg_batch_to_rgb(base, out=out_b, render='libjpeg', ctx=ctx)
+    vp, vb = leg_p(), leg_b()                                # (the warm-up of both legs)
+    torch.cuda.synchronize()
+    equal = all(bool(torch.equal(a, b)) for a, b in zip(vp, vb))
+    first_equals_pillow = bool(np.array_equal(vp[0].cpu().numpy(), np.asarray(Image.open(io.BytesIO(prog[0])).convert('RGB'))))
+    tp, tb = [], []
+    for _ in range(reps):                                    # alternating: both legs see the same machine
+        for fn, t in ((leg_p, tp), (leg_b, tb)):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e3)
+    ctx.profile(True)
+    leg_p()
+    kern, span = ctx.profile_read()
+    times = codec.pjpeg_scan_times(ctx, prog)
+    ctx.profile(False)
+    ctx.close()
+    kinds = {}
+    longest = (0.0, None)
+    for k, (f, per) in enumerate(zip(prog, times)):
+        scans = entropy.parse_pjpeg(f)['scans']
+        chains = {}
+        for j, us in per:
+            s = scans[j]
+            key = 'dc' if s['ss'] == 0 else 'ac%d' % s['components'][0]
+            kind = ('dc' if s['ss'] == 0 else 'ac') + ('_first' if s['ah'] == 0 else '_refine')
+            chains.setdefault(key, []).append((j, kind, s['ss'], s['se'], s['ah'], s['al'], us))
+            kinds[kind] = kinds.get(kind, 0.0) + us
+        for key, lst in chains.items():
+            tot = sum(x[-1] for x in lst)
+            if tot > longest[0]:
+                longest = (tot, {'file': k, 'chain': key, 'ms': tot / 1e3,
+                                 'scans': [{'scan': j, 'kind': kind, 'ss': ss, 'se': se, 'ah': ah, 'al': al, 'ms': us / 1e3}
+                                           for j, kind, ss, se, ah, al, us in lst]})
+    t0 = time.perf_counter()
+    for f in prog:
+        np.asarray(Image.open(io.BytesIO(f)).convert('RGB'))
+    pil_prog = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    for f in base:
+        np.asarray(Image.open(io.BytesIO(f)).convert('RGB'))
+    pil_base = (time.perf_counter() - t0) * 1e3
+    med = lambda t: sorted(t)[len(t) // 2]
+    row = {'leg': 'pillow_q50_420_1080p_progressive', 'n': n, 'H': H, 'W': W, 'reps': reps,
+           'progressive_bytes_total': int(sum(len(f) for f in prog)), 'baseline_bytes_total': int(sum(len(f) for f in base)),
+           'pjpeg_batch_to_rgb_ms': {'median': med(tp), 'min': min(tp), 'max': max(tp)},
+           'jpeg_batch_to_rgb_baseline_twins_ms': {'median': med(tb), 'min': min(tb), 'max': max(tb)},
+           'progressive_over_baseline': med(tp) / med(tb),
+           'kernels_ms_per_batch': {k: v[0] for k, v in kern.items()}, 'marks_span_ms_per_batch': span,
+           'k_pjpeg_chains_ms_events': kern.get('k_pjpeg_chains', [None])[0],
+           'longest_chain': longest[1], 'scan_kind_lane_ms_total': {k: v / 1e3 for k, v in kinds.items()},
+           'pillow_one_core_progressive_ms': pil_prog, 'pillow_one_core_baseline_ms': pil_base,
+           'chains_slower_than_pillow_one_core': bool(kern.get('k_pjpeg_chains', [0.0])[0] > pil_prog),
+           'progressive_equals_baseline_twins': equal, 'first_file_equals_pillow': first_equals_pillow}
+    print(json.dumps(row), flush=True)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'pjpeg_probe.json')
+    with open(out, 'w') as f:
+        json.dump([row], f, indent=1)
+        f.write('\n')
+    return 0 if equal and first_equals_pillow else 1
+
+
 def main():
+    if '--progressive' in sys.argv:
+        return progressive_main()
     if '--encode' in sys.argv:
         return encode_main()
     if '--resize' in sys.argv:
