@@ -46,7 +46,7 @@ int jds_jfif_parse(const uint8_t* data, int64_t len, jds_jfif_info* out) {
   return rc;
 }
 
-static int check_coef_cap(const int16_t* coeffs, int64_t cap, int64_t needed) {
+int check_coef_cap(const int16_t* coeffs, int64_t cap, int64_t needed) {
   if (!coeffs || cap < needed)
     return fail(JDS_EINVAL, "coefficient buffer too small: %lld entries needed", (long long)needed);
   return JDS_OK;
@@ -429,30 +429,105 @@ int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_
 // ------------------------------------------- batches of foreign files --
 // (DESIGN.md "Batches of foreign files")
 
-// What the layout keeps per batch: the parsed files, the inverse records of the
-// ones that take part (in batch order) and the tile maps of the four launches.
-struct BatchPlan {
-  std::vector<jds_jpeg_info> info;  // per file
-  std::vector<int> rec_of;          // per file: its record, or -1
-  std::vector<int> file_of;         // per record: its file
-  std::vector<JInvRec> recs;
-  std::vector<JInvMap> map[JI_MODES];          // the full-scale images
-  std::vector<JInvMap> smap[JI_MODES][LS_ND];  // the scaled ones, per denominator 2, 4, 8
-  bool any_scaled = false;
-  std::vector<int> denom;  // per file: the denominator it is decoded at
-  int64_t rgb_bytes = 0, coef_entries = 0;
-  int first_bad = -1;
-  char first_msg[400] = "";
+// The baseline front end of the batch driver (jds_abi_jpeg.hpp): either scan
+// form through the two decode groups and the restart-interval lanes.
+struct BaselineFront : BatchFront {
+  unsigned rounds = 0;  // the batch's propagation rounds, once it has run
+  int parse(int, const uint8_t* data, int64_t len, jds_jpeg_info* frame) override {
+    return jds_jpeg_parse(data, len, frame);
+  }
+  int check(int, const jds_jpeg_info* frame) override {
+    HuffDecTab t[4];
+    return dec_tables(frame->huff, t) ? JDS_OK : fail(JDS_EINVAL, "%s", DHT_OVERSUBSCRIBED);
+  }
+  // descriptors of both decode groups, lane intervals of both forms (a file's padded to whole workgroups)
+  std::vector<DecScan> sc_il, sc_pl;
+  std::vector<RstIv> iv_il, iv_pl;
+  std::vector<HuffDecTab> tabs;
+  std::vector<HdMcu> mcus;
+  long long ng_il = 0, ng_pl = 0;
+  int mx_il = 0, mx_pl = 0;
+  size_t scr_il = 0, o_tabs = 0, o_mcu = 0, o_ivil = 0, o_ivpl = 0;
+  int describe(BatchJob& j) override {
+    jds_ctx* c = j.c;
+    const BatchPlan& bp = j.bp;
+    const int nv = (int)bp.recs.size();
+    int lane_max;
+    rst_constants(&lane_max);
+    const int rst_g = rst_group_lanes();
+    tabs.resize(4 * (size_t)nv);
+    mcus.resize((size_t)nv);
+    long long dcs_n = 0;
+    for (int k = 0; k < nv; ++k) {
+      const int i = bp.file_of[(size_t)k];
+      const jds_jpeg_info& info = bp.info[(size_t)i];
+      (void)dec_tables(info.huff, &tabs[4 * (size_t)k]);  // (the layout checked them)
+      memset(&mcus[(size_t)k], 0, sizeof(HdMcu));
+      const FilePlace pl{k, (long long)j.foff[(size_t)k], bp.recs[(size_t)k].coef_off, dcs_n};
+      std::vector<DecScan>& sc = info.interleaved ? sc_il : sc_pl;
+      std::vector<RstIv>& iv = info.interleaved ? iv_il : iv_pl;
+      const size_t nsc0 = sc.size(), niv0 = iv.size();
+      if (info.interleaved) {
+        HdMcu m = hd_jpeg_mcu(&info);
+        for (int cc = 0; cc < 3; ++cc) m.off[cc] += pl.coef_off;
+        mcus[(size_t)k] = m;
+        dcs_n += (long long)m.bpm * m.mcu_cols * m.mcu_rows;
+      }
+      const DecJobsResult jr = dec_jobs_build(j.data[i], dec_jobs_of(&info), pl, lane_max, sc, iv, g_err, sizeof g_err);
+      if (jr == DEC_JOBS_MARKERS) {  // a defective scan, nothing of it is decoded
+        sc.resize(nsc0);
+        iv.resize(niv0);
+        j.st0[(size_t)k] = HD_RESTART;
+      } else if (jr) {
+        return JDS_ENOTSUP;
+      }
+      while (iv.size() % (size_t)rst_g) {
+        RstIv v{};
+        v.file = v.frame = k;
+        iv.push_back(v);
+      }
+    }
+    if (sc_il.size() > 0x7fffffffull || sc_pl.size() > 0x7fffffffull || iv_il.size() > 0x7fffffffull ||
+        iv_pl.size() > 0x7fffffffull)
+      return fail(JDS_ENOTSUP, "too many restart intervals");
+    ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
+    ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
+    if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
+    o_tabs = j.add(tabs);
+    o_mcu = j.add(mcus);
+    o_ivil = j.add(iv_il);
+    o_ivpl = j.add(iv_pl);
+    scr_il = (dec_scratch_bytes(ng_il, (int)sc_il.size()) + 255) & ~(size_t)255;
+    HIP_TRY(c->dec_scr.ensure(scr_il + dec_scratch_bytes(ng_pl, (int)sc_pl.size())));
+    HIP_TRY(c->dec_mcu.ensure(sizeof(int16_t) * (size_t)dcs_n));
+    HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)bp.coef_entries));
+    j.cf_d = (int16_t*)c->ent_cf.p;
+    j.zero_p = c->dec_mcu.p;  // the DC staging array of the interleaved scans
+    j.zero_n = sizeof(int16_t) * (size_t)dcs_n;
+    return JDS_OK;
+  }
+
+  int decode(BatchJob& j) override {
+    jds_ctx* c = j.c;
+    const uint8_t* files_d = j.dev<uint8_t>(0);
+    const HuffDecTab* tabs_d = j.dev<HuffDecTab>(o_tabs);
+    const HdMcu* mcu_d = j.dev<HdMcu>(o_mcu);
+    const DecGroup grp[2] = {{sc_il.data(), (int)sc_il.size(), ng_il, mx_il, c->dec_scr.p, true},
+                             {sc_pl.data(), (int)sc_pl.size(), ng_pl, mx_pl, (char*)c->dec_scr.p + scr_il, false}};
+    int too_many = 0;
+    HIP_TRY(dec_run_groups(files_d, grp, 2, tabs_d, j.cf_d, j.bp.coef_entries, j.st_d, j.s, &rounds, &too_many, mcu_d,
+                           (int16_t*)c->dec_mcu.p));
+    if (too_many)
+      return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
+    HIP_TRY(launch_dec_rst(files_d, j.dev<RstIv>(o_ivil), (long long)iv_il.size(), tabs_d, j.cf_d, j.st_d, j.s, mcu_d));
+    HIP_TRY(launch_dec_rst(files_d, j.dev<RstIv>(o_ivpl), (long long)iv_pl.size(), tabs_d, j.cf_d, j.st_d, j.s, nullptr));
+    return JDS_OK;
+  }
 };
 
-// Parse every file, check what the single call checks before it decodes, and
-// lay the outputs out: images JI_RGB_ALIGN apart at least, coefficients end to
-// end.  A file that fails takes no space and does not stop the batch.
-// draft (without denoms): {width, height} asked for; a file's denominator is
-// then the largest of 8, 4, 2, 1 that is at most min(W / width, H / height).
-static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items,
-                        BatchPlan& bp, int32_t render = JDS_RENDER_REFERENCE, const int32_t* denoms = nullptr,
-                        jds_jpeg_scaled_item* scaled = nullptr, const int64_t* draft = nullptr) {
+int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t n, jds_jpeg_batch_item* items, BatchPlan& bp,
+                 BatchFront& fe, int32_t render, const int32_t* denoms, jds_jpeg_scaled_item* scaled,
+                 const int64_t* draft) {
   if (n < 0 || (n > 0 && (!data || !lens || !items))) return fail(JDS_EINVAL, "null argument");
   for (int i = 0; denoms && i < n; ++i) {
     if (!ls_denom_ok(denoms[i])) return fail(JDS_EINVAL, "file %d: scale_denom %d is not 1, 2, 4 or 8", i, (int)denoms[i]);
@@ -472,7 +547,7 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
     jds_jpeg_info& info = bp.info[(size_t)i];
     JInvRec& r = parsed[(size_t)i];
     memset(&r, 0, sizeof r);
-    int rc = data[i] && lens[i] >= 0 ? jds_jpeg_parse(data[i], lens[i], &info) : fail(JDS_EINVAL, "null file");
+    int rc = data[i] && lens[i] >= 0 ? fe.parse(i, data[i], lens[i], &info) : fail(JDS_EINVAL, "null file");
     if (rc == JDS_OK) {
       it.H = info.H;
       it.W = info.W;
@@ -480,10 +555,7 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
       it.interleaved = info.interleaved;
       rc = jpeg_inv_args(&info, &r.a);
     }
-    if (rc == JDS_OK) {
-      HuffDecTab t[4];
-      if (!dec_tables(info.huff, t)) rc = fail(JDS_EINVAL, "%s", DHT_OVERSUBSCRIBED);
-    }
+    if (rc == JDS_OK) rc = fe.check(i, &info);
     it.rc = rc;
     if (rc != JDS_OK) msg[(size_t)i] = g_err;
   });
@@ -492,10 +564,7 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
     const jds_jpeg_info& info = bp.info[(size_t)i];
     JInvRec& r = parsed[(size_t)i];
     if (it.rc != JDS_OK) {
-      if (bp.first_bad < 0) {
-        bp.first_bad = i;
-        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", msg[(size_t)i].c_str());
-      }
+      bp.bad(i, msg[(size_t)i].c_str());
       continue;
     }
     long long rb = bp.rgb_bytes, ce = bp.coef_entries;
@@ -531,12 +600,11 @@ static int batch_layout(const uint8_t* const* data, const int64_t* lens, int32_t
   return JDS_OK;
 }
 
-// The first failing file by index, where jds_last_error finds it.
-static void batch_note(const BatchPlan& bp) {
-  if (bp.first_bad >= 0) {
+void batch_note(const BatchBad& b, const char* what) {
+  if (b.first_bad >= 0) {
     char m[400];
-    snprintf(m, sizeof m, "%s", bp.first_msg);
-    fail(0, "file %d: %s", bp.first_bad, m);
+    snprintf(m, sizeof m, "%s", b.first_msg);
+    fail(0, "%s %d: %s", what, b.first_bad, m);
   } else {
     g_err[0] = 0;
   }
@@ -552,7 +620,8 @@ int jds_jpeg_batch_layout_scaled(const uint8_t* const* data, const int64_t* lens
                                  const int32_t* scale_denoms, jds_jpeg_scaled_item* scaled) {
   if (!rgb_bytes || !coef_entries) return fail(JDS_EINVAL, "null argument");
   BatchPlan bp;
-  const int rc = batch_layout(data, lens, n, items, bp, JDS_RENDER_LIBJPEG, scale_denoms, scaled);
+  BaselineFront fe;
+  const int rc = batch_layout(data, lens, n, items, bp, fe, JDS_RENDER_LIBJPEG, scale_denoms, scaled);
   if (rc) return rc;
   *rgb_bytes = bp.rgb_bytes;
   *coef_entries = bp.coef_entries;
@@ -580,7 +649,8 @@ int jds_selftest_jpeg_batch_render_scaled(const uint8_t* const* data, const int6
   if ((rc = render_check(render))) return rc;
   if (subseq_bits < 64 || subseq_bits % 8) return fail(JDS_EINVAL, "subseq_bits must be a multiple of 8, at least 64");
   BatchPlan bp;
-  rc = batch_layout(data, lens, n, items, bp, render, scale_denoms, scaled);
+  BaselineFront fe;
+  rc = batch_layout(data, lens, n, items, bp, fe, render, scale_denoms, scaled);
   if (rc) return rc;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
     return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
@@ -622,158 +692,80 @@ int jds_selftest_jpeg_batch_render_scaled(const uint8_t* const* data, const int6
   return JDS_OK;
 }
 
-// The launches of a laid-out batch with at least one record: upload, entropy
-// decode into c->ent_cf (file k's coefficients at bp.recs[k].coef_off), then
-// with `inverse` the batch inverse into rgb; the status words into items.
-// Synchronous.  Without `inverse` (jds_jpeg_batch_transcode) rgb is not used.
-// after (nullable): called with the device status words once the rendering is
-// in the stream, for work that follows it there.
-static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
-                     int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, uint32_t* rounds_out,
-                     bool inverse, int32_t render = JDS_RENDER_REFERENCE,
-                     const std::function<int(const uint32_t*, hipStream_t)>* after = nullptr) {
+int batch_run(jds_ctx* c, BatchPlan& bp, BatchFront& fe, const uint8_t* const* data, const int64_t* lens, uint8_t* rgb,
+              int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, bool inverse, int32_t render,
+              const std::function<int(const uint32_t*, hipStream_t)>* after) {
   const int nv = (int)bp.recs.size();
   hipStream_t s = c->stream;
   HIP_TRY(hipSetDevice(c->device));
-  int lane_max;
-  rst_constants(&lane_max);
-  const int rst_g = rst_group_lanes();
-  // the upload: every part at a 256-byte boundary, files at 16-byte ones inside theirs
-  auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
-  std::vector<size_t> foff((size_t)nv);
+  BatchJob j{c, s, bp, data};
+  // the upload: the files (at 16-byte boundaries inside their section), the decode's descriptors,
+  // the inverse records, the tile maps of every launch, the status words
+  j.foff.resize((size_t)nv);
   size_t o = 0;
   for (int k = 0; k < nv; ++k) {
-    foff[(size_t)k] = o;
-    o = up(o + (size_t)lens[bp.file_of[(size_t)k]], 16);
+    j.foff[(size_t)k] = o;
+    o = (o + (size_t)lens[bp.file_of[(size_t)k]] + 15) / 16 * 16;
   }
-  // descriptors of both decode groups, lane intervals of both forms (a file's padded to whole workgroups)
-  std::vector<DecScan> sc_il, sc_pl;
-  std::vector<RstIv> iv_il, iv_pl;
-  std::vector<HuffDecTab> tabs(4 * (size_t)nv);
-  std::vector<HdMcu> mcus((size_t)nv);
-  std::vector<uint32_t> st0((size_t)nv, 0u);
-  long long dcs_n = 0;
-  for (int k = 0; k < nv; ++k) {
-    const int i = bp.file_of[(size_t)k];
-    const jds_jpeg_info& info = bp.info[(size_t)i];
-    (void)dec_tables(info.huff, &tabs[4 * (size_t)k]);  // (the layout checked them)
-    memset(&mcus[(size_t)k], 0, sizeof(HdMcu));
-    const FilePlace pl{k, (long long)foff[(size_t)k], bp.recs[(size_t)k].coef_off, dcs_n};
-    std::vector<DecScan>& sc = info.interleaved ? sc_il : sc_pl;
-    std::vector<RstIv>& iv = info.interleaved ? iv_il : iv_pl;
-    const size_t nsc0 = sc.size(), niv0 = iv.size();
-    if (info.interleaved) {
-      HdMcu m = hd_jpeg_mcu(&info);
-      for (int cc = 0; cc < 3; ++cc) m.off[cc] += pl.coef_off;
-      mcus[(size_t)k] = m;
-      dcs_n += (long long)m.bpm * m.mcu_cols * m.mcu_rows;
-    }
-    const DecJobsResult jr = dec_jobs_build(data[i], dec_jobs_of(&info), pl, lane_max, sc, iv, g_err, sizeof g_err);
-    if (jr == DEC_JOBS_MARKERS) {  // a defective scan, nothing of it is decoded
-      sc.resize(nsc0);
-      iv.resize(niv0);
-      st0[(size_t)k] = HD_RESTART;
-    } else if (jr) {
-      return JDS_ENOTSUP;
-    }
-    while (iv.size() % (size_t)rst_g) {
-      RstIv v{};
-      v.file = v.frame = k;
-      iv.push_back(v);
-    }
-  }
-  if (sc_il.size() > 0x7fffffffull || sc_pl.size() > 0x7fffffffull || iv_il.size() > 0x7fffffffull ||
-      iv_pl.size() > 0x7fffffffull)
-    return fail(JDS_ENOTSUP, "too many restart intervals");
-  int mx_il = 0, mx_pl = 0;
-  const long long ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
-  const long long ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
-  if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
-  int map_off[JI_MODES], nmap[JI_MODES], tiles[JI_MODES], nm = 0;
+  j.add(nullptr, o);  // (at 0)
+  j.files_bytes = (long long)j.total;
+  j.st0.assign((size_t)nv, 0u);
+  int rc;
+  if ((rc = fe.describe(j))) return rc;
+  std::vector<JInvMap> maps;
+  int map_off[JI_MODES], nmap[JI_MODES], tiles[JI_MODES];
   for (int m = 0; m < JI_MODES; ++m) {
-    map_off[m] = nm;
+    map_off[m] = (int)maps.size();
     nmap[m] = (int)bp.map[m].size() - 1;
     tiles[m] = bp.map[m].back().tile0;
-    nm += (int)bp.map[m].size();
+    maps.insert(maps.end(), bp.map[m].begin(), bp.map[m].end());
   }
   int smap_off[JI_MODES][LS_ND], nsmap[JI_MODES][LS_ND], stiles[JI_MODES][LS_ND];
   for (int m = 0; m < JI_MODES; ++m)
     for (int d = 0; d < LS_ND; ++d) {  // (a batch without scaled images uploads what it always did)
-      smap_off[m][d] = nm;
+      smap_off[m][d] = (int)maps.size();
       nsmap[m][d] = bp.any_scaled ? (int)bp.smap[m][d].size() - 1 : 0;
       stiles[m][d] = bp.any_scaled ? bp.smap[m][d].back().tile0 : 0;
-      if (bp.any_scaled) nm += (int)bp.smap[m][d].size();
+      if (bp.any_scaled) maps.insert(maps.end(), bp.smap[m][d].begin(), bp.smap[m][d].end());
     }
-  const size_t o_files = 0, o_tabs = up(o, 256), o_mcu = up(o_tabs + sizeof(HuffDecTab) * tabs.size(), 256),
-               o_rec = up(o_mcu + sizeof(HdMcu) * mcus.size(), 256), o_map = up(o_rec + sizeof(JInvRec) * (size_t)nv, 256),
-               o_ivil = up(o_map + sizeof(JInvMap) * (size_t)nm, 256), o_ivpl = up(o_ivil + sizeof(RstIv) * iv_il.size(), 256),
-               o_st = up(o_ivpl + sizeof(RstIv) * iv_pl.size(), 256), total = up(o_st + 4 * (size_t)nv, 256);
-  if (total > c->bat_host_cap) {
+  const size_t o_rec = j.add(bp.recs), o_map = j.add(maps), o_st = j.add(j.st0);
+  if (j.total > c->bat_host_cap) {  // the staging buffer and its device copy, grown to the upload's size
     if (c->bat_host) (void)hipHostFree(c->bat_host);
     c->bat_host = nullptr;
     c->bat_host_cap = 0;
-    HIP_TRY(hipHostMalloc(&c->bat_host, total, hipHostMallocDefault));
-    c->bat_host_cap = total;
+    HIP_TRY(hipHostMalloc(&c->bat_host, j.total, hipHostMallocDefault));
+    c->bat_host_cap = j.total;
   }
+  HIP_TRY(c->bat.ensure(j.total));
   char* h = (char*)c->bat_host;
+  for (const BatchJob::Part& p : j.parts)
+    if (p.src && p.bytes) memcpy(h + p.off, p.src, p.bytes);
   batch_parallel(nv, [&](int k) {
     const int i = bp.file_of[(size_t)k];
-    memcpy(h + o_files + foff[(size_t)k], data[i], (size_t)lens[i]);
+    memcpy(h + j.foff[(size_t)k], data[i], (size_t)lens[i]);
   });
-  memcpy(h + o_tabs, tabs.data(), sizeof(HuffDecTab) * tabs.size());
-  memcpy(h + o_mcu, mcus.data(), sizeof(HdMcu) * mcus.size());
-  memcpy(h + o_rec, bp.recs.data(), sizeof(JInvRec) * (size_t)nv);
-  for (int m = 0; m < JI_MODES; ++m)
-    memcpy(h + o_map + sizeof(JInvMap) * (size_t)map_off[m], bp.map[m].data(), sizeof(JInvMap) * bp.map[m].size());
-  for (int m = 0; bp.any_scaled && m < JI_MODES; ++m)
-    for (int d = 0; d < LS_ND; ++d)
-      memcpy(h + o_map + sizeof(JInvMap) * (size_t)smap_off[m][d], bp.smap[m][d].data(),
-             sizeof(JInvMap) * bp.smap[m][d].size());
-  if (!iv_il.empty()) memcpy(h + o_ivil, iv_il.data(), sizeof(RstIv) * iv_il.size());
-  if (!iv_pl.empty()) memcpy(h + o_ivpl, iv_pl.data(), sizeof(RstIv) * iv_pl.size());
-  memcpy(h + o_st, st0.data(), 4 * (size_t)nv);
-  const size_t scr_il = (dec_scratch_bytes(ng_il, (int)sc_il.size()) + 255) & ~(size_t)255;
-  HIP_TRY(c->bat.ensure(total));
-  HIP_TRY(c->dec_scr.ensure(scr_il + dec_scratch_bytes(ng_pl, (int)sc_pl.size())));
-  HIP_TRY(c->dec_mcu.ensure(sizeof(int16_t) * (size_t)dcs_n));
-  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)bp.coef_entries));
   uint8_t* dst = rgb;
   if (inverse && !rgb_on_device) {
     HIP_TRY(c->out.ensure((size_t)bp.rgb_bytes));
     dst = (uint8_t*)c->out.p;
   }
-  char* dv = (char*)c->bat.p;
+  j.dv = (char*)c->bat.p;
+  j.st_d = (uint32_t*)(j.dv + o_st);
   const CtxMarkScope marks_(c, s);
-  HIP_TRY(hipMemcpyAsync(dv, h, total, hipMemcpyHostToDevice, s));
-  if (dcs_n) HIP_TRY(hipMemsetAsync(c->dec_mcu.p, 0, sizeof(int16_t) * (size_t)dcs_n, s));
+  HIP_TRY(hipMemcpyAsync(j.dv, h, j.total, hipMemcpyHostToDevice, s));
+  if (j.zero_n) HIP_TRY(hipMemsetAsync(j.zero_p, 0, j.zero_n, s));
   kmark(s, "(batch upload)");
-  const uint8_t* files_d = (const uint8_t*)(dv + o_files);
-  const HuffDecTab* tabs_d = (const HuffDecTab*)(dv + o_tabs);
-  const HdMcu* mcu_d = (const HdMcu*)(dv + o_mcu);
-  uint32_t* st_d = (uint32_t*)(dv + o_st);
-  int16_t* cf_d = (int16_t*)c->ent_cf.p;
-  const DecGroup grp[2] = {{sc_il.data(), (int)sc_il.size(), ng_il, mx_il, c->dec_scr.p, true},
-                           {sc_pl.data(), (int)sc_pl.size(), ng_pl, mx_pl, (char*)c->dec_scr.p + scr_il, false}};
-  unsigned rounds = 0;
-  int too_many = 0;
-  HIP_TRY(dec_run_groups(files_d, grp, 2, tabs_d, cf_d, bp.coef_entries, st_d, s, &rounds, &too_many, mcu_d,
-                         (int16_t*)c->dec_mcu.p));
-  if (too_many)
-    return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", mx_il > mx_pl ? mx_il : mx_pl);
-  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivil), (long long)iv_il.size(), tabs_d, cf_d, st_d, s, mcu_d));
-  HIP_TRY(launch_dec_rst(files_d, (const RstIv*)(dv + o_ivpl), (long long)iv_pl.size(), tabs_d, cf_d, st_d, s, nullptr));
+  if ((rc = fe.decode(j))) return rc;
+  const JInvRec* rec_d = j.dev<JInvRec>(o_rec);
+  const JInvMap* map_d = j.dev<JInvMap>(o_map);
   if (inverse && render == JDS_RENDER_LIBJPEG)
-    HIP_TRY(launch_jpeg_ljt_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
-                                  st_d, cf_d, dst, s));
+    HIP_TRY(launch_jpeg_ljt_batch(rec_d, map_d, map_off, nmap, tiles, j.st_d, j.cf_d, dst, s));
   else if (inverse)
-    HIP_TRY(launch_jpeg_inv_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), map_off, nmap, tiles,
-                                  st_d, cf_d, dst, s));
+    HIP_TRY(launch_jpeg_inv_batch(rec_d, map_d, map_off, nmap, tiles, j.st_d, j.cf_d, dst, s));
   if (inverse && bp.any_scaled)
-    HIP_TRY(launch_jpeg_ljs_batch((const JInvRec*)(dv + o_rec), (const JInvMap*)(dv + o_map), smap_off, nsmap, stiles,
-                                  st_d, cf_d, dst, s));
+    HIP_TRY(launch_jpeg_ljs_batch(rec_d, map_d, smap_off, nsmap, stiles, j.st_d, j.cf_d, dst, s));
   if (after) {  // (jds_jpeg_batch_to_tensor: the resize behind the rendering, on the same stream)
-    const int rc = (*after)(st_d, s);
-    if (rc) return rc;
+    if ((rc = (*after)(j.st_d, s))) return rc;
   }
   if (inverse && !rgb_on_device)  // image by image: the gaps of the caller's buffer stay as they are
     for (int k = 0; k < nv; ++k) {
@@ -783,12 +775,11 @@ static int batch_run(jds_ctx* c, BatchPlan& bp, const uint8_t* const* data, cons
       HIP_TRY(hipMemcpyAsync(rgb + r.rgb_off, dst + r.rgb_off, (size_t)oh * (size_t)ow * 3, hipMemcpyDeviceToHost, s));
     }
   if (coeffs)
-    HIP_TRY(hipMemcpyAsync(coeffs, cf_d, sizeof(int16_t) * (size_t)bp.coef_entries, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(st0.data(), st_d, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(coeffs, j.cf_d, sizeof(int16_t) * (size_t)bp.coef_entries, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(j.st0.data(), j.st_d, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
   kmark(s, "(batch download)");
   HIP_TRY(hipStreamSynchronize(s));
-  for (int k = 0; k < nv; ++k) items[bp.file_of[(size_t)k]].status = st0[(size_t)k];
-  if (rounds_out) *rounds_out = rounds;
+  for (int k = 0; k < nv; ++k) items[bp.file_of[(size_t)k]].status = j.st0[(size_t)k];
   return JDS_OK;
 }
 
@@ -814,14 +805,15 @@ int jds_jpeg_batch_to_rgb_scaled(jds_ctx* c, const uint8_t* const* data, const i
   if ((rc = render_check(render))) return rc;
   if (!c) return fail(JDS_EINVAL, "null argument");
   BatchPlan bp;
-  rc = batch_layout(data, lens, n, items, bp, render, scale_denoms, scaled);
+  BaselineFront fe;
+  rc = batch_layout(data, lens, n, items, bp, fe, render, scale_denoms, scaled);
   if (rc) return rc;
   if (rounds_out) *rounds_out = 0;
   if (bp.rgb_bytes > 0 && (!rgb || rgb_cap < bp.rgb_bytes))
     return fail(JDS_EINVAL, "image buffer too small: %lld bytes needed", (long long)bp.rgb_bytes);
-  if (!bp.recs.empty() &&
-      (rc = batch_run(c, bp, data, lens, rgb, rgb_on_device, coeffs, items, rounds_out, true, render)))
+  if (!bp.recs.empty() && (rc = batch_run(c, bp, fe, data, lens, rgb, rgb_on_device, coeffs, items, true, render)))
     return rc;
+  if (rounds_out) *rounds_out = fe.rounds;
   batch_note(bp);
   return JDS_OK;
 }
@@ -840,7 +832,8 @@ int jds_jpeg_batch_to_tensor(jds_ctx* c, const uint8_t* const* data, const int64
     return fail(JDS_ENOTSUP, "image too large: more than 2^31 - 1 bytes");
   const int64_t slot = out_h * out_w * 3, draft[2] = {out_w, out_h};
   BatchPlan bp;
-  int rc = batch_layout(data, lens, n, items, bp, JDS_RENDER_LIBJPEG, scale_denoms, scaled, draft);
+  BaselineFront fe;
+  int rc = batch_layout(data, lens, n, items, bp, fe, JDS_RENDER_LIBJPEG, scale_denoms, scaled, draft);
   if (rc) return rc;
   if (rounds_out) *rounds_out = 0;
   if (n > 0 && (!out || out_cap < slot * n))
@@ -882,8 +875,8 @@ int jds_jpeg_batch_to_tensor(jds_ctx* c, const uint8_t* const* data, const int64
     return JDS_OK;
   };
   if (!bp.recs.empty()) {
-    rc = batch_run(c, bp, data, lens, (uint8_t*)c->rsz_src.p, 1, nullptr, items, rounds_out, true, JDS_RENDER_LIBJPEG,
-                   &after);
+    rc = batch_run(c, bp, fe, data, lens, (uint8_t*)c->rsz_src.p, 1, nullptr, items, true, JDS_RENDER_LIBJPEG, &after);
+    if (rc == JDS_OK && rounds_out) *rounds_out = fe.rounds;
   } else if (n > 0) {  // no file decodes: every slot is zeros
     rc = after(nullptr, c->stream);
     if (rc == JDS_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(JDS_EHIP, "hipStreamSynchronize");
@@ -911,7 +904,7 @@ int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j) {
   return JDS_OK;
 }
 
-static int mcu_job_splice(const uint8_t* data, int64_t len, McuJob* j) {
+int mcu_job_splice(const uint8_t* data, int64_t len, McuJob* j) {
   const int64_t n = mcu_splice(data, len, nullptr, 0);
   if (n < 0 || n > 0x7fffffffll) return fail(JDS_EINVAL, "header splice: no marker sequence from SOI to an SOS");
   j->pfx.resize((size_t)n);
@@ -1210,7 +1203,8 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
   *out_bytes = 0;
   std::vector<jds_jpeg_batch_item> bi((size_t)(n > 0 ? n : 0));
   BatchPlan bp;
-  int rc = batch_layout(data, lens, n, bi.data(), bp);
+  BaselineFront fe;
+  int rc = batch_layout(data, lens, n, bi.data(), bp, fe);
   if (rc) return rc;
   // the transformed planes follow the decoder's in c->ent_cf: sized before the decode fills it
   std::vector<XfJob> xj((size_t)(xform && n > 0 ? n : 0));
@@ -1222,10 +1216,7 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
     const int rc1 = xf_prepare(data[i], lens[i], &bp.info[(size_t)i], ops ? ops[i] : JDS_XF_AUTO, &x);
     if (rc1) {  // refused: an item error with the code the file would get alone
       bi[(size_t)i].rc = rc1;
-      if (bp.first_bad < 0 || i < bp.first_bad) {
-        bp.first_bad = i;
-        snprintf(bp.first_msg, sizeof bp.first_msg, "%s", g_err);
-      }
+      bp.bad(i, g_err);
       continue;
     }
     bi[(size_t)i].H = x.plan.dst.H;
@@ -1236,8 +1227,36 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(xbase + xtotal)));
   }
-  if (!bp.recs.empty() && (rc = batch_run(c, bp, data, lens, nullptr, 0, nullptr, bi.data(), nullptr, false)))
-    return rc;
+  if (!bp.recs.empty() && (rc = batch_run(c, bp, fe, data, lens, nullptr, 0, nullptr, bi.data(), false))) return rc;
+  XfSet xs;
+  int64_t xcur = xbase;
+  return batch_transcode_tail(
+      c, bp, bi, n,
+      [&](size_t k, int i, McuJob* j) {
+        int r;
+        if (xform && xj[(size_t)i].op != JDS_XF_NONE) {  // the writer sees the destination planes
+          XfJob& x = xj[(size_t)i];
+          if ((r = mcu_job_geo(&x.plan.dst, xcur, j))) return r;
+          XfFile rec = x.plan.rec;
+          for (int cc = 0; cc < 3; ++cc) {
+            rec.soff[cc] += bp.recs[k].coef_off;
+            rec.doff[cc] += xcur;
+          }
+          xs.add(rec);
+          xcur += xf_align(x.plan.dst.coeffs_needed);
+          j->pfx = std::move(x.pfx);
+          return JDS_OK;
+        }
+        if ((r = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, j))) return r;
+        return mcu_job_splice(data[i], lens[i], j);
+      },
+      &xs, optimize, out, out_cap, out_on_device, items, out_bytes);
+}
+
+int batch_transcode_tail(jds_ctx* c, BatchPlan& bp, const std::vector<jds_jpeg_batch_item>& bi, int32_t n,
+                         const std::function<int(size_t, int, McuJob*)>& job_of, const XfSet* xf, int32_t optimize,
+                         uint8_t* out, int64_t out_cap, int32_t out_on_device, jds_jpeg_transcode_item* items,
+                         int64_t* out_bytes) {
   for (int i = 0; i < n; ++i) {
     jds_jpeg_transcode_item& it = items[i];
     memset(&it, 0, sizeof it);
@@ -1252,43 +1271,21 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
   // the files that decoded take part in the writer's launches
   std::vector<McuJob> jobs;
   std::vector<int> job_file;
-  XfSet xs;
-  int64_t xcur = xbase;
+  int rc;
   for (size_t k = 0; k < bp.recs.size(); ++k) {
     const int i = bp.file_of[k];
     if (items[i].status || items[i].rc) continue;
     McuJob j;
-    if (xform && xj[(size_t)i].op != JDS_XF_NONE) {  // the writer sees the destination planes
-      XfJob& x = xj[(size_t)i];
-      if ((rc = mcu_job_geo(&x.plan.dst, xcur, &j))) return rc;
-      XfFile rec = x.plan.rec;
-      for (int cc = 0; cc < 3; ++cc) {
-        rec.soff[cc] += bp.recs[k].coef_off;
-        rec.doff[cc] += xcur;
-      }
-      xs.add(rec);
-      xcur += xf_align(x.plan.dst.coeffs_needed);
-      j.pfx = std::move(x.pfx);
-    } else {
-      if ((rc = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, &j))) return rc;
-      if ((rc = mcu_job_splice(data[i], lens[i], &j))) return rc;
-    }
+    if ((rc = job_of(k, i, &j))) return rc;
     jobs.push_back(std::move(j));
     job_file.push_back(i);
   }
-  if (jobs.empty()) {
-    batch_note(bp);
-    return JDS_OK;
+  if (!jobs.empty()) {
+    const CtxMarkScope marks_(c, c->stream);
+    rc = mcu_write_batch(c, jobs, job_file, optimize, xf && !xf->files.empty() ? xf : nullptr, out, out_cap, out_on_device,
+                         items, out_bytes, [&](int i, const char* m) { bp.bad(i, m); });
+    if (rc) return rc;
   }
-  const CtxMarkScope marks_(c, c->stream);
-  rc = mcu_write_batch(c, jobs, job_file, optimize, xs.files.empty() ? nullptr : &xs, out, out_cap, out_on_device, items,
-                       out_bytes, [&](int i, const char* m) {
-                         if (bp.first_bad < 0 || i < bp.first_bad) {
-                           bp.first_bad = i;
-                           snprintf(bp.first_msg, sizeof bp.first_msg, "%s", m);
-                         }
-                       });
-  if (rc) return rc;
   batch_note(bp);
   return JDS_OK;
 }
@@ -1577,19 +1574,10 @@ int jds_rgb_batch_to_jpeg(jds_ctx* c, const uint8_t* rgb_base, int32_t rgb_on_de
                           jds_jpeg_transcode_item* items, int64_t* out_bytes) {
   if (!c || !out_bytes || n < 0 || (n > 0 && (!items_in || !items || !rgb_base))) return fail(JDS_EINVAL, "null argument");
   *out_bytes = 0;
-  int first_bad = -1;
-  char first_msg[400] = "";
-  auto note = [&](int i, const char* m) {
-    if (first_bad < 0 || i < first_bad) {
-      first_bad = i;
-      snprintf(first_msg, sizeof first_msg, "%s", m);
-    }
-  };
+  BatchBad first;
+  auto note = [&](int i, const char* m) { first.bad(i, m); };
   auto finish = [&]() {
-    if (first_bad >= 0)
-      fail(0, "image %d: %s", first_bad, first_msg);
-    else
-      g_err[0] = 0;
+    batch_note(first, "image");
     return JDS_OK;
   };
   // the images that take part: records in batch order, coefficients end to end

@@ -56,172 +56,271 @@ inline int hd_block_counts(int64_t H, int64_t W, int mode, int64_t* ny, int64_t*
 // parser, two profiles").
 enum HdProfile { HD_ANY, HD_OWN };
 
-// The marker walk: SOI, segments up to EOI, with or without restart intervals.
-// Never reads outside [data, data + len).  Where a segment has two defects the
-// order of its checks decides which one is reported, and the two profiles'
-// orders differ on purpose (each keeps its own messages and return codes).
+// ---- the pieces of a marker walk, shared by the baseline walk (hd_walk) and
+// the progressive one (hd_pjpeg_parse, jds_pjpeg_parse.hpp): each check and its
+// message is written once.  None reads outside [data, data + len).
+struct HdWalk {
+  const uint8_t* data;
+  int64_t len;
+  char* msg;
+  size_t cap;
+  int64_t p = 2;  // where the next segment is looked for (an SOS moves it behind its scan data)
+  int m = 0;  // the segment at hand: marker FF m, payload s[0 .. sl)
+  int64_t sl = 0;
+  const uint8_t* s = nullptr;
+  uint8_t qt[4][64];  // DQT: the tables as written (zig-zag order), and which are defined
+  bool qdef[4] = {false, false, false, false};
+  int ri = 0;  // the restart interval in effect (DRI), 0: none
+  bool sof = false;
+  int ncomp = 3, gray_id = 0;  // a one-component frame: its component id as written (the SOS must name it)
+  template <class... A>
+  int fail(int code, const char* fmt, A... a) const {
+    return hd_fail(msg, cap, code, fmt, a...);
+  }
+};
+
+// The next segment a walk has to look at: a frame header (SOFn), DHT, SOS, or
+// EOI (m = 0xD9, no payload).  Fill bytes are passed over, DRI and DQT taken in,
+// APPn, COM and anything else with a length skipped.
+inline int hd_next(HdWalk& w) {
+  const uint8_t* data = w.data;
+  for (int64_t p = w.p;;) {
+    if (p + 2 > w.len) return w.fail(JDS_EINVAL, "truncated file: EOI missing");
+    if (data[p] != 0xFF) return w.fail(JDS_EINVAL, "marker expected at byte %lld", (long long)p);
+    const int m = w.m = data[p + 1];
+    if (m == 0xFF) {  // fill byte
+      ++p;
+      continue;
+    }
+    if (m == 0xD9) return JDS_OK;
+    if (m >= 0xD0 && m <= 0xD7)
+      return w.fail(JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
+    if (m == 0xD8 || m == 0x01 || m == 0x00)
+      return w.fail(JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
+    if (p + 4 > w.len) return w.fail(JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
+    const int64_t ln = ((int64_t)data[p + 2] << 8) | data[p + 3];
+    if (ln < 2 || p + 2 + ln > w.len)
+      return w.fail(JDS_EINVAL, "segment 0x%02X at byte %lld: length %lld reaches past the end of the file", m,
+                     (long long)p, (long long)ln);
+    const uint8_t* s = w.s = data + p + 4;
+    const int64_t sl = w.sl = ln - 2;
+    w.p = p = p + 2 + ln;
+    if ((m >= 0xC0 && m <= 0xCF && m != 0xC8) || m == 0xDA) return JDS_OK;
+    if (m == 0xDD) {
+      if (ln != 4) return w.fail(JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
+      w.ri = (s[0] << 8) | s[1];
+    }
+    for (int64_t q = 0; m == 0xDB && q < sl; q += 65) {
+      const int pq = s[q] >> 4, id = s[q] & 15;
+      if (pq == 1) return w.fail(JDS_ENOTSUP, "16-bit DQT is not supported");
+      if (pq != 0 || id > 3) return w.fail(JDS_EINVAL, "bad DQT table header 0x%02X", s[q]);
+      if (q + 65 > sl) return w.fail(JDS_EINVAL, "truncated DQT");
+      memcpy(w.qt[id], s + q + 1, 64);
+      w.qdef[id] = true;
+    }
+  }
+}
+
+// The frame header at hand, `name` ("SOF0", "SOF2") in its messages, into out:
+// size, subsampling, tq, hs, vs, the grids, coeffs_needed, single_table,
+// blocks_per_mcu, the MCU grid and reference_grid; w.ncomp and w.gray_id.
+inline int hd_frame(HdWalk& w, const char* name, bool own, jds_jpeg_info* out) {
+  const uint8_t* s = w.s;
+  if (w.sof) return w.fail(JDS_EINVAL, "second %s", name);
+  if (w.sl < 6) return w.fail(JDS_EINVAL, "%s too short", name);
+  if (s[0] != 8) return w.fail(JDS_ENOTSUP, "sample precision %d (12-bit and other depths are not supported)", s[0]);
+  out->H = (s[1] << 8) | s[2];
+  out->W = (s[3] << 8) | s[4];
+  const int nf = s[5];
+  if (own && nf == 1) return w.fail(JDS_ENOTSUP, "grayscale files (one component) are not supported");
+  if (nf != 3 && (own || nf != 1))
+    return w.fail(JDS_ENOTSUP, "%d components (%s are supported)", nf, own ? "three" : "one or three");
+  if (w.sl != 6 + 3 * nf) return w.fail(JDS_EINVAL, "%s length does not match its component count", name);
+  if (out->H < 1 || out->W < 1)
+    return w.fail(JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
+  if (nf == 1) {
+    // grayscale: any component id; the sampling byte is checked and then ignored, since a
+    // one-component scan is never interleaved and holds ceil(W/8) x ceil(H/8) blocks (T.81 A.2.2)
+    const int h1 = s[7] >> 4, v1 = s[7] & 15;
+    if (h1 < 1 || h1 > 4 || v1 < 1 || v1 > 4) return w.fail(JDS_EINVAL, "sampling factors %dx%d (1..4 each)", h1, v1);
+    w.gray_id = s[6];
+    out->subsampling = JDS_SS_GRAY;
+  } else {
+    for (int c = 0; c < 3; ++c)
+      if (s[6 + 3 * c] != c + 1) return w.fail(JDS_ENOTSUP, "component ids other than 1, 2, 3");
+    const int ys = s[7];
+    if (ys != 0x11 && ys != 0x21 && ys != 0x22)
+      return w.fail(JDS_ENOTSUP, "luma sampling %dx%d (1x1, 2x1 and 2x2 are supported)", ys >> 4, ys & 15);
+    if (s[10] != 0x11 || s[13] != 0x11) return w.fail(JDS_ENOTSUP, "subsampled or oversampled chroma factors");
+    out->subsampling = ys == 0x11 ? JDS_SS_444 : (ys == 0x21 ? JDS_SS_422 : JDS_SS_420);
+    if (own && (s[8] != s[11] || s[8] != s[14]))
+      return w.fail(JDS_ENOTSUP, "two quantisation tables in use (one is supported)");
+  }
+  w.ncomp = nf;
+  const int hmax = nf == 1 ? 1 : s[7] >> 4, vmax = nf == 1 ? 1 : s[7] & 15;
+  for (int c = 0; c < nf; ++c) {
+    out->tq[c] = s[8 + 3 * c];
+    if (out->tq[c] > 3) return w.fail(JDS_EINVAL, "quantisation table id %d", out->tq[c]);
+    out->hs[c] = c ? 1 : hmax;
+    out->vs[c] = c ? 1 : vmax;
+    const int64_t xc = (out->W * out->hs[c] + hmax - 1) / hmax, yc = (out->H * out->vs[c] + vmax - 1) / vmax;
+    out->grid_cols[c] = (xc + 7) / 8;
+    out->grid_rows[c] = (yc + 7) / 8;
+    out->coeffs_needed += 64 * out->grid_cols[c] * out->grid_rows[c];
+  }
+  out->single_table = nf == 1 || (out->tq[0] == out->tq[1] && out->tq[0] == out->tq[2]);
+  out->blocks_per_mcu = nf == 1 ? 1 : hmax * vmax + 2;
+  out->mcu_cols = (out->W + 8 * hmax - 1) / (8 * hmax);
+  out->mcu_rows = (out->H + 8 * vmax - 1) / (8 * vmax);
+  int64_t ny = 0, nc = 0;
+  out->reference_grid = nf == 3 && hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, nullptr, 0) == JDS_OK;
+  w.sof = true;
+  return JDS_OK;
+}
+
+// A frame header other than the walk's own; only: the tail of the message.
+inline int hd_refuse_sof(const HdWalk& w, const char* only) {
+  if (w.m == 0xCC || w.m >= 0xC9) return w.fail(JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", w.m);
+  return w.fail(JDS_ENOTSUP, "%s (SOF%d) is not supported: %s", w.m == 0xC2 ? "progressive JPEG" : "this frame type",
+                 w.m - 0xC0, only);
+}
+
+// The table at byte q of the DHT at hand: Tc/Th (th_max: the highest id the walk
+// takes, 3 by T.81), BITS, its nv values within the segment, and its codes.
+// fixed (nullable): the file's tables [2 * Tc + Th] once a scan has used them.
+inline int hd_dht_table(const HdWalk& w, int64_t q, int th_max, const jds_jfif_huff* fixed, int* tc, int* th, int* nv) {
+  const uint8_t* s = w.s + q;
+  if (q + 17 > w.sl) return w.fail(JDS_EINVAL, "truncated DHT");
+  *tc = s[0] >> 4;
+  *th = s[0] & 15;
+  if (*tc > 1 || *th > 3) return w.fail(JDS_EINVAL, "bad DHT table header 0x%02X", s[0]);
+  if (*th > th_max) return w.fail(JDS_ENOTSUP, "Huffman table id %d (baseline has 0 and 1)", *th);
+  *nv = 0;
+  for (int i = 0; i < 16; ++i) *nv += s[1 + i];
+  if (*nv > 256) return w.fail(JDS_EINVAL, "DHT: BITS sum to %d symbols (more than 256)", *nv);
+  if (q + 17 + *nv > w.sl) return w.fail(JDS_EINVAL, "truncated DHT");
+  if (fixed && fixed[2 * *tc + *th].defined) return w.fail(JDS_ENOTSUP, "Huffman table redefined between scans");
+  uint8_t vals[256];
+  memset(vals, 0, sizeof vals);
+  memcpy(vals, s + 17, (size_t)*nv);
+  HuffDecTab t;
+  if (hd_build(s + 1, vals, &t) < 0)
+    return w.fail(JDS_EINVAL, "DHT %d/%d: BITS over-subscribe the code space", *tc, *th);
+  return JDS_OK;
+}
+
+// The i-th component id of the SOS at hand (ns components) as the info counts
+// them, from 1.  pre: what the walk puts in front of a scan's messages.
+inline int hd_sos_component(const HdWalk& w, int i, int ns, const char* pre, int* comp) {
+  int id = w.s[1 + 2 * i];
+  if (w.ncomp == 1) {
+    if (id != w.gray_id)
+      return w.fail(JDS_EINVAL, "%sSOS names component %d, the grayscale frame's component is %d", pre, id, w.gray_id);
+    id = 1;  // (the file's own id stays in its header)
+  }
+  if (id < 1 || id > 3) return w.fail(JDS_EINVAL, "%sSOS names component %d", pre, id);
+  if (ns == 3 && id != i + 1)
+    return w.fail(JDS_ENOTSUP, "%sinterleaved scan whose components are not 1, 2, 3 in that order", pre);
+  *comp = id;
+  return JDS_OK;
+}
+
+// The entropy-coded bytes of scan `scan` behind the SOS at hand: from w.p (the
+// scan's offset) up to the next marker (0xFF, then neither 0x00 nor a fill
+// 0xFF) that is no RSTm; with a restart interval in effect the RSTm markers
+// belong to the scan.  *nm (nullable): how many there are; in_order: the i-th must be
+// RST(i & 7).  *end: where the walk goes on.
+inline int hd_scan_end(const HdWalk& w, int scan, bool in_order, int64_t* end, int64_t* nm = nullptr) {
+  const uint8_t* data = w.data;  // (locals: this loop sees every byte of the file)
+  const int64_t len = w.len;
+  int64_t e = w.p, n = 0;
+  for (;;) {
+    if (e + 1 >= len) return w.fail(JDS_EINVAL, "truncated scan data: EOI missing");
+    if (data[e] == 0xFF && data[e + 1] != 0x00) {
+      const int r = data[e + 1] - 0xD0;
+      if (r < 0 || r > 7) break;
+      if (!w.ri)
+        return w.fail(JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)", scan, r);
+      if (in_order && r != (int)(n & 7))
+        return w.fail(JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)", scan, r,
+                       (int)(n & 7), w.ri);
+      ++n;
+      e += 2;
+      continue;
+    }
+    ++e;
+  }
+  *end = e;
+  if (nm) *nm = n;
+  return JDS_OK;
+}
+
+// The components' quantisation tables in row-major order, as everything behind the parser reads them.
+inline void hd_qtables(const HdWalk& w, jds_jpeg_info* out) {
+  for (int c = 0; c < w.ncomp; ++c)
+    for (int k = 0; k < 64; ++k) out->qtable[c][HD_ZZ[k]] = (double)w.qt[out->tq[c]][k];
+}
+
+// The baseline marker walk: SOI, segments up to EOI, with or without restart
+// intervals.  Where a segment has two defects the order of its checks decides
+// which one is reported, and the two profiles' orders differ on purpose (each
+// keeps its own messages and return codes).
 inline int hd_walk(const uint8_t* data, int64_t len, HdProfile prof, jds_jpeg_info* out, char* msg, size_t cap) {
   const bool own = prof == HD_OWN;
   if (!data || !out || len < 0) return hd_fail(msg, cap, JDS_EINVAL, "null argument");
   memset(out, 0, sizeof *out);
   if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) return hd_fail(msg, cap, JDS_EINVAL, "not a JPEG file: SOI missing");
-  uint8_t qt[4][64];
-  bool qdef[4] = {false, false, false, false};
-  bool sof = false, seen[4] = {false, false, false, false};
-  int ri = 0;                  // the restart interval in effect (DRI), 0: none
-  int ncomp = 3, gray_id = 0;  // a one-component frame: its component id as written (the SOS must name it)
+  HdWalk w{data, len, msg, cap};
+  bool seen[4] = {false, false, false, false};
   int rc;
-  int64_t p = 2;
   for (;;) {
-    if (p + 2 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated file: EOI missing");
-    if (data[p] != 0xFF) return hd_fail(msg, cap, JDS_EINVAL, "marker expected at byte %lld", (long long)p);
-    const int m = data[p + 1];
-    if (m == 0xFF) {  // fill byte
-      ++p;
-      continue;
-    }
-    if (m == 0xD9) break;  // EOI
-    if (m >= 0xD0 && m <= 0xD7)
-      return hd_fail(msg, cap, JDS_EINVAL, "restart marker RST%d outside scan data at byte %lld", m - 0xD0, (long long)p);
-    if (m == 0xD8 || m == 0x01 || m == 0x00)
-      return hd_fail(msg, cap, JDS_EINVAL, "unexpected marker 0x%02X at byte %lld", m, (long long)p);
-    if (p + 4 > len) return hd_fail(msg, cap, JDS_EINVAL, "truncated segment header at byte %lld", (long long)p);
-    const int64_t ln = ((int64_t)data[p + 2] << 8) | data[p + 3];
-    if (ln < 2 || p + 2 + ln > len)
-      return hd_fail(msg, cap, JDS_EINVAL, "segment 0x%02X at byte %lld: length %lld reaches past the end of the file", m,
-                     (long long)p, (long long)ln);
-    const uint8_t* s = data + p + 4;
-    const int64_t sl = ln - 2;
+    if ((rc = hd_next(w))) return rc;
+    if (w.m == 0xD9) break;  // EOI
+    const int m = w.m, ri = w.ri;
     if (m == 0xC0) {
-      if (sof) return hd_fail(msg, cap, JDS_EINVAL, "second SOF0");
-      if (sl < 6) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 too short");
-      if (s[0] != 8) return hd_fail(msg, cap, JDS_ENOTSUP, "sample precision %d (12-bit and other depths are not supported)", s[0]);
-      out->H = (s[1] << 8) | s[2];
-      out->W = (s[3] << 8) | s[4];
-      const int nf = s[5];
-      if (own && nf == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "grayscale files (one component) are not supported");
-      if (nf != 3 && (own || nf != 1))
-        return hd_fail(msg, cap, JDS_ENOTSUP, "%d components (%s are supported)", nf, own ? "three" : "one or three");
-      if (sl != 6 + 3 * nf) return hd_fail(msg, cap, JDS_EINVAL, "SOF0 length does not match its component count");
-      if (out->H < 1 || out->W < 1) return hd_fail(msg, cap, JDS_ENOTSUP, "frame size %lldx%lld (DNL is not supported)", (long long)out->H, (long long)out->W);
-      if (nf == 1) {
-        // grayscale: any component id; the sampling byte is checked and then ignored, since a
-        // one-component scan is never interleaved and holds ceil(W/8) x ceil(H/8) blocks (T.81 A.2.2)
-        const int h1 = s[7] >> 4, v1 = s[7] & 15;
-        if (h1 < 1 || h1 > 4 || v1 < 1 || v1 > 4)
-          return hd_fail(msg, cap, JDS_EINVAL, "sampling factors %dx%d (1..4 each)", h1, v1);
-        ncomp = 1;
-        gray_id = s[6];
-        out->subsampling = JDS_SS_GRAY;
-      } else {
-        for (int c = 0; c < 3; ++c)
-          if (s[6 + 3 * c] != c + 1) return hd_fail(msg, cap, JDS_ENOTSUP, "component ids other than 1, 2, 3");
-        const int ys = s[7];
-        if (ys != 0x11 && ys != 0x21 && ys != 0x22)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "luma sampling %dx%d (1x1, 2x1 and 2x2 are supported)", ys >> 4, ys & 15);
-        if (s[10] != 0x11 || s[13] != 0x11) return hd_fail(msg, cap, JDS_ENOTSUP, "subsampled or oversampled chroma factors");
-        out->subsampling = ys == 0x11 ? JDS_SS_444 : (ys == 0x21 ? JDS_SS_422 : JDS_SS_420);
-        if (own && (s[8] != s[11] || s[8] != s[14]))
-          return hd_fail(msg, cap, JDS_ENOTSUP, "two quantisation tables in use (one is supported)");
-      }
-      const int hmax = ncomp == 1 ? 1 : s[7] >> 4, vmax = ncomp == 1 ? 1 : s[7] & 15;
-      for (int c = 0; c < ncomp; ++c) {
-        out->tq[c] = s[8 + 3 * c];
-        if (out->tq[c] > 3) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table id %d", out->tq[c]);
-        out->hs[c] = c ? 1 : hmax;
-        out->vs[c] = c ? 1 : vmax;
-        const int64_t xc = (out->W * out->hs[c] + hmax - 1) / hmax, yc = (out->H * out->vs[c] + vmax - 1) / vmax;
-        out->grid_cols[c] = (xc + 7) / 8;
-        out->grid_rows[c] = (yc + 7) / 8;
-        out->coeffs_needed += 64 * out->grid_cols[c] * out->grid_rows[c];
-      }
-      out->single_table = ncomp == 1 || (out->tq[0] == out->tq[1] && out->tq[0] == out->tq[2]);
-      out->blocks_per_mcu = ncomp == 1 ? 1 : hmax * vmax + 2;
-      out->mcu_cols = (out->W + 8 * hmax - 1) / (8 * hmax);
-      out->mcu_rows = (out->H + 8 * vmax - 1) / (8 * vmax);
-      int64_t ny = 0, nc = 0;
-      out->reference_grid = ncomp == 3 && hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, nullptr, 0) == JDS_OK;
-      sof = true;
-    } else if ((m >= 0xC1 && m <= 0xCF) && m != 0xC4 && m != 0xC8) {
-      if (m == 0xCC || m >= 0xC9) return hd_fail(msg, cap, JDS_ENOTSUP, "arithmetic coding (marker 0x%02X) is not supported", m);
-      return hd_fail(msg, cap, JDS_ENOTSUP, "%s (SOF%d) is not supported: baseline SOF0 only", m == 0xC2 ? "progressive JPEG" : "this frame type", m - 0xC0);
-    } else if (m == 0xDD) {
-      if (ln != 4) return hd_fail(msg, cap, JDS_EINVAL, "DRI segment of length %lld (4 expected)", (long long)ln);
-      ri = (s[0] << 8) | s[1];
-    } else if (m == 0xDB) {
-      int64_t q = 0;
-      while (q < sl) {
-        const int pq = s[q] >> 4, id = s[q] & 15;
-        if (pq == 1) return hd_fail(msg, cap, JDS_ENOTSUP, "16-bit DQT is not supported");
-        if (pq != 0 || id > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DQT table header 0x%02X", s[q]);
-        if (q + 65 > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DQT");
-        memcpy(qt[id], s + q + 1, 64);
-        qdef[id] = true;
-        q += 65;
-      }
+      if ((rc = hd_frame(w, "SOF0", own, out))) return rc;
     } else if (m == 0xC4) {
-      int64_t q = 0;
-      while (q < sl) {
-        int tc = 0, th = 0, nv = 0;
-        if (q + 17 <= sl) {  // the table's header and BITS
-          tc = s[q] >> 4;
-          th = s[q] & 15;
-          if (tc > 1 || th > 3) return hd_fail(msg, cap, JDS_EINVAL, "bad DHT table header 0x%02X", s[q]);
-          if (th > 1) return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table id %d (baseline has 0 and 1)", th);
-          for (int i = 0; i < 16; ++i) nv += s[q + 1 + i];
-          if (nv > 256) return hd_fail(msg, cap, JDS_EINVAL, "DHT: BITS sum to %d symbols (more than 256)", nv);
-        }
-        if (q + 17 + nv > sl) return hd_fail(msg, cap, JDS_EINVAL, "truncated DHT");
+      int tc, th, nv;
+      for (int64_t q = 0; q < w.sl; q += 17 + nv) {
+        if ((rc = hd_dht_table(w, q, 1, out->n_scans ? out->huff : nullptr, &tc, &th, &nv))) return rc;
         jds_jfif_huff* h = &out->huff[2 * tc + th];
-        if (out->n_scans && h->defined)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "Huffman table redefined between scans");
         memset(h, 0, sizeof *h);
-        memcpy(h->bits, s + q + 1, 16);
-        memcpy(h->vals, s + q + 17, (size_t)nv);
+        memcpy(h->bits, w.s + q + 1, 16);
+        memcpy(h->vals, w.s + q + 17, (size_t)nv);
         h->n_vals = nv;
-        HuffDecTab t;
-        if (hd_build(h->bits, h->vals, &t) < 0)
-          return hd_fail(msg, cap, JDS_EINVAL, "DHT %d/%d: BITS over-subscribe the code space", tc, th);
         h->defined = 1;
-        q += 17 + nv;
       }
     } else if (m == 0xDA) {
-      if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
-      if (sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
-      const int ns = s[0];
+      if (!w.sof) return hd_fail(msg, cap, JDS_EINVAL, "SOS before SOF0");
+      if (w.sl < 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS too short");
+      const int ns = w.s[0];
       jds_jpeg_scan cur;  // (joins out->scan once every check has passed)
       memset(&cur, 0, sizeof cur);
       // the checks of an SOS, each written once; the profiles run them in their own orders below
       auto length = [&] {
-        return sl != 4 + 2 * ns ? hd_fail(msg, cap, JDS_EINVAL, "SOS length does not match its component count") : 0;
+        return w.sl != 4 + 2 * ns ? hd_fail(msg, cap, JDS_EINVAL, "SOS length does not match its component count") : 0;
       };
       auto count = [&] { return out->n_scans >= 3 ? hd_fail(msg, cap, JDS_EINVAL, "more than three scans") : 0; };
       auto spectral = [&] {
-        const uint8_t* t = s + 1 + 2 * ns;
+        const uint8_t* t = w.s + 1 + 2 * ns;
         return t[0] != 0 || t[1] != 63 || t[2] != 0
                    ? hd_fail(msg, cap, JDS_ENOTSUP, "spectral selection / successive approximation (progressive scan parameters)")
                    : 0;
       };
       auto component = [&](int i) {
-        int comp = s[1 + 2 * i];
-        if (ncomp == 1) {
-          if (comp != gray_id)
-            return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d, the grayscale frame's component is %d", comp, gray_id);
-          comp = 1;  // (the info counts components from 1; the file's own id stays in its header)
-        }
-        if (comp < 1 || comp > 3) return hd_fail(msg, cap, JDS_EINVAL, "SOS names component %d", comp);
-        if (ns == 3 && comp != i + 1)
-          return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan whose components are not 1, 2, 3 in that order");
+        int comp;
+        const int r = hd_sos_component(w, i, ns, "", &comp);
+        if (r) return r;
         if (seen[comp]) return hd_fail(msg, cap, JDS_ENOTSUP, "component %d has a second scan", comp);
         cur.component[i] = comp;
         return 0;
       };
       auto tables = [&](int i) {
-        const int td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15, tq = out->tq[cur.component[i] - 1];
+        const int td = w.s[2 + 2 * i] >> 4, ta = w.s[2 + 2 * i] & 15, tq = out->tq[cur.component[i] - 1];
         if (td > 1 || ta > 1) return hd_fail(msg, cap, JDS_EINVAL, "SOS table ids %d/%d", td, ta);
         if (!out->huff[td].defined || !out->huff[2 + ta].defined)
           return hd_fail(msg, cap, JDS_EINVAL, "SOS refers to a Huffman table the file has not defined");
-        if (!qdef[tq]) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", tq);
+        if (!w.qdef[tq]) return hd_fail(msg, cap, JDS_EINVAL, "quantisation table %d is not defined", tq);
         cur.dc_table[i] = td;
         cur.ac_table[i] = ta;
         return 0;
@@ -230,9 +329,9 @@ inline int hd_walk(const uint8_t* data, int64_t len, HdProfile prof, jds_jpeg_in
         if (ns != 1) return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan (Ns = %d): non-interleaved scans only", ns);
         if ((rc = length()) || (rc = component(0)) || (rc = spectral()) || (rc = tables(0)) || (rc = count())) return rc;
       } else {
-        if (ncomp == 1 && ns != 1)
+        if (w.ncomp == 1 && ns != 1)
           return hd_fail(msg, cap, JDS_EINVAL, "scan of %d components in a grayscale (one-component) frame", ns);
-        if (ncomp == 1 && out->n_scans)
+        if (w.ncomp == 1 && out->n_scans)
           return hd_fail(msg, cap, JDS_ENOTSUP, "a second scan in a grayscale (one-component) file");
         if (ns == 2)
           return hd_fail(msg, cap, JDS_ENOTSUP, "interleaved scan of two components (Ns = 2): one scan of three or three of one only");
@@ -245,26 +344,9 @@ inline int hd_walk(const uint8_t* data, int64_t len, HdProfile prof, jds_jpeg_in
           if ((rc = component(i)) || (rc = tables(i))) return rc;
         if ((rc = spectral())) return rc;
       }
-      // entropy-coded segment: up to the next marker (0xFF, then neither 0x00 nor a fill 0xFF);
-      // with a restart interval in effect its RSTm markers belong to it, m = i & 7 for the i-th
-      int64_t e = p + 2 + ln, nm = 0;
-      for (;;) {
-        if (e + 1 >= len) return hd_fail(msg, cap, JDS_EINVAL, "truncated scan data: EOI missing");
-        if (data[e] == 0xFF && data[e + 1] != 0x00) {
-          const int r = data[e + 1] - 0xD0;
-          if (r < 0 || r > 7) break;
-          if (!ri)
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d without a restart interval (no DRI)",
-                           out->n_scans, r);
-          if (r != (int)(nm & 7))
-            return hd_fail(msg, cap, JDS_EINVAL, "scan %d: restart marker RST%d where RST%d belongs (DRI %d)",
-                           out->n_scans, r, (int)(nm & 7), ri);
-          ++nm;
-          e += 2;
-          continue;
-        }
-        ++e;
-      }
+      // the entropy-coded segment; its RSTm markers are counted here and must come in order
+      int64_t e, nm;
+      if ((rc = hd_scan_end(w, out->n_scans, true, &e, &nm))) return rc;
       if (ri) {
         // the scan's MCUs: T.81's; own: the reference's block counts, the same number where they exist
         int64_t ny = 0, nc = 0;
@@ -282,22 +364,20 @@ inline int hd_walk(const uint8_t* data, int64_t len, HdProfile prof, jds_jpeg_in
       for (int i = 0; i < ns; ++i) seen[cur.component[i]] = true;
       cur.n_components = ns;
       cur.restart_interval = ri;
-      cur.offset = p + 2 + ln;
+      cur.offset = w.p;
       cur.length = e - cur.offset;
       out->scan[out->n_scans++] = cur;
       out->interleaved = ns == 3;
-      p = e;
-      continue;
+      w.p = e;
+    } else {
+      return hd_refuse_sof(w, "baseline SOF0 only");
     }
-    // APPn, COM and anything else with a length: skipped
-    p += 2 + ln;
   }
-  if (!sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
-  if (out->n_scans != (out->interleaved || ncomp == 1 ? 1 : 3))
+  if (!w.sof) return hd_fail(msg, cap, JDS_EINVAL, "no SOF0 segment");
+  if (out->n_scans != (out->interleaved || w.ncomp == 1 ? 1 : 3))
     return hd_fail(msg, cap, JDS_EINVAL, "%d scans (%s expected)", out->n_scans,
                    own ? "one per component" : "one interleaved scan or one per component");
-  for (int c = 0; c < ncomp; ++c)
-    for (int k = 0; k < 64; ++k) out->qtable[c][HD_ZZ[k]] = (double)qt[out->tq[c]][k];
+  hd_qtables(w, out);
   int64_t ny = 0, nc = 0;
   return own ? hd_block_counts(out->H, out->W, out->subsampling, &ny, &nc, msg, cap) : JDS_OK;
 }

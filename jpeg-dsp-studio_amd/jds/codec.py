@@ -382,6 +382,12 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     scale_denom: 1, 2, 4 or 8, or one per file (render='libjpeg' for any other than 1): each
     image is jpeg_to_rgb(scale_denom=...)'s, out_H x out_W x 3, placed by that size
     (k_jpeg_ljs_batch, one launch per mode and denominator present)."""
+    return _batch_to_rgb(files, device, out, with_info, errors, ctx, render, scale_denom)
+
+
+def _batch_to_rgb(files, device, out, with_info, errors, ctx, render, scale_denom, progressive=False):
+    """jpeg_batch_to_rgb, and with `progressive` pjpeg_batch_to_rgb: the same buffers, items and
+    errors around the layout call and the run call of either kind of file."""
     if errors not in ('raise', 'return'):
         raise ValueError("errors must be 'raise' or 'return'")
     code = _abi.render_code(render)
@@ -392,7 +398,10 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     if out is None or isinstance(out, str):
         # the output is sized here, from the layout; a caller's buffer is checked by the call itself
         rb, ce = C.c_int64(0), C.c_int64(0)
-        check(_batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c))
+        if progressive:
+            check(lib().jds_pjpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce), dens_c, None))
+        else:
+            check(_batch_layout_call(ptrs, lens, n, items, rb, ce, dens_c))
         cap = int(rb.value)
     if out is None:
         buf = np.empty(max(cap, 1), np.uint8)
@@ -412,6 +421,9 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     rounds = C.c_uint32(0)
 
     def run(c):
+        if progressive:
+            return lib().jds_pjpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, code, dens_c, items,
+                                                None, None)
         if dens_c is not None:
             return lib().jds_jpeg_batch_to_rgb_scaled(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, None,
                                                       items, C.byref(rounds), code, dens_c, None)
@@ -439,9 +451,11 @@ def jpeg_batch_to_rgb(files, device: int = 0, out=None, with_info: bool = False,
     if not with_info:
         return imgs
     ok = [it for it in info if it['rc'] == 0]
-    return imgs, {'items': info, 'rounds': int(rounds.value),
-                  'rgb_bytes': sum(-(-it['out_H'] * it['out_W'] * 3 // 256) * 256 for it in ok),
-                  'coef_entries': sum(it['coeffs_needed'] for it in ok)}
+    d = {'items': info, 'rgb_bytes': sum(-(-it['out_H'] * it['out_W'] * 3 // 256) * 256 for it in ok),
+         'coef_entries': sum(it['coeffs_needed'] for it in ok)}
+    if not progressive:
+        d['rounds'] = int(rounds.value)     # (the chains of a progressive file have no propagation rounds)
+    return imgs, d
 
 
 def host_jpeg_batch(files, subseq_bits: int = 1024, render: str = 'reference', scale_denom=1):
@@ -700,57 +714,7 @@ def pjpeg_batch_to_rgb(files, out='device', render: str = 'libjpeg', scale_denom
     and ctx as jpeg_batch_to_rgb's, with its layout (images at multiples of 256) and its item
     contract: a baseline file ("not progressive"), an incomplete progression or defective scan
     data is that file's error and does not stop the others."""
-    if errors not in ('raise', 'return'):
-        raise ValueError("errors must be 'raise' or 'return'")
-    code = _abi.render_code(render)
-    keep, ptrs, lens = _batch_args(files)
-    n = len(keep)
-    dens, dens_c = _batch_denoms(scale_denom, n, render)
-    items = (_abi.JpegBatchItem * max(n, 1))()
-    if out is None or isinstance(out, str):
-        rb, ce = C.c_int64(0), C.c_int64(0)
-        check(lib().jds_pjpeg_batch_layout(ptrs, lens, n, items, C.byref(rb), C.byref(ce), dens_c, None))
-        cap = int(rb.value)
-    if out is None:
-        buf = np.empty(max(cap, 1), np.uint8)
-        dst, on_dev = buf.ctypes.data, 0
-    else:
-        if isinstance(out, str):
-            if out != 'device':
-                raise ValueError("out must be None, 'device' or a 1-D uint8 device tensor")
-            import torch
-            buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=f'cuda:{device}')
-        else:
-            buf = out
-            if buf.dim() != 1 or buf.element_size() != 1 or not buf.is_contiguous():
-                raise ValueError('out must be a contiguous 1-D uint8 device tensor')
-            cap = int(buf.numel())
-        dst, on_dev = int(buf.data_ptr()), 1
-
-    def run(c):
-        return lib().jds_pjpeg_batch_to_rgb(c.handle, ptrs, lens, n, C.c_void_p(dst), cap, on_dev, code, dens_c, items,
-                                            None, None)
-    if ctx is not None:
-        check(run(ctx))
-    else:
-        with lease(device) as c:
-            check(run(c))
-    info = [_batch_item_dict(items[i], dens[i]) for i in range(n)]
-    first = _batch_first_error(info)
-    if first and errors == 'raise':
-        raise ValueError(first)
-    imgs = []
-    for it in info:
-        if it['rc'] != 0 or it['status'] != 0:
-            imgs.append(None)
-            continue
-        o, sz = it['rgb_off'], it['out_H'] * it['out_W'] * 3
-        imgs.append(buf[o:o + sz].reshape(it['out_H'], it['out_W'], 3))
-    if not with_info:
-        return imgs
-    ok = [it for it in info if it['rc'] == 0]
-    return imgs, {'items': info, 'rgb_bytes': sum(-(-it['out_H'] * it['out_W'] * 3 // 256) * 256 for it in ok),
-                  'coef_entries': sum(it['coeffs_needed'] for it in ok)}
+    return _batch_to_rgb(files, device, out, with_info, errors, ctx, render, scale_denom, progressive=True)
 
 
 def pjpeg_scan_times(ctx, files, took_part=None):

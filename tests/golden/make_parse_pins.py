@@ -14,7 +14,16 @@ Per source, parser and mutation group one SHA-256 over the group's ordered lines
 `rc \\t message \\t sha256(struct bytes)` is stored (message on failure only, struct hash on
 success only).  Groups: 'orig'; 'trunc' (every length up to the end of the first SOS header,
 every 7th after it); one per value of VALUES (every byte from offset 2 to the end of the first
-SOS header set to it).  The named double-defect cases are stored in full."""
+SOS header set to it).  The named double-defect cases are stored in full.
+
+--pjpeg: the same for jds_pjpeg_parse and tests/golden/pjpeg_parse_pins.json
+(tests/test_pjpeg_parse_pins_cpu.py), recorded from the build before the progressive walk was
+put on the baseline walk's pieces.  Its sources are pure-Python files (tests/progressive_ref.py's
+writer); its mutated bytes are the header's and, where this parser's own logic lives, every byte
+of the marker segments between the scans (DHT, DRI, SOS).
+
+    JDS_LIB_PATH=<the older build>/libjds.so python tests/golden/make_parse_pins.py --pjpeg
+    python tests/golden/make_parse_pins.py --pjpeg --check"""
 import ctypes as C
 import hashlib
 import json
@@ -33,6 +42,7 @@ import numpy as np  # noqa: E402
 PINS = os.path.join(HERE, 'parse_pins.json')
 VALUES = (0x00, 0x01, 0x03, 0x05, 0x11, 0x22, 0x3F, 0xC0, 0xC2, 0xC4, 0xD0, 0xD9, 0xDA, 0xDB, 0xDD, 0xFF)
 PARSERS = ('jfif', 'jpeg')
+PJPEG_PINS = os.path.join(HERE, 'pjpeg_parse_pins.json')
 MAX_SOURCE_BYTES = 4096
 
 
@@ -152,8 +162,71 @@ def double_defects():
     return out
 
 
+def pjpeg_sources():
+    """{name: bytes}, in a fixed order: the scan scripts over the two geometries, the 64-scan
+    gray file, and a baseline file (it answers "not progressive")."""
+    import interleaved_ref as il
+    import pjpeg_cases as pc
+    import progressive_ref as pr
+    out = {}
+    for H, W, mode in pc.SCRIPT_GEOS:
+        geo = '%dx%d_%s/' % (H, W, mode.replace(':', ''))
+        out[geo + 'pillow'] = pr.write(pc.padded(H, W, mode), H, W, mode, pc.QT, pr.pillow_script(mode))
+        for name in ('ids_2_3', 'shared_tables', 'ri1', 'ri5', 'stops_at_al1', 'bands'):
+            out[geo + name] = pc.script_file(H, W, mode, name)[0]
+    H, W, mode = pc.SCRIPT_GEOS[0]
+    out['gray/64_scans'] = _pjpeg_gray_scans(64)
+    out['baseline/%dx%d' % (H, W)] = il.write(pc.padded(H, W, mode), H, W, mode, pc.QT)
+    for name, data in out.items():
+        assert len(data) < MAX_SOURCE_BYTES, (name, len(data))
+    return out
+
+
+def _pjpeg_gray_scans(n):
+    """The gray file of test_refusals_by_name: one scan per coefficient; 65: DC in two passes."""
+    import pjpeg_cases as pc
+    import progressive_ref as pr
+    H, W, mode = pc.SCRIPT_GEOS[0]
+    g = [np.asarray(pc.padded(H, W, mode)[0])[:3, :5]]
+    s = [((0,), 0, 0, 0, 0)] + [((0,), k, k, 0, 0) for k in range(1, 64)]
+    if n == 65:
+        s = [((0,), 0, 0, 0, 1)] + s[1:] + [((0,), 0, 0, 1, 0)]
+    return pr.write(g, H, W, 'gray', {0: pc.QT[0]}, s)
+
+
+def pjpeg_double_defects():
+    """{name: bytes}: progressive files whose report depends on the order of the checks."""
+    import pjpeg_cases as pc
+    import progressive_ref as pr
+    H, W, mode = pc.SCRIPT_GEOS[0]
+    good = pr.write(pc.padded(H, W, mode), H, W, mode, pc.QT, pr.pillow_script(mode))
+    data0 = [a for a, _ in pc._scan_ranges(good)]        # each scan's first data byte; Ss, Se, Ah|Al end its SOS
+
+    def patched(at, new, src=good):
+        d = bytearray(src)
+        d[at:at + len(new)] = new
+        return bytes(d)
+    out = {}
+    out['sos_ss_above_se_and_al_14'] = patched(data0[1] - 3, bytes([6, 5, 0x0E]))
+    out['ac_scan_ns3_names_an_undefined_table'] = patched(data0[0] - 8, b'\x33', patched(data0[0] - 3, bytes([1, 5])))
+    out['refinement_before_first_pass_with_wrong_ah'] = patched(data0[1] - 1, b'\x31')
+    s65 = _pjpeg_gray_scans(65)
+    out['scan_65_also_malformed'] = patched(pc._scan_ranges(s65)[64][0] - 3, bytes([6, 5]), s65)
+    dht = _segment(good, 0xC4)
+    out['dht_bad_header_and_oversubscribed'] = patched(dht + 4, b'\x24\x03')
+    sof = _segment(good, 0xC2)
+    out['sof2_precision_12_and_4_components'] = patched(sof + 9, b'\x04', patched(sof + 4, b'\x0c'))
+    return out
+
+
+# What a fixture is made of: its file, its parsers, its inputs, and whether the segments
+# between the scans are mutated too.
+BASELINE = dict(pins=PINS, parsers=PARSERS, sources=sources, double_defects=double_defects, later=False)
+PJPEG = dict(pins=PJPEG_PINS, parsers=('pjpeg',), sources=pjpeg_sources, double_defects=pjpeg_double_defects, later=True)
+
+
 class Lib:
-    """The two parse calls of one libjds.so."""
+    """The parse calls of one libjds.so."""
 
     def __init__(self, path=None):
         from jds import _abi
@@ -163,6 +236,8 @@ class Lib:
         self.lib.jds_last_error.restype = C.c_char_p
         self.info = {'jfif': _abi.JfifInfo(), 'jpeg': _abi.JpegInfo()}
         self.fn = {'jfif': self.lib.jds_jfif_parse, 'jpeg': self.lib.jds_jpeg_parse}
+        if hasattr(self.lib, 'jds_pjpeg_parse'):
+            self.info['pjpeg'], self.fn['pjpeg'] = _abi.PjpegInfo(), self.lib.jds_pjpeg_parse
         for f in self.fn.values():
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
@@ -181,9 +256,21 @@ class Lib:
         return '%d\t%s\t%s' % (rc, msg, h)
 
 
-def group_lines(lib, parser, data, group):
+def later_segments(lib, data):
+    """The bytes of the marker segments between the scans, by this library's own parse of the
+    file (the 'orig' group pins that parse, struct bytes and all)."""
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    if lib.answer('pjpeg', buf, len(data))[0] != 0:
+        return []
+    info = lib.info['pjpeg']
+    sc = [info.scan[i] for i in range(info.n_scans)]
+    return [i for a, b in zip(sc, sc[1:]) for i in range(a.offset + a.length, b.offset)]
+
+
+def group_lines(lib, parser, data, group, later=False):
     """The ordered lines of one mutation group of one source."""
     n, end = len(data), first_sos_end(data)
+    where = list(range(2, end)) + (later_segments(lib, data) if later and group not in ('orig', 'trunc') else [])
     buf = (C.c_uint8 * max(n, 1)).from_buffer_copy(data)
     if group == 'orig':
         return [lib.line(parser, buf, n)]
@@ -191,7 +278,7 @@ def group_lines(lib, parser, data, group):
         return [lib.line(parser, buf, k) for k in list(range(end + 1)) + list(range(end + 7, n, 7))]
     v = int(group, 16)
     out = []
-    for i in range(2, end):
+    for i in where:
         old, buf[i] = buf[i], v
         out.append(lib.line(parser, buf, n))
         buf[i] = old
@@ -205,22 +292,22 @@ def digest(lines):
     return hashlib.sha256('\n'.join(lines).encode()).hexdigest()
 
 
-def record(lib):
+def record(lib, fx=BASELINE):
     out = {'sources': {}, 'digests': {}, 'double_defects': {}}
-    for name, data in sources().items():
+    for name, data in fx['sources']().items():
         out['sources'][name] = hashlib.sha256(data).hexdigest()
-        for parser in PARSERS:
+        for parser in fx['parsers']:
             for g in GROUPS:
-                out['digests']['%s|%s|%s' % (name, parser, g)] = digest(group_lines(lib, parser, data, g))
-    for name, data in double_defects().items():
+                out['digests']['%s|%s|%s' % (name, parser, g)] = digest(group_lines(lib, parser, data, g, fx['later']))
+    for name, data in fx['double_defects']().items():
         buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
-        out['double_defects'][name] = {p: list(lib.answer(p, buf, len(data))) for p in PARSERS}
+        out['double_defects'][name] = {p: list(lib.answer(p, buf, len(data))) for p in fx['parsers']}
     return out
 
 
-def differences(lib, pins):
+def differences(lib, pins, fx=BASELINE):
     """[(key, what differs)] of this library against the recorded pins; covers every case."""
-    got, diffs = record(lib), []
+    got, diffs = record(lib, fx), []
     for sect in ('sources', 'digests', 'double_defects'):
         if sorted(got[sect]) != sorted(pins[sect]):
             diffs.append((sect, 'the set of cases differs'))
@@ -232,13 +319,15 @@ def differences(lib, pins):
 
 if __name__ == '__main__':
     lib = Lib()
+    fx = PJPEG if '--pjpeg' in sys.argv else BASELINE
+    PINS = fx['pins']
     if '--check' in sys.argv:
-        d = differences(lib, json.load(open(PINS)))
+        d = differences(lib, json.load(open(PINS)), fx)
         for k, what in d[:20]:
             print(k, what)
         print('%s: %d differences over %d parses' % (lib.path, len(d), lib.parses))
         sys.exit(1 if d else 0)
-    pins = record(lib)
+    pins = record(lib, fx)
     with open(PINS, 'w') as f:
         json.dump(pins, f, indent=0, sort_keys=True)
         f.write('\n')

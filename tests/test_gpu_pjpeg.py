@@ -206,3 +206,39 @@ def test_gpu_mixed_batch_transcode():
     back = codec.jpeg_batch_to_rgb([t.cpu().numpy() for t in dev[:8]], render='libjpeg')
     for i in range(8):
         assert np.array_equal(back[i], pc.pillow_rgb(files[i])), i
+
+
+# ------------------------------------------- 5. both front ends on one context --
+
+def test_gpu_both_front_ends_share_one_contexts_batch_buffers():
+    """The baseline and the progressive batch calls share one driver and one pair of staging and
+    device buffers per context: batch sizes go up and then down on one caller-owned Context, so
+    each front end runs in buffers the other grew, with stale contents beyond its own upload.
+    Every image is Pillow's decode of the same file."""
+    from jds import _abi, codec
+    small = [pc.pillow_pair(9, 9, 2, 0, 75), pc.pillow_pair(24, 40, 'L', 0, 75), pc.pillow_pair(40, 56, 2, 0, 75)]
+    prog, base = [p[1] for p in small], [p[2] for p in small]
+    big = [pc.pillow_pair(200, 264, 2, 0, 75)[2], pc.pillow_pair(264, 200, 0, 0, 75)[2]]
+    one = pc.pillow_pair(1, 1, 0, 0, 75)[1]
+    ctx = _abi.Context(0)
+    try:
+        imgs = codec.pjpeg_batch_to_rgb(prog, out=None, ctx=ctx)
+        for f, im in zip(prog, imgs):
+            assert np.array_equal(im, pc.pillow_rgb(f))
+        imgs = codec.jpeg_batch_to_rgb(big, render='libjpeg', ctx=ctx)
+        for f, im in zip(big, imgs):
+            assert np.array_equal(im, pc.pillow_rgb(f))
+        dev = codec.pjpeg_batch_transcode(prog, out='device', ctx=ctx)
+        back = [t.cpu().numpy() for t in dev]
+        imgs = codec.jpeg_batch_to_rgb(back, render='libjpeg', ctx=ctx)
+        for f, t, im in zip(prog, back, imgs):
+            assert not codec.is_progressive(t) and np.array_equal(im, pc.pillow_rgb(bytes(t)))
+            assert np.array_equal(im, pc.pillow_rgb(f))
+        imgs = codec.pjpeg_batch_to_rgb([one], ctx=ctx)                       # out='device'
+        assert np.array_equal(imgs[0].cpu().numpy(), pc.pillow_rgb(one))
+        dens = [1, 2, 4]
+        imgs = codec.jpeg_batch_to_rgb(base, render='libjpeg', scale_denom=dens, ctx=ctx)
+        for f, dn, im in zip(base, dens, imgs):
+            assert np.array_equal(im, pc.pillow_rgb(f) if dn == 1 else draft_pixels(f, dn)), dn
+    finally:
+        ctx.close()

@@ -249,6 +249,34 @@ def test_pjpeg_struct_layout_matches_the_c_header_and_exports(E, tmp_path):
     assert all(n in _abi._SIGS for n in names)
 
 
+@pytest.mark.parametrize('mix', [False, True], ids=['denoms-1', 'denoms-1-2-4-8'])
+def test_the_two_layouts_are_one(E, mix):
+    """jds_pjpeg_batch_layout on progressive files and jds_jpeg_batch_layout_scaled on their baseline
+    twins place the same images and coefficients; each list holds one file its parser refuses."""
+    from jds import _abi, codec
+    pairs = [pc.pillow_pair(*prm) for prm in pc.PILLOW_PARAMS if prm[4] == 75]
+    prog = [p[1] for p in pairs[:4]] + [pairs[0][2]] + [p[1] for p in pairs[4:]]     # (a baseline file: "not progressive")
+    base = [p[2] for p in pairs[:4]] + [pairs[0][1]] + [p[2] for p in pairs[4:]]     # (a progressive file: refused by name)
+    n = len(prog)
+    assert n == 10
+    dens = [(1, 2, 4, 8)[i % 4] if mix else 1 for i in range(n)]
+    got = []
+    for fn, files in ((codec.lib().jds_pjpeg_batch_layout, prog), (codec.lib().jds_jpeg_batch_layout_scaled, base)):
+        keep, ptrs, lens = codec._batch_args(files)
+        items, scaled = (_abi.JpegBatchItem * n)(), (_abi.JpegScaledItem * n)()
+        rb, ce = C.c_int64(-1), C.c_int64(-1)
+        codec.check(fn(ptrs, lens, n, items, C.byref(rb), C.byref(ce), (C.c_int32 * n)(*dens), scaled))
+        got.append((int(rb.value), int(ce.value),
+                    [tuple(getattr(it, f) for f in ('rc', 'H', 'W', 'subsampling', 'interleaved', 'rgb_off', 'coef_off',
+                                                     'coeffs_needed')) for it in items],
+                    [(s.scale_denom, s.out_h, s.out_w) for s in scaled]))
+    assert got[0] == got[1]
+    rbytes, centries, items, scaled = got[0]
+    assert [it[0] != 0 for it in items] == [i == 4 for i in range(n)] and items[4][5] == items[4][6] == -1
+    assert rbytes > 0 and centries == sum(it[7] for it in items)
+    assert [s[0] for s in scaled] == dens and all(s[1] == -(-it[1] // s[0]) for s, it in zip(scaled, items) if it[0] == 0)
+
+
 # ------------------------------------------------------------ 6. sanitizers --
 
 def build_pjpeg_san(tmp_path):
