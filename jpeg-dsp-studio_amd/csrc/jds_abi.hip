@@ -430,11 +430,7 @@ void jds_ctx_destroy(jds_ctx* c) {
   c->ent_cf.release();
   c->ent_out.release();
   c->ent_meta.release();
-  c->dec_file.release();
-  c->dec_tab.release();
   c->dec_scr.release();
-  c->dec_st.release();
-  c->dec_iv.release();
   c->dec_mcu.release();
   c->pj_ticks.release();
   c->bat.release();

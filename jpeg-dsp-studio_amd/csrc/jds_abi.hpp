@@ -220,11 +220,11 @@ struct jds_ctx {
   DevBuf chunks;
   DevBuf planes;  // 16x16 path: reconstructed chroma planes
   DevBuf ent[8], ent_hdr, ent_tab, ent_cf, ent_out, ent_meta;  // entropy coder (jds_encode_jfif)
-  DevBuf dec_file, dec_tab, dec_scr, dec_st;  // entropy decoder (jds_decode_jfif): file, tables, scratch, status
-  DevBuf dec_iv;                              // its restart interval table
-  DevBuf dec_mcu;                             // interleaved scans (jds_decode_jpeg): MCU descriptor, DC staging array
-  // jds_jpeg_batch_to_rgb: everything a batch uploads (file bytes, table sets, MCU and inverse records, tile maps,
-  // interval lists, initial status words) is gathered in one pinned host buffer and copied once to bat
+  // foreign files (batch_run, jds_abi_jpeg.hip; a single-file call is a batch of one): the decode kernels'
+  // scratch and the DC staging array of the interleaved scans; everything a run uploads (file bytes, table
+  // sets, MCU and inverse records, tile maps, interval lists, initial status words) is gathered in one
+  // pinned host buffer and copied once to bat
+  DevBuf dec_scr, dec_mcu;
   DevBuf bat;
   DevBuf mcu_up, mcu_scr;  // interleaved-scan writer (jds_jpeg_transcode): its uploads (records, segment table, prefixes), scratch
   void* bat_host = nullptr;

@@ -111,78 +111,16 @@ static bool dec_tables(const jds_jfif_huff* huff, HuffDecTab* tabs) {
 }
 static const char* const DHT_OVERSUBSCRIBED = "DHT: BITS over-subscribe the code space";
 
-// Upload one parsed file and decode it into c->ent_cf (device coefficients).
-// jf: its scans (jds_dec_jobs.hpp); m: the MCU record of an interleaved scan,
-// else null.  The status word and the propagation rounds come back.
-static int decode_dev(jds_ctx* c, const uint8_t* data, int64_t len, const jds_jfif_huff* huff, const DecJobFile& jf,
-                      const HdMcu* m, int64_t n_coeffs, uint32_t* status, uint32_t* rounds_out) {
-  hipStream_t s = c->stream;
-  HuffDecTab tabs[4];
-  if (!dec_tables(huff, tabs)) return fail(JDS_EINVAL, "%s", DHT_OVERSUBSCRIBED);
-  int lane_max;
-  rst_constants(&lane_max);
-  std::vector<DecScan> sc;
-  std::vector<RstIv> ivs;
-  const DecJobsResult jr = dec_jobs_build(data, jf, FilePlace{0, 0, 0, 0}, lane_max, sc, ivs, g_err, sizeof g_err);
-  if (jr) return jr == DEC_JOBS_MARKERS ? JDS_EINVAL : JDS_ENOTSUP;
-  if (sc.size() > 0x7fffffffull) return fail(JDS_ENOTSUP, "too many restart intervals");
-  const int nsc = (int)sc.size();
-  int max_ngrp = 0;
-  const long long ng = dec_layout(sc.data(), nsc, &max_ngrp);
-  if (ng < 0) return fail(JDS_ENOTSUP, "scan too long");
-  // interleaved: the MCU record, then the DC staging array of the scan's blocks
-  const size_t dcs_off = (sizeof(HdMcu) + 15) & ~(size_t)15, dcs_bytes = m ? sizeof(int16_t) * (size_t)jf.scan[0].nblocks : 0;
-  HIP_TRY(c->dec_file.ensure((size_t)len));
-  HIP_TRY(c->dec_tab.ensure(sizeof tabs));
-  HIP_TRY(c->dec_scr.ensure(dec_scratch_bytes(ng, nsc)));
-  HIP_TRY(c->dec_st.ensure(16));
-  HIP_TRY(c->dec_iv.ensure(sizeof(RstIv) * ivs.size()));
-  if (m) HIP_TRY(c->dec_mcu.ensure(dcs_off + dcs_bytes));
-  if (!ivs.empty())
-    HIP_TRY(hipMemcpyAsync(c->dec_iv.p, ivs.data(), sizeof(RstIv) * ivs.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(c->ent_cf.ensure((size_t)n_coeffs * sizeof(int16_t)));
-  HIP_TRY(hipMemcpyAsync(c->dec_file.p, data, (size_t)len, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(c->dec_tab.p, tabs, sizeof tabs, hipMemcpyHostToDevice, s));
-  const HdMcu* mcu_dev = m ? (const HdMcu*)c->dec_mcu.p : nullptr;
-  int16_t* dcs = m ? (int16_t*)((char*)c->dec_mcu.p + dcs_off) : nullptr;
-  if (m) {
-    HIP_TRY(hipMemcpyAsync(c->dec_mcu.p, m, sizeof *m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(dcs, 0, dcs_bytes, s));
-  }
-  HIP_TRY(hipMemsetAsync(c->dec_st.p, 0, 16, s));
-  HIP_TRY(hipStreamSynchronize(s));  // tabs (and the caller's m) are stack objects
-  unsigned rounds = 0;
-  int too_many = 0;
-  // (zero-fills the coefficients; with no descriptors that is all it does, and rounds stays 0)
-  HIP_TRY(dec_run((const uint8_t*)c->dec_file.p, sc.data(), nsc, ng, max_ngrp, (const HuffDecTab*)c->dec_tab.p,
-                  c->dec_scr.p, (int16_t*)c->ent_cf.p, n_coeffs, (uint32_t*)c->dec_st.p, s, &rounds, &too_many,
-                  mcu_dev, dcs));
-  if (too_many) return fail(JDS_EHIP, "entropy decode: propagation did not settle within %d rounds", max_ngrp);
-  HIP_TRY(launch_dec_rst((const uint8_t*)c->dec_file.p, (const RstIv*)c->dec_iv.p, (long long)ivs.size(),
-                         (const HuffDecTab*)c->dec_tab.p, (int16_t*)c->ent_cf.p, (uint32_t*)c->dec_st.p, s, mcu_dev));
-  uint32_t st = 0;
-  HIP_TRY(hipMemcpyAsync(&st, c->dec_st.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *status = st;
-  *rounds_out = rounds;
-  if (st) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(st), st);
-  return JDS_OK;
-}
-
-// A parsed file of either scan form into c->ent_cf.
-static int decode_jpeg_dev(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
-  const HdMcu m = hd_jpeg_mcu(info);
-  return decode_dev(c, data, len, info->huff, dec_jobs_of(info), info->interleaved ? &m : nullptr,
-                    info->coeffs_needed, &info->status, &info->rounds);
-}
+// A parsed file of either profile and scan form into c->ent_cf: the batch of
+// one (defined behind batch_run).  Fills info->status and info->rounds.
+static int decode_one(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info);
 
 // jds_decode_jpeg / _jfif once the file is parsed.
 static int decode_parsed(jds_ctx* c, const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap,
                          jds_jpeg_info* info) {
   int rc;
   if ((rc = check_coef_cap(coeffs, coeffs_cap, info->coeffs_needed))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  if ((rc = decode_one(c, data, len, info))) return rc;
   HIP_TRY(hipMemcpy(coeffs, c->ent_cf.p, (size_t)info->coeffs_needed * sizeof(int16_t), hipMemcpyDeviceToHost));
   return JDS_OK;
 }
@@ -232,7 +170,7 @@ static int decompress_parsed(jds_ctx* c, const uint8_t* data, int64_t len, uint8
   int rc;
   if ((rc = check_tables(&prm))) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
+  if ((rc = decode_one(c, data, len, info))) return rc;
   return inverse_of_decoded(c, &prm, info->H, info->W, info->coeffs_needed, rgb_out, coeffs);
 }
 
@@ -371,7 +309,7 @@ int jds_jpeg_to_rgb_scaled(jds_ctx* c, const uint8_t* data, int64_t len, uint8_t
   JInvArgs a;
   if ((rc = jpeg_inv_args(info, &a))) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: rgb_out is not written)
+  if ((rc = decode_one(c, data, len, info))) return rc;  // (a defective scan: rgb_out is not written)
   uint8_t* dst = rgb_out;
   if (!rgb_on_device) {
     HIP_TRY(c->out.ensure(nimg));
@@ -433,6 +371,7 @@ int jds_selftest_jpeg_window(int32_t d0, int32_t d1, int32_t dst_n, int32_t src_
 // form through the two decode groups and the restart-interval lanes.
 struct BaselineFront : BatchFront {
   unsigned rounds = 0;  // the batch's propagation rounds, once it has run
+  const char* too_long = "batch too long for one decode";  // (a single call names its scan)
   int parse(int, const uint8_t* data, int64_t len, jds_jpeg_info* frame) override {
     return jds_jpeg_parse(data, len, frame);
   }
@@ -492,7 +431,7 @@ struct BaselineFront : BatchFront {
       return fail(JDS_ENOTSUP, "too many restart intervals");
     ng_il = dec_layout(sc_il.data(), (int)sc_il.size(), &mx_il);
     ng_pl = dec_layout(sc_pl.data(), (int)sc_pl.size(), &mx_pl);
-    if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "batch too long for one decode");
+    if (ng_il < 0 || ng_pl < 0) return fail(JDS_ENOTSUP, "%s", too_long);
     o_tabs = j.add(tabs);
     o_mcu = j.add(mcus);
     o_ivil = j.add(iv_il);
@@ -783,6 +722,35 @@ int batch_run(jds_ctx* c, BatchPlan& bp, BatchFront& fe, const uint8_t* const* d
   return JDS_OK;
 }
 
+int single_result(int item_rc, uint32_t status) {
+  if (item_rc) {
+    std::string m = g_err;
+    if (m.rfind("file 0: ", 0) == 0) m = m.substr(8);
+    return fail(item_rc, "%s", m.c_str());
+  }
+  if (status) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(status), status);
+  return JDS_OK;
+}
+
+// The one way a single baseline file reaches the device: the plan of its frame
+// (no second parse, none of the renderings' checks) through batch_run without
+// the inverse; the single-image renderings and the writer follow in the callers.
+// The front end's HD_RESTART for DEC_JOBS_MARKERS is never this call's result:
+// the parser that filled *info counted in each scan exactly the RSTm markers
+// next_rst finds, one fewer than its intervals, so the builder finds them all.
+static int decode_one(jds_ctx* c, const uint8_t* data, int64_t len, jds_jpeg_info* info) {
+  BaselineFront fe;
+  fe.too_long = "scan too long";
+  int rc;
+  if ((rc = fe.check(0, info))) return rc;  // (before anything is uploaded)
+  BatchPlan bp(*info);
+  jds_jpeg_batch_item it;  // (its status is all a run writes)
+  if ((rc = batch_run(c, bp, fe, &data, &len, nullptr, 0, nullptr, &it, false))) return rc;
+  info->status = it.status;
+  info->rounds = fe.rounds;
+  return single_result(JDS_OK, it.status);
+}
+
 int jds_jpeg_batch_to_rgb(jds_ctx* c, const uint8_t* const* data, const int64_t* lens, int32_t n, uint8_t* rgb,
                           int64_t rgb_cap, int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items,
                           uint32_t* rounds_out) {
@@ -1065,25 +1033,21 @@ static int mcu_emit(jds_ctx* c, const McuRun& r, const std::vector<long long>& f
   return JDS_OK;
 }
 
-// One job whose coefficients are in c->ent_cf, to host memory.
+// One job whose coefficients are in c->ent_cf, to host memory: the writer's
+// batch of one, packed at 1, so *out_len is the exact length also where the
+// buffer is too small, and a job that is not baseline-codable is JDS_EINVAL.
 static int mcu_single(jds_ctx* c, McuJob& job, int32_t optimize, uint8_t* out, int64_t out_cap, int64_t* out_len,
                       const XfSet* xf = nullptr) {
   std::vector<McuJob> jobs(1);
   jobs[0] = std::move(job);
-  McuRun r;
+  jds_jpeg_transcode_item it;
+  memset(&it, 0, sizeof it);
+  int64_t need = 0;
   const CtxMarkScope marks_(c, c->stream);
-  int rc = mcu_code(c, jobs, optimize, &r, xf);
-  if (rc) return rc;
-  if (r.len[0] == 0) return fail(JDS_EINVAL, "%s", MCU_NOT_CODABLE);
-  *out_len = r.len[0];
-  if (r.len[0] > out_cap || !out)
-    return fail(JDS_EINVAL, "output buffer too small: %lld bytes needed", (long long)r.len[0]);
-  HIP_TRY(c->ent_out.ensure((size_t)r.len[0]));
-  const std::vector<long long> fout(1, 0ll);
-  if ((rc = mcu_emit(c, r, fout, (uint8_t*)c->ent_out.p))) return rc;
-  HIP_TRY(hipMemcpyAsync(out, c->ent_out.p, (size_t)r.len[0], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return JDS_OK;
+  const int rc = mcu_write_batch(c, jobs, {0}, optimize, xf, out, out_cap, 0, &it, &need, [](int, const char*) {}, 1);
+  if (it.rc) return it.rc;
+  if (it.out_len) *out_len = it.out_len;
+  return rc;
 }
 
 int jds_encode_jpeg(jds_ctx* c, const jds_jpeg_info* info, const int16_t* coeffs, int32_t optimize,
@@ -1108,8 +1072,7 @@ int jds_jpeg_transcode(jds_ctx* c, const uint8_t* data, int64_t len, int32_t opt
   McuJob job;
   if ((rc = mcu_job_geo(info, 0, &job))) return rc;
   if ((rc = mcu_job_splice(data, len, &job))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  if ((rc = decode_one(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
   return mcu_single(c, job, optimize, out, out_cap, out_len);
 }
 
@@ -1147,15 +1110,32 @@ static int xf_prepare(const uint8_t* data, int64_t len, const jds_jpeg_info* inf
   return JDS_OK;
 }
 
+// The writer's job of a transformed file (x.op is not none) whose source planes
+// start at src_off of c->ent_cf: the destination planes at *xcur, which moves on
+// to the next xf_align'ed place, the record added to xs, the edited prefix.
+static int xf_job(XfJob& x, int64_t src_off, int64_t* xcur, XfSet* xs, McuJob* j) {
+  const int rc = mcu_job_geo(&x.plan.dst, *xcur, j);
+  if (rc) return rc;
+  XfFile rec = x.plan.rec;
+  for (int cc = 0; cc < 3; ++cc) {
+    rec.soff[cc] += src_off;
+    rec.doff[cc] += *xcur;
+  }
+  xs->add(rec);
+  *xcur += xf_align(x.plan.dst.coeffs_needed);
+  j->pfx = std::move(x.pfx);
+  return JDS_OK;
+}
+
 // The writer over a batch's jobs, whose coefficients are in c->ent_cf (job k is
 // item job_item[k]): its launches, the files packed in job order at multiples
-// of 256 into out (jds_jpeg_batch_transcode's contract) with out_off / out_len
+// of `align` into out (jds_jpeg_batch_transcode's contract: 256) with out_off / out_len
 // of their items, and rc for a job that is not baseline-codable, of which
 // bad(item, message) hears.  Synchronous.
 int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int>& job_item, int32_t optimize,
-                           const XfSet* xf, uint8_t* out, int64_t out_cap, int32_t out_on_device,
-                           jds_jpeg_transcode_item* items, int64_t* out_bytes,
-                           const std::function<void(int, const char*)>& bad) {
+                    const XfSet* xf, uint8_t* out, int64_t out_cap, int32_t out_on_device,
+                    jds_jpeg_transcode_item* items, int64_t* out_bytes,
+                    const std::function<void(int, const char*)>& bad, int64_t align) {
   hipStream_t s = c->stream;
   McuRun r;
   int rc;
@@ -1172,7 +1152,7 @@ int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int
     fout[k] = cur;
     items[i].out_off = cur;
     items[i].out_len = r.len[k];
-    cur = (cur + r.len[k] + 255) & ~(int64_t)255;
+    cur = (cur + r.len[k] + align - 1) & -align;
   }
   *out_bytes = cur;
   if (cur > 0 && (!out || out_cap < cur))
@@ -1233,22 +1213,10 @@ static int batch_transcode(jds_ctx* c, const uint8_t* const* data, const int64_t
   return batch_transcode_tail(
       c, bp, bi, n,
       [&](size_t k, int i, McuJob* j) {
-        int r;
-        if (xform && xj[(size_t)i].op != JDS_XF_NONE) {  // the writer sees the destination planes
-          XfJob& x = xj[(size_t)i];
-          if ((r = mcu_job_geo(&x.plan.dst, xcur, j))) return r;
-          XfFile rec = x.plan.rec;
-          for (int cc = 0; cc < 3; ++cc) {
-            rec.soff[cc] += bp.recs[k].coef_off;
-            rec.doff[cc] += xcur;
-          }
-          xs.add(rec);
-          xcur += xf_align(x.plan.dst.coeffs_needed);
-          j->pfx = std::move(x.pfx);
-          return JDS_OK;
-        }
-        if ((r = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, j))) return r;
-        return mcu_job_splice(data[i], lens[i], j);
+        if (xform && xj[(size_t)i].op != JDS_XF_NONE)  // the writer sees the destination planes
+          return xf_job(xj[(size_t)i], bp.recs[k].coef_off, &xcur, &xs, j);
+        const int r = mcu_job_geo(&bp.info[(size_t)i], bp.recs[k].coef_off, j);
+        return r ? r : mcu_job_splice(data[i], lens[i], j);
       },
       &xs, optimize, out, out_cap, out_on_device, items, out_bytes);
 }
@@ -1327,24 +1295,17 @@ int jds_jpeg_transform(jds_ctx* c, const uint8_t* data, int64_t len, int32_t op,
   XfJob x;
   if ((rc = xf_prepare(data, len, info, op, &x))) return rc;
   McuJob job;
+  XfSet xs;
+  int64_t xcur = xf_align(info->coeffs_needed);  // the transformed planes follow the decoder's
   if (x.op == JDS_XF_NONE) {  // jds_jpeg_transcode
     if ((rc = mcu_job_geo(info, 0, &job))) return rc;
     job.pfx = std::move(x.pfx);
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;
-    return mcu_single(c, job, optimize, out, out_cap, out_len);
+  } else if ((rc = xf_job(x, 0, &xcur, &xs, &job))) {
+    return rc;
   }
-  const int64_t base = xf_align(info->coeffs_needed);
-  if ((rc = mcu_job_geo(&x.plan.dst, base, &job))) return rc;
-  job.pfx = std::move(x.pfx);
-  XfFile rec = x.plan.rec;
-  for (int cc = 0; cc < 3; ++cc) rec.doff[cc] += base;
-  XfSet xs;
-  xs.add(rec);
   HIP_TRY(hipSetDevice(c->device));
-  // the transformed planes follow the decoder's: sized before the decode fills the buffer
-  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)(base + x.plan.dst.coeffs_needed)));
-  if ((rc = decode_jpeg_dev(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
+  HIP_TRY(c->ent_cf.ensure(sizeof(int16_t) * (size_t)xcur));  // sized before the decode fills the buffer
+  if ((rc = decode_one(c, data, len, info))) return rc;  // (a defective scan: nothing is written)
   return mcu_single(c, job, optimize, out, out_cap, out_len, &xs);
 }
 

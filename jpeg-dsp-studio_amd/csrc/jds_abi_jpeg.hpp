@@ -45,6 +45,13 @@ struct BatchPlan : BatchBad {
   bool any_scaled = false;
   std::vector<int> denom;  // per file: the denominator it is decoded at
   int64_t rgb_bytes = 0, coef_entries = 0;
+  BatchPlan() {}
+  // One parsed frame, for a run without the inverse (the single-file calls): no second parse and none
+  // of the renderings' checks, so the record has no launch arguments and the maps are their sentinels.
+  explicit BatchPlan(const jds_jpeg_info& frame)
+      : info{frame}, rec_of{0}, file_of{0}, recs(1), denom{1}, coef_entries(frame.coeffs_needed) {
+    for (std::vector<JInvMap>& m : map) m.assign(1, JInvMap{0, -1});
+  }
 };
 
 // A run as its front end sees it.
@@ -127,6 +134,9 @@ int batch_run(jds_ctx* c, BatchPlan& bp, BatchFront& fe, const uint8_t* const* d
               int32_t rgb_on_device, int16_t* coeffs, jds_jpeg_batch_item* items, bool inverse,
               int32_t render = JDS_RENDER_REFERENCE,
               const std::function<int(const uint32_t*, hipStream_t)>* after = nullptr);
+// A batch of one as a single call's result: the item's error (batch_note's
+// "file 0: <message>" -> the message), or its scan data's defect, is the call's.
+int single_result(int item_rc, uint32_t status);
 // Behind a run without the inverse: the transcode items from the batch's, the
 // writer over the files that decoded (job_of(k, i, job): record k's, file i's
 // geometry and header prefix; xf, nullable: the transformed files it adds to),
@@ -141,9 +151,11 @@ int mcu_job_geo(const jds_jpeg_info* info, int64_t coef_off, McuJob* j);
 // The header prefix of a transcoded file: every segment before the first SOS except DHT and DRI.
 int mcu_job_splice(const uint8_t* data, int64_t len, McuJob* j);
 // The writer over a batch's jobs, whose coefficients are in c->ent_cf (job k is
-// item job_item[k]); jds_jpeg_batch_transcode's packing and item contract.
+// item job_item[k]); jds_jpeg_batch_transcode's packing (files at multiples of
+// `align`, a power of two: 1 for a single call, whose *out_bytes is then its
+// file's exact length) and item contract.
 int mcu_write_batch(jds_ctx* c, std::vector<McuJob>& jobs, const std::vector<int>& job_item, int32_t optimize,
                     const XfSet* xf, uint8_t* out, int64_t out_cap, int32_t out_on_device,
                     jds_jpeg_transcode_item* items, int64_t* out_bytes,
-                    const std::function<void(int, const char*)>& bad);
+                    const std::function<void(int, const char*)>& bad, int64_t align = 256);
 }

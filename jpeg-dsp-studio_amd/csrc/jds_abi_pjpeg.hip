@@ -4,8 +4,6 @@
 // writer, which take the decoded coefficients as they take a baseline file's.
 //
 // Host side only: descriptors (jds_pjpeg_parse.hpp), uploads and launches.
-#include <string>
-
 #include "jds_abi.hpp"
 #include "jds_abi_jpeg.hpp"
 #include "jds_jpeg_ljs.hpp"
@@ -29,17 +27,10 @@ static int pj_parse_file(const uint8_t* data, int64_t len, jds_pjpeg_info* out) 
 
 int jds_pjpeg_parse(const uint8_t* data, int64_t len, jds_pjpeg_info* out) { return pj_parse_file(data, len, out); }
 
-// A batch of one: the item's error (batch_note's "file 0: <message>" -> the
-// message), or its scan data's defect, is the call's.
+// A batch of one (single_result, jds_abi_jpeg.hip), its status into both places of the info.
 static int pj_single_result(int item_rc, uint32_t status, jds_pjpeg_info* info) {
   info->status = info->frame.status = status;
-  if (item_rc) {
-    std::string m = g_err;
-    if (m.rfind("file 0: ", 0) == 0) m = m.substr(8);
-    return fail(item_rc, "%s", m.c_str());
-  }
-  if (status) return fail(JDS_EINVAL, "defective scan data: %s (status 0x%x)", hd_status_text(status), status);
-  return JDS_OK;
+  return single_result(item_rc, status);
 }
 
 int jds_selftest_pjpegdec(const uint8_t* data, int64_t len, int16_t* coeffs, int64_t coeffs_cap, jds_pjpeg_info* info) {

@@ -2,8 +2,8 @@
 //
 // Host only and HIP-free (plain C++, like jds_jpeg_parse.hpp):
 // the index arithmetic that decides which bytes every decode workgroup reads
-// and where its blocks go.  The drivers in jds_abi_jpeg.hip call it for single
-// files and batches; tools/dec_jobs_san.cpp runs it under the host sanitizers.
+// and where its blocks go.  The batch driver in jds_abi_jpeg.hip calls it (a
+// single file is its batch of one); tools/dec_jobs_san.cpp runs it under the host sanitizers.
 #pragma once
 
 #include <stdint.h>
@@ -16,7 +16,7 @@
 namespace jds {
 
 // Where a file's descriptors point in launches that serve several files
-// (jds_jpeg_batch_to_rgb); the single-file calls pass zeros.
+// (jds_jpeg_batch_to_rgb); a single-file call is the batch of one, placed at zeros.
 struct FilePlace {
   int file;            // its table set (tabs + 4 * file), MCU record (mcu + file) and status word
   long long data_off;  // its first byte, from the files base

@@ -349,7 +349,8 @@ JDS_HDI uint32_t hd_write_lane(const Src& src, const TC& tc, uint64_t entry, uin
 // decode tables (tabs + 4 * file) and, interleaved, its MCU descriptor
 // (mcu + file), whose off[] then include the file's place in the batch's
 // coefficient buffer; a non-interleaved descriptor's dc_tab / ac_tab already
-// index the whole table array.  Single-file calls and plans leave file at 0.
+// index the whole table array.  Plans leave file at 0; so does a single-file
+// call, the batch of one.
 struct DecScan {
   long long data_off;  // the scan's stuffed bytes, from the files base
   long long nbytes;

@@ -206,7 +206,7 @@ def test_gpu_existing_paths_unchanged():
 
 
 def test_gpu_one_context_alternates_scan_forms():
-    """The single-file driver serves both scan forms over the same context buffers: lanes,
+    """The single-file calls serve both scan forms over the same context buffers: lanes,
     one descriptor, and descriptors per interval, interleaved and not, in turn on one
     context.  A stale interval table, MCU record or DC staging array of the previous file
     would show; the first file decodes the same again at the end."""
@@ -235,6 +235,71 @@ def test_gpu_one_context_alternates_scan_forms():
         exp = (entropy.host_decode_jfif if jfif else entropy.host_decode_jpeg)(data)[0]
         assert np.array_equal(cf, exp)
     assert np.array_equal(got[0], got[-1])
+
+
+def test_gpu_one_context_single_and_batch_calls_in_turn():
+    """A single-file call is the batch driver's batch of one, so on one context the single calls
+    and the batch calls take turns on the same upload buffer, pinned staging, scratch and DC
+    staging array: decode, batch render, decode of the other scan form by descriptors per
+    interval, render into a device tensor, batch transcode, transcode, transform, and the first
+    decode again.  Every result is the host model's; the first and the last are equal."""
+    import ctypes as C
+    import torch
+    from jds import _abi, codec, entropy
+    lib, lane_max = _abi.lib(), entropy.restart_info()[1]
+    rstrow, small, rst2 = (fixture(n)[0] for n in ('p48x48_420_opt_rstrow', 'p9x9_444', 'p40x72_420_rst2'))
+    ny, nc = rr.counts(40, 56, '4:2:0')
+    plain5 = rr.encode_jfif_rst(fixture('p40x72_420_rst2')[1][:(ny + 2 * nc) * 64], 40, 56, '4:2:0', Q50, 5)[0]
+    ny, nc = rr.counts(96, 104, '4:2:0')      # 156 luma blocks: intervals of 130 and 26 blocks, each a descriptor
+    wide = rr.encode_jfif_rst(np.random.default_rng(96).integers(-9, 10, (ny + 2 * nc) * 64).astype(np.int16), 96, 104,
+                              '4:2:0', Q50, lane_max + 2)[0]
+    d = entropy.parse_jpeg(rstrow)
+    assert d['interleaved'] and d['scans'][0]['restart_interval'] * d['mcu']['blocks'] <= lane_max
+    assert not entropy.parse_jpeg(wide)['interleaved'] and ny > lane_max + 2 and (d['H'], d['W']) == (48, 48)
+
+    def host_image(data):
+        p = entropy.parse_jpeg(data)
+        return codec.host_jpeg_render(entropy.host_decode_jpeg(data)[0], p['H'], p['W'], p['mode'], p['qtables'],
+                                      p['grids'], render='reference')
+
+    def decode(ctx, data):
+        a, p, n = entropy._bytes_arg(data)
+        info = _abi.JpegInfo()
+        _abi.check(lib.jds_jpeg_parse(p, n, C.byref(info)))
+        cf = np.full(int(info.coeffs_needed), 0x5555, np.int16)
+        _abi.check(lib.jds_decode_jpeg(ctx.handle, p, n, cf.ctypes.data, cf.size, C.byref(info)))
+        return cf
+
+    def rewritten(ctx, data, xf=None):
+        a, p, n = entropy._bytes_arg(data)
+        info = _abi.JpegInfo()
+        if xf is None:
+            return entropy._grown(lambda o, cap, m: lib.jds_jpeg_transcode(ctx.handle, p, n, 1, o.ctypes.data, cap,
+                                                                           C.byref(m), C.byref(info)), 2 * n)
+        return entropy._grown(lambda o, cap, m: lib.jds_jpeg_transform(ctx.handle, p, n, _abi.xf_code(xf), 1, o.ctypes.data,
+                                                                       cap, C.byref(m), C.byref(info)), 2 * n)
+
+    with _abi.lease(0) as ctx:
+        first = decode(ctx, rstrow)
+        imgs = codec.jpeg_batch_to_rgb([small, plain5, rst2], ctx=ctx)
+        cf_wide = decode(ctx, wide)
+        a, p, n = entropy._bytes_arg(rst2)
+        info = _abi.JpegInfo()
+        dev = torch.full((40, 72, 3), 0xA5, dtype=torch.uint8, device='cuda:0')
+        torch.cuda.synchronize()
+        _abi.check(lib.jds_jpeg_to_rgb(ctx.handle, p, n, C.c_void_p(int(dev.data_ptr())), dev.numel(), 1, None, C.byref(info)))
+        outs = codec.jpeg_batch_transcode([rstrow, plain5], ctx=ctx)
+        one = rewritten(ctx, small)
+        turned = rewritten(ctx, rstrow, 'rot90')
+        last = decode(ctx, rstrow)
+    assert np.array_equal(first, entropy.host_decode_jpeg(rstrow)[0]) and np.array_equal(first, last)
+    for img, data in zip(imgs, (small, plain5, rst2)):
+        assert np.array_equal(img, host_image(data))
+    assert np.array_equal(cf_wide, entropy.host_decode_jpeg(wide)[0])
+    assert np.array_equal(dev.cpu().numpy(), host_image(rst2))
+    assert outs == [entropy.host_transcode_jpeg(f) for f in (rstrow, plain5)]
+    assert one == entropy.host_transcode_jpeg(small)
+    assert turned == entropy.host_transform_jpeg(rstrow, 'rot90')
 
 
 def test_gpu_own_profile_files_through_both_decode_calls():

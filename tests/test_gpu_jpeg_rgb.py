@@ -183,6 +183,38 @@ def test_gpu_defective_files_raise_and_leave_out_alone(name):
         assert np.array_equal(codec.jpeg_to_rgb(data), good)        # the same pooled context
 
 
+def test_gpu_defective_file_status_and_device_output_on_one_context():
+    """jds_jpeg_to_rgb_render into the caller's device buffer on a leased context: a defective
+    scan returns before the single-image rendering (the batch renderings would write zeros), so
+    the buffer keeps its fill; info.status is the host model's word; the same context then
+    renders the good file."""
+    import ctypes as C
+    import re
+    import torch
+    from jds import _abi, entropy
+    lib = _abi.lib()
+    data, exp = fixture('p24x40_420')
+    d = ir.decode(data)
+    good = oracle_image(exp, d['H'], d['W'], d['mode'], d['qtables'], d['grids'])
+    with _abi.lease(0) as ctx:
+        for kind, f in _defects(data).items():
+            with pytest.raises(ValueError, match='defective scan data: .* \\(status 0x') as host:
+                entropy.host_decode_jpeg(f)
+            out = torch.full((d['H'], d['W'], 3), 0xA5, dtype=torch.uint8, device='cuda:0')
+            torch.cuda.synchronize()
+            for image, want in ((f, int(re.search(r'status 0x([0-9a-f]+)', str(host.value)).group(1), 16)), (data, 0)):
+                a, p, n = entropy._bytes_arg(image)
+                info = _abi.JpegInfo()
+                rc = lib.jds_jpeg_to_rgb_render(ctx.handle, p, n, C.c_void_p(int(out.data_ptr())), out.numel(), 1, None,
+                                                C.byref(info), _abi.render_code('reference'))
+                assert int(info.status) == want, kind
+                if want:
+                    assert rc == _abi.JDS_EINVAL and bool((out == 0xA5).all()), kind
+                    assert re.match(r'defective scan data: .* \(status 0x', lib.jds_last_error().decode())
+                else:
+                    assert rc == 0 and np.array_equal(out.cpu().numpy(), good), kind
+
+
 def test_gpu_with_info():
     from jds import codec, entropy
     data, exp = fixture('p33x35_422')

@@ -177,6 +177,36 @@ def test_gpu_not_codable_agrees_with_host_model():
         codec.jpeg_batch_transcode([good, src, good])
 
 
+def test_gpu_single_calls_report_and_take_the_exact_length():
+    """The single calls run the batch writer packed at 1, not at 256: a buffer of exactly the
+    file's length suffices, and one byte less is JDS_EINVAL with *out_len the exact length
+    (jds_jpeg_transcode; jds_rgb_to_jpeg on a 16 x 16 image)."""
+    import ctypes as C
+    from jds import _abi, entropy
+    lib = _abi.lib()
+    src = tc.pillow(17, 33, '4:2:0', 50, False, True)
+    a, p, n = entropy._bytes_arg(src)
+    info = _abi.JpegInfo()
+    img = np.random.default_rng(16).integers(0, 256, (16, 16, 3), dtype=np.uint8)
+    buf = io.BytesIO()
+    Image.fromarray(img).save(buf, 'JPEG', quality=75, subsampling=2)      # (what jds_rgb_to_jpeg writes, byte for byte)
+    pil = buf.getvalue()
+    with _abi.lease(0) as ctx:
+        calls = ((entropy.host_transcode_jpeg(src, True),
+                  lambda o, cap, m: lib.jds_jpeg_transcode(ctx.handle, p, n, 1, o.ctypes.data, cap, C.byref(m), C.byref(info))),
+                 (pil,
+                  lambda o, cap, m: lib.jds_rgb_to_jpeg(ctx.handle, C.c_void_p(img.ctypes.data), 0, 16, 16, 75,
+                                                        _abi.JPEG_MODE_CODES['4:2:0'], 0, o.ctypes.data, cap, C.byref(m))))
+        for want, call in calls:
+            assert len(want) % 256                           # (the batch's packing would ask for more)
+            out, m = np.full(len(want), 0xA5, np.uint8), C.c_int64(-1)
+            assert call(out, len(want) - 1, m) == _abi.JDS_EINVAL and m.value == len(want)
+            assert 'output buffer too small: %d bytes needed' % len(want) in lib.jds_last_error().decode()
+            assert bool((out == 0xA5).all())
+            m = C.c_int64(-1)
+            assert call(out, len(want), m) == 0 and m.value == len(want) and out.tobytes() == want
+
+
 def test_gpu_stuffing_agrees_with_host_model():
     from jds import entropy
     src = tc.pillow(64, 48, '4:2:0', 100, False, False, noise=True)
