@@ -597,7 +597,10 @@ int jds_decompress_jpeg(jds_ctx* ctx, const uint8_t* data, int64_t len, uint8_t*
  * jds_jpeg_to_rgb: parse, decode and that launch on the context's stream, then
  *   the image into rgb_out: host memory, or with rgb_on_device != 0 a device
  *   buffer of the context's device (written in place by the kernel).
- *   Synchronous either way.  coeffs: NULL, or host memory of coeffs_needed
+ *   Synchronous either way.  Here and at every *_on_device parameter of this
+ *   header the context's stream waits for no other stream: a device buffer
+ *   must be idle, or the work queued on it ordered before the call.
+ *   coeffs: NULL, or host memory of coeffs_needed
  *   entries.  The error contract of jds_decode_jpeg; on a defective scan
  *   (JDS_EINVAL naming the defect) rgb_out is not written and the context stays
  *   usable. */

@@ -284,6 +284,7 @@ def jpeg_to_rgb(data, device: int = 0, with_info: bool = False, out=None, render
         if tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.element_size() != 1:
             raise ValueError(f'out must be a contiguous uint8 ({H}, {W}, 3) device tensor')
         img, dst, on_dev = out, int(out.data_ptr()), 1
+        _torch_settled(device)
     cf = np.empty(int(info.coeffs_needed), np.int16) if with_info else None
     with lease(device) as ctx:
         if d != 1:
@@ -418,6 +419,7 @@ def _batch_to_rgb(files, device, out, with_info, errors, ctx, render, scale_deno
                 raise ValueError('out must be a contiguous 1-D uint8 device tensor')
             cap = int(buf.numel())
         dst, on_dev = int(buf.data_ptr()), 1
+        _torch_settled(device)
     rounds = C.c_uint32(0)
 
     def run(c):
@@ -575,6 +577,8 @@ def _batch_transcode(files, optimize, out, errors, device, ctx, ops, progressive
         check(rc)
         return buf
 
+    if out is not None:
+        _torch_settled(device)      # (once: torch queues nothing between here and a retry's allocation)
     if ctx is not None:
         buf = attempt(ctx)
     else:
@@ -695,6 +699,7 @@ def pjpeg_to_rgb(data, out=None, render: str = 'libjpeg', scale_denom: int = 1, 
         if tuple(out.shape) != (H, W, 3) or not out.is_contiguous() or out.element_size() != 1:
             raise ValueError(f'out must be a contiguous uint8 ({H}, {W}, 3) device tensor')
         img, dst, on_dev = out, int(out.data_ptr()), 1
+        _torch_settled(device)
     cf = np.empty(int(info.frame.coeffs_needed), np.int16) if with_info else None
     with lease(device) as ctx:
         check(lib().jds_pjpeg_to_rgb(ctx.handle, p, n, C.c_void_p(dst), H * W * 3, on_dev, code, d,
@@ -818,7 +823,10 @@ def _image_arg(image, device: int = 0):
 
 
 def _torch_settled(device: int) -> None:
-    """The context's stream does not wait for torch's: what torch has queued for the images ends first."""
+    """The context's stream does not wait for torch's: what torch has queued on its current stream
+    ends first -- for a source tensor the work that produces it, for a destination tensor (the
+    caller's, or one allocated here, whose block the caching allocator may have recycled from a
+    tensor with work still queued) the work that would otherwise land after this call's."""
     import torch
     torch.cuda.current_stream(device).synchronize()
 
@@ -920,7 +928,6 @@ def rgb_batch_to_jpeg(images, quality=75, subsampling='4:2:0', optimize: bool = 
             keep = torch.cat([a[0].reshape(-1) for a in args])
             base, offs = int(keep.data_ptr()), [0] + list(np.cumsum(sizes[:-1]))
         on_dev = 1
-        _torch_settled(device)
     else:                                        # host arrays (a device tensor among them comes to the host)
         offs = [0] + list(np.cumsum([-(-s // 256) * 256 for s in sizes[:-1]])) if n else []
         keep = np.zeros(max(sum(-(-s // 256) * 256 for s in sizes), 1), np.uint8)
@@ -928,6 +935,8 @@ def rgb_batch_to_jpeg(images, quality=75, subsampling='4:2:0', optimize: bool = 
             src = a[0].cpu().numpy() if a[2] else a[0]
             keep[o:o + s] = src.reshape(-1)
         base, on_dev = keep.ctypes.data, 0
+    if on_dev or out is not None:
+        _torch_settled(device)
     items_in = (_abi.RgbItem * max(n, 1))()
     for i, (a, o) in enumerate(zip(args, offs)):
         items_in[i].rgb_off, items_in[i].H, items_in[i].W = int(o), a[3], a[4]
@@ -1284,7 +1293,9 @@ def psnr_ssim_batch_dev(a_ptrs, b_ptrs, H: int, W: int, device: int = 0, after=N
 
 def magnitude_bits_f32_dev(coeffs_ptr: int, n_coeffs: int, device: int = 0, after=None) -> float:
     """jds_magnitude_bits_f32_dev: NumPy's float32 np.sum of magnitude_bits
-    (utils/metrics.py:77-78) over n_coeffs device-resident int16 coefficients."""
+    (utils/metrics.py:77-78) over n_coeffs device-resident int16 coefficients.
+    after as in psnr_ssim_dev: None = the caller has synchronised the coefficients;
+    a stream handle = wait for that stream's queued work."""
     out = C.c_double()
     with lease(device) as ctx:
         check(lib().jds_magnitude_bits_f32_dev(ctx.handle, int(coeffs_ptr), int(n_coeffs), C.byref(out),
@@ -1295,7 +1306,8 @@ def magnitude_bits_f32_dev(coeffs_ptr: int, n_coeffs: int, device: int = 0, afte
 def magnitude_bits_f32_batch_dev(coeffs_ptr: int, n_items: int, n_coeffs: int, item_stride: int,
                                  device: int = 0, after=None) -> np.ndarray:
     """jds_magnitude_bits_f32_batch_dev: magnitude_bits_f32_dev for n_items
-    coefficient arrays at coeffs_ptr + 2 * i * item_stride bytes, one host wait."""
+    coefficient arrays at coeffs_ptr + 2 * i * item_stride bytes, one host wait
+    (after as magnitude_bits_f32_dev's)."""
     out = np.empty(n_items, np.float64)
     if n_items == 0:
         return out

@@ -268,7 +268,9 @@ def decode_pjpeg(data, device: int = 0, with_status: bool = False) -> dict:
 def decode_pjpeg_dev(data, coeffs_ptr: int, coeffs_cap: int, device: int = 0) -> dict:
     """jds_pjpeg_decode_dev: decode_pjpeg with the coefficients left in the caller's device buffer
     (coeffs_cap int16 entries at coeffs_ptr; entries [0, coeffs_needed) are written) -> parse_pjpeg's
-    dict plus 'status' (never raises for defective scan data)."""
+    dict plus 'status' (never raises for defective scan data).  A raw pointer: the decode runs on the
+    context's stream, which waits for no other, so the caller must have synchronised whatever it
+    queued on that buffer (torch's fill of it, say); the call returns when the entries are written."""
     a, p, n = _bytes_arg(data)
     info = _abi.PjpegInfo()
     with _abi.lease(device) as ctx:

@@ -92,3 +92,92 @@ def test_short_lived_threads_reuse_pooled_contexts():
         _abi.Context.__init__ = orig
     assert created == [], 'each run created a new context (HIP stream + scratch)'
     assert 1 <= _abi.pool_size(0) <= _abi._POOL_MAX
+
+
+# The file-facing calls from two threads: what data-loader workers run.  They share the context
+# pool, each context's staging buffers (grown by whichever call leased it last) and thread-local
+# host tables.  Per thread and round the (H, W) of the files: growing, then shrinking.
+FILE_SHAPES = [
+    [[(9, 9), (17, 23)], [(65, 257), (130, 16), (40, 72), (33, 35), (31, 45)], [(3, 4)]],
+    [[(31, 45), (16, 32), (33, 129)], [(200, 264), (24, 130), (64, 96), (97, 150), (17, 33), (48, 64), (24, 40)],
+     [(16, 16), (37, 53)]],
+]
+TENSOR_SIZE = (16, 16)
+
+
+def _file_jobs(t, r):
+    """Thread t's round r -> [(name, call -> host result, Pillow's item 0)], in that thread's order."""
+    import pjpeg_cases as pc
+    from PIL import Image
+    from jds import codec
+    from test_jpeg_forward_cpu import image, pillow_save
+    from test_jpeg_render_cpu import pillow_file, pillow_pixels
+    from test_resize_cpu import pillow_draft_resize
+    shapes = FILE_SHAPES[t][r]
+    n = len(shapes)
+    base = [pillow_file(h, w, ['4:2:0', '4:4:4', '4:2:2', 'L'][(i + t) % 4]) for i, (h, w) in enumerate(shapes)]
+    prog = [pc.pillow_pair(h, w, [2, 0, 1, 'L'][(i + t) % 4], 0, 75)[1] for i, (h, w) in enumerate(shapes)]
+    imgs = [image(h, w, 'noise', t) for h, w in shapes]
+    modes, quals = [['4:2:0', '4:4:4', '4:2:2'][(i + t) % 3] for i in range(n)], [60 + 15 * t] * n
+    plain = [pillow_save(im, m, q, False) for im, m, q in zip(imgs, modes, quals)]
+    opt0 = pillow_save(imgs[0], modes[0], quals[0], True)
+    dens = [[1, 2, 4, 8][i % 4] for i in range(n)]
+    ops = [['none', 'rot180', 'hflip', 'vflip'][i % 4] for i in range(n)]
+
+    def files_host(views):
+        return [v.cpu().numpy().tobytes() for v in views]
+    jobs = [
+        ('to_rgb', lambda: codec.jpeg_batch_to_rgb(base, render='libjpeg', scale_denom=dens), pillow_pixels(base[0])),
+        ('pjpeg', lambda: [v.cpu().numpy() for v in codec.pjpeg_batch_to_rgb(prog)], pc.pillow_rgb(prog[0])),
+        ('transcode', lambda: files_host(codec.jpeg_batch_transcode(plain, out='device')), opt0),
+        ('encode', lambda: codec.rgb_batch_to_jpeg(imgs, quals, modes, optimize=True), opt0),
+        ('to_tensor', lambda: codec.jpeg_batch_to_tensor(base, TENSOR_SIZE, 'bilinear').cpu().numpy(),
+         pillow_draft_resize(base[0], TENSOR_SIZE, Image.BILINEAR)),
+        ('transform', lambda: codec.jpeg_batch_transform(plain, ops, trim=True), opt0),     # (item 0: 'none')
+    ]
+    k = (3 * t + r) % len(jobs)                              # another order in each thread and round
+    return jobs[k:] + jobs[:k]
+
+
+def _equal(a, b):
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.shape == b.shape and np.array_equal(a, b)
+    if isinstance(a, list):
+        return isinstance(b, list) and len(a) == len(b) and all(_equal(x, y) for x, y in zip(a, b))
+    return a == b
+
+
+def test_two_threads_file_api_equals_single_threaded():
+    from jds import _abi, build
+    build.build()
+    rounds = len(FILE_SHAPES[0])
+    jobs = [[_file_jobs(t, r) for r in range(rounds)] for t in range(len(FILE_SHAPES))]
+    refs = [[[call() for _, call, _ in rj] for rj in tj] for tj in jobs]
+    for tj, tr in zip(jobs, refs):
+        for rj, rr in zip(tj, tr):
+            for (name, _, pil), ref in zip(rj, rr):
+                assert _equal(ref[0], pil), name             # item 0 of every call is Pillow's
+    results = [[None] * rounds for _ in jobs]
+    errors = []
+    start = threading.Barrier(len(jobs))
+
+    def worker(t):
+        try:
+            start.wait()
+            for r in range(rounds):
+                results[t][r] = [call() for _, call, _ in jobs[t][r]]
+        except Exception as e:  # surfaced in the main thread
+            errors.append(e)
+
+    ths = [threading.Thread(target=worker, args=(t,)) for t in range(len(jobs))]
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join(timeout=120)
+    assert not any(th.is_alive() for th in ths), 'a worker thread hung'
+    assert not errors, errors
+    for t, tj in enumerate(jobs):
+        for r, rj in enumerate(tj):
+            for k, (name, _, _) in enumerate(rj):
+                assert _equal(results[t][r][k], refs[t][r][k]), (t, r, name)
+    assert _abi.pool_size(0) <= _abi._POOL_MAX

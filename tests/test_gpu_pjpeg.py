@@ -109,6 +109,7 @@ def _decode_between_guards(f):
     from jds import entropy
     need = entropy.parse_pjpeg(f)['coeffs_needed']
     buf = torch.full((need + 2 * GUARD,), 0x5A5A, dtype=torch.int16, device='cuda')
+    torch.cuda.synchronize()                  # (a raw pointer: the call does not wait for the fill)
     d = entropy.decode_pjpeg_dev(f, buf.data_ptr() + 2 * GUARD, need)
     torch.cuda.synchronize()
     h = buf.cpu().numpy()
